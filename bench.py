@@ -11,13 +11,20 @@ step, max over ranks).  The line carries
   roofline       the dominant part of the step, the FIT: the in-LDS eigen-solves K3 (k_jacobi_solve launches + the Jacobi rounds
                  inside k_brent_warm), algorithmic LDS bytes counted by the kernels themselves over HIP-event launch durations;
   roofline_eval  the evaluation product K2r against the fp64 matrix peak;
+and, with `--full` only:
   cpu_baseline   (N = 1) the oracle - the faithful CPU restatement of the reference - on 16 records + a hull-masked sub-grid,
                  extrapolated to timesteps/s;
 and, at N = 1, secondary objects that are NOT part of `value`: `single_record` (BASELINE configs[1], the latency path: one
 record + 128^3 grid per step, mean / median / max over sixteen distinct records, with the K3 launch figures of that path),
 `roofline_eval_fused` (the fused evaluation kernel with and without the hull pass), `eval_many_timesteps`, `batched_records`
 (configs[2]: 1000 records in one batch).
-`--workload c1` prints the configs[1] line on its own (weak-scaling replica per rank), as rounds 1-3 did at N = 1.
+A plain run (no `--full`) sets up, warms up, times the steps and prints the line: nothing else runs on the host or the GPU.
+`--workload c1` prints the configs[1] line on its own (weak-scaling replica per rank), as rounds 1-3 did at N = 1; its
+`cpu_baseline`, `roofline_eval` (the evaluation kernel on its own), `eval_many_timesteps` and `batched_records` come with `--full`.
+`--dump-outputs DIR` writes, after the timed steps, what the timed path computed in its last step (rank 0's share) as
+DIR/<name>.npy in float64 with every value finite (a NaN of the path as 0, marked 0 in the float32 mask DIR/<name>_finite.npy),
+at most 64 MB in all (fixed, seeded samples of the larger arrays); the inputs are the same seeded synthetic data from run to
+run, so two builds can be compared output for output.
 Inputs (beam geometry, weights/data, query grid, regularisation matrix, hull facets) are resident in HBM before the
 timed region; outputs stay on the device.  Shared parameters are broadcast once from rank 0 over RCCL before the timed
 region; if RCCL was to be used and did not come up, the line says so and the exit status is 3.
@@ -73,10 +80,16 @@ def parse_args():
     ap.add_argument('--records', type=int, default=10000, help='timesteps of workload c3 (all ranks together)')
     ap.add_argument('--grid', type=int, default=128, help='query grid edge of the configs[1] figures (128 -> 128^3 points)')
     ap.add_argument('--c3-grid', type=int, default=256, help='query grid edge of workload c3 (rehearsals: smaller)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-secondary', action='store_true', help='workload c3 at N = 1: skip the secondary objects')
-    ap.add_argument('--no-eval-many', action='store_true', help='skip the secondary many-timesteps evaluation figure')
-    ap.add_argument('--no-batched', action='store_true', help='skip the secondary batched-records figure (configs[2])')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline figure does not need: the CPU baseline (N = 1), the secondary objects '
+                         '(workload c3 at N = 1) and the evaluation kernel on its own, many-timesteps and batched figures '
+                         '(workload c1); the --no-* options below switch parts of it off')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-secondary', action='store_true', help='with --full, workload c3 at N = 1: skip the secondary objects')
+    ap.add_argument('--no-eval-many', action='store_true', help='with --full: skip the secondary many-timesteps evaluation figure')
+    ap.add_argument('--no-batched', action='store_true', help='with --full: skip the secondary batched-records figure (configs[2])')
     ap.add_argument('--batched-records', type=int, default=1000, help='records of the configs[2] figure')
     args = ap.parse_args()
     if args.steps is None:
@@ -103,6 +116,67 @@ def spawn_ranks(n):
     sys.stdout.write(out.decode())
     sys.stdout.flush()
     return max(abs(rc) for rc in rcs)
+
+
+# ---- --dump-outputs: what the timed path computed in its last step ----------------------------------------------------
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _sample_index(n, k, seed):
+    """All of range(n) when n <= k, else a fixed, seeded, sorted sample of k of them."""
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+
+
+def fit_outputs(res, max_records=10000, cov_records=64):
+    """The arrays a caller of the fit receives: coefficients, chi^2, regularisation parameter and rank of the final solve of
+    every record (of a seeded sample of max_records when there are more), and the covariances of a seeded sample of
+    cov_records of those."""
+    rows = _sample_index(res['Coeffs'].shape[0], max_records, 1)
+    out = {'coeffs': res['Coeffs'][rows], 'chi_sq': res['chi_sq'][rows],
+           'alpha_curvature': np.array([res['reg_params'][t]['curvature'] for t in rows], dtype=np.float64)}
+    if res.get('ranks') is not None:
+        out['ranks'] = np.asarray(res['ranks'])[rows]
+    if res.get('Covariance') is not None:
+        out['covariance_sample'] = res['Covariance'][rows[_sample_index(len(rows), cov_records, 2)]]
+    return out
+
+
+def density_sample(ctx, dout, Q, nrows, max_rows, max_points):
+    """Densities of the last evaluation call, read back from its device buffer `dout` (row-major, Q points per timestep):
+    a seeded sample of max_rows of its first nrows rows (the timesteps that call wrote) x max_points grid points."""
+    from volumetricinterp_amd import _lib
+    assert 0 < nrows and nrows * Q <= dout.size
+    rows = _sample_index(nrows, max_rows, 3)
+    pts = _sample_index(Q, max_points, 4)
+    row = np.empty(Q, dtype=np.float64)
+    out = np.empty((len(rows), len(pts)))
+    for i, r in enumerate(rows):
+        _lib.check(_lib.lib.vi_d2h(ctx.handle, row.ctypes.data_as(C.c_void_p), dout.offset_ptr(int(r) * Q), Q * 8), 'vi_d2h')
+        out[i] = row[pts]
+    return out
+
+
+def write_outputs(dirname, arrays):
+    """arrays as dirname/<name>.npy in float64 (the precision of the path), every value finite: a NaN or infinity the path
+    returned - the coefficients, alpha and chi^2 of a record without a root, the density of a grid point outside the hull -
+    is written as 0, and dirname/<name>_finite.npy (float32, same shape, always written) holds 1 where the value was finite
+    and 0 where it was not.  At most DUMP_LIMIT_BYTES in all."""
+    out = {}
+    for k, v in arrays.items():
+        v = np.asarray(v, dtype=np.float64)
+        fin = np.isfinite(v)
+        out[k] = np.ascontiguousarray(np.where(fin, v, 0.))
+        out[k + '_finite'] = np.ascontiguousarray(fin, dtype=np.float32)
+    arrays = out
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError('--dump-outputs: %d bytes, more than the %d allowed' % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + '.npy'), a)
+    sys.stderr.write('bench.py: %d arrays, %.1f MB, written to %s\n' % (len(arrays), total / 1e6, dirname))
 
 
 # ---- CPU baseline (rank 0, N = 1 only) -------------------------------------------------------------------------
@@ -230,10 +304,10 @@ def run(args):
     world = int(os.environ.get('WORLD_SIZE', '1'))
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
     os.environ.setdefault('VINTERP_DEVICE', str(local_rank))
-    # CPU baseline first (rank 0, N = 1 only): its worker processes are started before this process has loaded the
+    # CPU baseline first (--full, rank 0, N = 1 only): its worker processes are started before this process has loaded the
     # HIP runtime, and nothing runs on the GPU while the host cores are being timed
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline(args.grid, 'points/s') if args.workload == 'c1' else cpu_baseline(args.c3_grid, 'timesteps/s')
         except Exception as e:                       # a timed-out or dead worker: say so in the line, do not hang or die
@@ -278,12 +352,12 @@ def run(args):
     A = At.download().T
     if args.workload == 'c3':
         out = run_c3(args, ctx, comm, model, h, At, A, R, hull_eq, hull_tol, rank, world)
-        if rank == 0 and world == 1:
+        if args.full and rank == 0 and world == 1:
             out['cpu_baseline'] = cpu
             if not args.no_secondary:
                 # secondary objects (not part of `value`): the single-record latency path of configs[1] and the evaluation
                 # kernels on their own, measured after the timed region of workload c3
-                c1 = run_c1(args, ctx, comm, model, h, At, A, R, hull_eq, hull_tol, rank, world, steps=16, warmup=1)
+                c1 = run_c1(args, ctx, comm, model, h, At, A, R, hull_eq, hull_tol, rank, world, steps=16, warmup=1, full=True)
                 out['single_record'] = {
                     'workload': c1['config']['workload'], 'points_per_sec': c1['value'], 'ms_per_step': c1['ms_per_step'],
                     'steps': c1['steps'], 'step_ms': c1['step_ms'], 'guard_verdicts': c1['guard_verdicts'],
@@ -296,20 +370,22 @@ def run(args):
             real_stdout.write(json.dumps(out) + '\n')
             real_stdout.flush()
         return finish(comm, world)
-    out = run_c1(args, ctx, comm, model, h, At, A, R, hull_eq, hull_tol, rank, world, steps=args.steps, warmup=args.warmup)
+    out = run_c1(args, ctx, comm, model, h, At, A, R, hull_eq, hull_tol, rank, world, steps=args.steps, warmup=args.warmup,
+                 full=args.full, dump=args.dump_outputs)
     if rank == 0:
-        if world == 1:
+        if args.full and world == 1:
             out['cpu_baseline'] = cpu
         real_stdout.write(json.dumps(out) + '\n')
         real_stdout.flush()
     return finish(comm, world)
 
 
-def run_c1(args, ctx, comm, model, h, At, A, R, hull_eq, hull_tol, rank, world, steps, warmup):
+def run_c1(args, ctx, comm, model, h, At, A, R, hull_eq, hull_tol, rank, world, steps, warmup, full=True, dump=None):
     """BASELINE configs[1], the single-record latency path: a step = fit ONE record (26 x 100, N = 144, curvature, chi^2
     search, covariance) + evaluate it on a 128^3 grid with the hull mask; step t fits record t mod 16 of sixteen distinct
     resident records.  Returns the line of `--workload c1` (rank 0; None elsewhere); workload c3 at N = 1 embeds parts of it
-    as secondary objects."""
+    as secondary objects.  full: also the figures that take runs of their own (evaluation kernel alone, many timesteps,
+    batched records); dump: directory for the outputs of the last timed step."""
     from volumetricinterp_amd import _lib, synth
     from volumetricinterp_amd.fitengine import FitEngine
     N, P = model.nbasis, A.shape[0]
@@ -402,6 +478,11 @@ def run_c1(args, ctx, comm, model, h, At, A, R, hull_eq, hull_tol, rank, world, 
     elapsed = comm.max_over_ranks(time.perf_counter() - t0)
     st = ctx.solve_timing(0)
     solves_per_step = sum(e_.stats['solves'] for e_ in engs) / max(1, steps + warmup)
+    if dump and rank == 0 and steps > 0:
+        # the last timed step: its record's fit and its densities on the grid (dout is not written again before this)
+        outs = fit_outputs(res)
+        outs['density_sample'] = density_sample(ctx, dout, Q, T, max_rows=1, max_points=1 << 21)
+        write_outputs(dump, outs)
 
     def kernel_ms(fn, reps=5):
         best = float('inf')
@@ -416,7 +497,7 @@ def run_c1(args, ctx, comm, model, h, At, A, R, hull_eq, hull_tol, rank, world, 
 
     # ---- the evaluation kernel on its own (not part of `value`): with and without the hull pass ---------------------
     ev_kernel_hull = ev_kernel_nohull = ev_call_nohull = float('nan')
-    if rank == 0:
+    if full and rank == 0:
         ev_kernel_hull = kernel_ms(lambda: eval_grid(dC, T, dout, hull=True))
         ev_kernel_nohull = kernel_ms(lambda: eval_grid(dC, T, dout, hull=False))
         best = float('inf')
@@ -428,7 +509,7 @@ def run_c1(args, ctx, comm, model, h, At, A, R, hull_eq, hull_tol, rank, world, 
 
     # ---- secondary figure (not part of `value`): many timesteps on the same grid (SURVEY 8d row E2, configs[3]) ----
     many = None
-    if rank == 0 and not args.no_eval_many:
+    if full and rank == 0 and not args.no_eval_many:
         Tm = 64
         dCm = ctx.to_device(np.random.default_rng(3).standard_normal((Tm, N)))
         dom = ctx.empty((Tm, Q))
@@ -471,7 +552,7 @@ def run_c1(args, ctx, comm, model, h, At, A, R, hull_eq, hull_tol, rank, world, 
     # ---- secondary figure (not part of `value`): BASELINE configs[2] - 1000 records of one geometry fitted as one
     #      batch (the single-record step above keeps one CU of 256 busy).  One warm-up pass, one timed pass.
     batched = None
-    if rank == 0 and not args.no_batched and args.batched_records > 0:
+    if full and rank == 0 and not args.no_batched and args.batched_records > 0:
         Tb = args.batched_records
         vb, eb = synth.synth_records(A, Tb, seed0=5000)
         engb = FitEngine(ctx, At, P, N, {'curvature': R}, ['curvature'])
@@ -574,20 +655,21 @@ def run_c1(args, ctx, comm, model, h, At, A, R, hull_eq, hull_tol, rank, world, 
                 'fp64': {'achieved_tflops': flops_per_launch / (avg_ms * 1e-3) / 1e12, 'peak_tflops': FP64_PEAK_TF,
                          'frac': flops_per_launch / (avg_ms * 1e-3) / 1e12 / FP64_PEAK_TF,
                          'flops_model': '10 N^3 per solve (SURVEY 8d F2)'}}
-        # ---- second object: the fused evaluation kernel (0.5 % of the step, the headline kernel of the evaluate half)
-        out['roofline_eval'] = {
-            'kernel': 'k_eval_sph_fast<6,4,1> (+ k_hull_mask_mx)', 'bound': 'fp64 VALU (AI ~94 flop/B >> 9.8)',
-            'kernel_ms_hull_on': ev_kernel_hull, 'kernel_ms_hull_off': ev_kernel_nohull, 'call_ms_hull_off': ev_call_nohull,
-            'call_ms_hull_on': ev,
-            'hbm': {'achieved': EVAL_BYTES_PER_POINT * Q * T / (ev_kernel_nohull * 1e-3) / 1e9, 'peak': HBM_PEAK_GBS,
-                    'unit': 'GB/s', 'frac': EVAL_BYTES_PER_POINT * Q * T / (ev_kernel_nohull * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                    'traffic': traffic_eval},
-            'valu': {'achieved': EVAL_FLOPS_PER_POINT * Q * T / (ev_kernel_nohull * 1e-3) / 1e12, 'peak': FP64_PEAK_TF,
-                     'unit': 'TFLOP/s', 'frac': EVAL_FLOPS_PER_POINT * Q * T / (ev_kernel_nohull * 1e-3) / 1e12 / FP64_PEAK_TF,
-                     'flops_model': '~3.0 kflop/point at the default order (SURVEY 8d E1)'},
-            'points_per_sec_hull_on': Q * T / (ev * 1e-3), 'points_per_sec_hull_off': Q * T / (ev_kernel_nohull * 1e-3),
-            'hull_note': 'hull on: the whole vi_eval_f64 call (matrix-core mask pass k_hull_mask_mx + evaluation kernel, HIP events around '
-                         'the call); hull off: the evaluation kernel alone'}
+        # ---- second object (--full): the fused evaluation kernel (0.5 % of the step, the headline kernel of the evaluate half)
+        if full:
+            out['roofline_eval'] = {
+                'kernel': 'k_eval_sph_fast<6,4,1> (+ k_hull_mask_mx)', 'bound': 'fp64 VALU (AI ~94 flop/B >> 9.8)',
+                'kernel_ms_hull_on': ev_kernel_hull, 'kernel_ms_hull_off': ev_kernel_nohull, 'call_ms_hull_off': ev_call_nohull,
+                'call_ms_hull_on': ev,
+                'hbm': {'achieved': EVAL_BYTES_PER_POINT * Q * T / (ev_kernel_nohull * 1e-3) / 1e9, 'peak': HBM_PEAK_GBS,
+                        'unit': 'GB/s', 'frac': EVAL_BYTES_PER_POINT * Q * T / (ev_kernel_nohull * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                        'traffic': traffic_eval},
+                'valu': {'achieved': EVAL_FLOPS_PER_POINT * Q * T / (ev_kernel_nohull * 1e-3) / 1e12, 'peak': FP64_PEAK_TF,
+                         'unit': 'TFLOP/s', 'frac': EVAL_FLOPS_PER_POINT * Q * T / (ev_kernel_nohull * 1e-3) / 1e12 / FP64_PEAK_TF,
+                         'flops_model': '~3.0 kflop/point at the default order (SURVEY 8d E1)'},
+                'points_per_sec_hull_on': Q * T / (ev * 1e-3), 'points_per_sec_hull_off': Q * T / (ev_kernel_nohull * 1e-3),
+                'hull_note': 'hull on: the whole vi_eval_f64 call (matrix-core mask pass k_hull_mask_mx + evaluation kernel, HIP events around '
+                             'the call); hull off: the evaluation kernel alone'}
         if many is not None:
             out['eval_many_timesteps'] = many
         if batched is not None:
@@ -679,6 +761,7 @@ def run_c3(args, ctx, comm, model, h, At, A, R, hull_eq, hull_tol, rank, world):
             eval_ms.append(ems)
             basis_ms.append(bms)
             step_s_list.append(t2 - t0)
+        return res
 
     for _ in range(args.warmup):
         step()
@@ -686,8 +769,9 @@ def run_c3(args, ctx, comm, model, h, At, A, R, hull_eq, hull_tol, rank, world):
     ctx.sync()
     comm.barrier()
     t0 = time.perf_counter()
+    res = None
     for _ in range(args.steps):
-        step(record=True)
+        res = step(record=True)
     ctx.sync()
     comm.barrier()
     wall = comm.max_over_ranks(time.perf_counter() - t0)
@@ -699,6 +783,13 @@ def run_c3(args, ctx, comm, model, h, At, A, R, hull_eq, hull_tol, rank, world):
     fits = [float(np.frombuffer(b_, dtype=np.float64)[0])
             for b_ in comm.allgather_bytes(np.array([float(np.mean(fit_s)) if fit_s else 0.]).tobytes())]
     step_s = wall / args.steps            # barrier to barrier, max over ranks: nothing scaled
+    if args.dump_outputs and rank == 0 and res is not None:
+        # the last timed step: the fit of the shard (in res_bufs) and the densities of its last evaluation call (dout holds
+        # them in its first rows, the timesteps from the last multiple of TILE on)
+        outs = fit_outputs(res)
+        outs['density_sample'] = density_sample(ctx, dout, Q, share - (share - 1) // TILE * TILE, max_rows=16,
+                                                max_points=1 << 17)
+        write_outputs(args.dump_outputs, outs)
     # free what the secondary legs of an N = 1 run do not need (the basis matrix of the grid alone is 19 GB)
     for b_ in dq + [dhull, dC, dout] + ([dY] if dY is not None else []):
         b_.free()

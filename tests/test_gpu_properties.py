@@ -42,14 +42,14 @@ def test_eval_128cubed_linearity_and_tiles():
     assert rel(sixteen[0], out[5]) <= 1e-13 and rel(sixteen[15], out[20]) <= 1e-13
 
 
-def test_fast_and_generic_eval_kernels_agree_at_128cubed():
+def test_fast_and_generic_eval_kernels_agree_at_128cubed(tmp_path):
     code = ("import sys, numpy as np\nsys.path.insert(0, %r); sys.path.insert(0, %r)\n"
             "from test_gpu_properties import _eval\n"
             "C = np.random.default_rng(1).standard_normal((2, 144))\n"
             "np.save(sys.argv[1], _eval(C))\n") % (REPO, os.path.join(REPO, 'tests'))
     outs = []
     for mode in ('fast', 'generic'):
-        fn = '/tmp/vi_prop_%s.npy' % mode
+        fn = str(tmp_path / ('vi_prop_%s.npy' % mode))
         env = dict(os.environ, VINTERP_EVAL=mode)
         r = subprocess.run([sys.executable, '-c', code, fn], env=env, capture_output=True, text=True)
         assert r.returncode == 0, r.stderr

@@ -1,16 +1,28 @@
 """world_size = 2 rehearsal of the multi-GPU plumbing on CPU (gloo): broadcast of shared parameters,
 contiguous sharding of records, gather of per-rank rows - the only communication the path has."""
 import os
+import shutil
 import socket
 import subprocess
 import sys
+import tempfile
 import textwrap
 
 import numpy as np
+import pytest
 
 from volumetricinterp_amd.parallel import shard_bounds
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture
+def rdv_dir():
+    """A private directory with a short path for the rendezvous sockets: a Unix-domain socket path holds at most 107
+    bytes, and pytest's tmp_path under a long TMPDIR can exceed that."""
+    d = tempfile.mkdtemp(prefix='vi-rdv-', dir='/tmp' if os.path.isdir('/tmp') else None)
+    yield d
+    shutil.rmtree(d, ignore_errors=True)
 
 
 def test_shard_bounds_partition():
@@ -48,11 +60,8 @@ WORKER = textwrap.dedent('''
 ''')
 
 
-import pytest
-
-
 @pytest.mark.parametrize('backend,world', [('gloo', 2), ('socket', 2), ('socket', 3)])
-def test_multi_rank_equals_single_process(tmp_path, backend, world):
+def test_multi_rank_equals_single_process(tmp_path, rdv_dir, backend, world):
     script = tmp_path / 'worker.py'
     script.write_text(WORKER % REPO)
     with socket.socket() as s:
@@ -62,7 +71,7 @@ def test_multi_rank_equals_single_process(tmp_path, backend, world):
     procs = []
     for r in range(world):
         env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK=str(r), MASTER_ADDR='127.0.0.1',
-                   MASTER_PORT=str(port), TEST_BACKEND=backend, VINTERP_RDV_PATH=str(tmp_path / 'rdv.sock'))
+                   MASTER_PORT=str(port), TEST_BACKEND=backend, VINTERP_RDV_PATH=os.path.join(rdv_dir, 'rdv.sock'))
         procs.append(subprocess.Popen([sys.executable, str(script), out], env=env, stdout=subprocess.PIPE,
                                       stderr=subprocess.STDOUT))
     for p in procs:
@@ -136,7 +145,7 @@ CALC_WORKER = textwrap.dedent('''
 
 
 @pytest.mark.parametrize('world', [2, 3, 8])
-def test_sharded_calc_coeffs_equals_single_process(tmp_path, world):
+def test_sharded_calc_coeffs_equals_single_process(tmp_path, rdv_dir, world):
     """Interpolate.calc_coeffs(comm=...) - the record loop sharded over ranks (8 ranks > 7 records: one rank has an
     empty block) - gives exactly the single-process arrays."""
     script = tmp_path / 'worker.py'
@@ -147,7 +156,7 @@ def test_sharded_calc_coeffs_equals_single_process(tmp_path, world):
         procs = []
         for r in range(w):
             env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(w), LOCAL_RANK=str(r), MASTER_ADDR='127.0.0.1',
-                       MASTER_PORT='0', VINTERP_RDV_PATH=str(tmp_path / ('rdv%d.sock' % w)))
+                       MASTER_PORT='0', VINTERP_RDV_PATH=os.path.join(rdv_dir, 'rdv%d.sock' % w))
             procs.append(subprocess.Popen([sys.executable, str(script), out], env=env, stdout=subprocess.PIPE,
                                           stderr=subprocess.STDOUT))
         for p in procs:
