@@ -1,16 +1,29 @@
 #!/usr/bin/env python3
-"""Exact-arithmetic answers for the truncated solve at the default order (build container only; needs mpmath).
+"""Exact-arithmetic answers for the truncated solve (build container only; needs mpmath).
 
 The reference solves X c = y by scipy.linalg.lstsq (LAPACK gelsd, rcond = eps): mathematically the minimum-norm
 solution with the singular values below eps * sigma_max dropped.  LAPACK evaluates that definition with absolute errors of
 eps * sigma_max on every singular value, i.e. 10-100 % on the ones near the cut, and its answer moves by O(1) under one
 ulp on alpha; this script evaluates the SAME definition in 50-digit arithmetic (mpmath symmetric eigen-decomposition of
-the float64 matrix X), which gives the well-defined answer both LAPACK and the GPU solver approximate.  Systems: the
-reference's own X = A^T W A + alpha R and y of fixture fit_default_c2 (26 x 100, N = 144), at the reference's alpha of
-each record and 0.2 decades below.  Output tests/golden/exact_default_c2.npz (data only)."""
+the float64 matrix X), which gives the well-defined answer both LAPACK and the GPU solver approximate.
+
+Without arguments - systems: the reference's own X = A^T W A + alpha R and y of fixture fit_default_c2 (26 x 100,
+N = 144), at the reference's alpha of each record and 0.2 decades below.  Output tests/golden/exact_default_c2.npz.
+
+With --maxk / --maxl / --out - graded systems at an order past the QR pre-conditioner (N > 144), built from this
+package's own CPU code: the oracle basis on synth.beams(*synth.GEOM_C2), records 0 .. --records - 1 of
+synth.synth_records, the curvature matrix of the host builder (regmat.eval_omega) and, per record, alpha at the two
+integer decades around chi^2 = nu (nu = number of points) of a float64 CPU scan.  X is symmetrised in float64 before the
+exact evaluation and stored as its upper triangle (X_triu, row-major np.triu_indices order).  The fixtures of
+tests/test_gpu_solver_geometry.py:
+    python tools/gen_exact.py --maxk 5 --maxl 6 --out tests/golden/exact_n180.npz
+    python tools/gen_exact.py --maxk 4 --maxl 7 --out tests/golden/exact_n196.npz
+The systems are evaluated in parallel processes (--jobs, at most 16; ~5-10 min each at N = 180-196).  Data only."""
+import argparse
 import math
 import os
 import sys
+from multiprocessing import Pool
 
 import mpmath as mp
 import numpy as np
@@ -21,38 +34,123 @@ import oracle                                         # noqa: E402  (the CPU res
 
 mp.mp.dps = 50
 EPS = np.finfo(float).eps
-f = np.load(os.path.join(ROOT, 'tests', 'golden', 'fit_default_c2.npz'), allow_pickle=True)
-o = oracle.SphHarmLagOracle()
-A = o.basis(f['lat'], f['lon'], f['alt'])
-R = f['R']
-Xs, ys, Cs, chis, ranks, las, recs, cuts = [], [], [], [], [], [], [], []
-for t in range(f['value'].shape[0]):
-    if not np.isfinite(f['alpha'][t]) or f['alpha'][t] <= 0:
-        continue
-    b, W = f['value'][t], f['error'][t]**-2.
-    AWA = np.einsum('ji,j,jk->ik', A, W, A)
-    y = np.einsum('ji,j,j->i', A, W, b)
-    for dl in (0.0, -0.2):
-        la = math.log10(f['alpha'][t]) + dl
-        X = AWA + 10.**la * R
-        E, Q = mp.eigsy(mp.matrix(X.tolist()))
-        lam = np.array([float(x) for x in E])
-        thr = EPS * np.max(np.abs(lam))
-        ym = [mp.mpf(float(v)) for v in y]
-        C = [mp.mpf(0)] * len(y)
-        kept = 0
-        for i in range(len(lam)):
-            if abs(lam[i]) > thr:
-                kept += 1
-                g = sum(Q[r, i] * ym[r] for r in range(len(y))) / E[i]
-                for r in range(len(y)):
-                    C[r] += Q[r, i] * g
-        Cn = np.array([float(c) for c in C])
-        srt = np.sort(np.abs(lam))[::-1]
-        Xs.append(X); ys.append(y); Cs.append(Cn); ranks.append(kept); las.append(la); recs.append(t)
-        chis.append(float(sum((A @ Cn - b)**2 * W)))
-        cuts.append(srt[kept - 2:kept + 2] / srt[0])
-        print('record %d log10 alpha %.5f: rank %d chi2 %.6f  |lambda|/max around the cut %s' % (t, la, kept, chis[-1], cuts[-1]))
-np.savez_compressed(os.path.join(ROOT, 'tests', 'golden', 'exact_default_c2.npz'), X=np.array(Xs), y=np.array(ys),
-                    C=np.array(Cs), chi2=np.array(chis), rank=np.array(ranks), log10_alpha=np.array(las),
-                    record=np.array(recs), around_cut=np.array(cuts))
+
+
+def exact_solve(X, y):
+    """Minimum-norm solution of X c = y with the eigenvalues |lambda| <= eps max|lambda| dropped, in 50-digit arithmetic.
+    Returns C (float64), rank, |lambda| / max around the cut (two on each side)."""
+    mp.mp.dps = 50
+    E, Q = mp.eigsy(mp.matrix(X.tolist()))
+    lam = np.array([float(x) for x in E])
+    thr = EPS * np.max(np.abs(lam))
+    ym = [mp.mpf(float(v)) for v in y]
+    C = [mp.mpf(0)] * len(y)
+    kept = 0
+    for i in range(len(lam)):
+        if abs(lam[i]) > thr:
+            kept += 1
+            g = sum(Q[r, i] * ym[r] for r in range(len(y))) / E[i]
+            for r in range(len(y)):
+                C[r] += Q[r, i] * g
+    Cn = np.array([float(c) for c in C])
+    srt = np.sort(np.abs(lam))[::-1]
+    return Cn, kept, srt[max(kept - 2, 0):kept + 2] / srt[0]
+
+
+def _exact_task(args):
+    return exact_solve(*args)
+
+
+def default_c2():
+    f = np.load(os.path.join(ROOT, 'tests', 'golden', 'fit_default_c2.npz'), allow_pickle=True)
+    o = oracle.SphHarmLagOracle()
+    A = o.basis(f['lat'], f['lon'], f['alt'])
+    R = f['R']
+    Xs, ys, Cs, chis, ranks, las, recs, cuts = [], [], [], [], [], [], [], []
+    for t in range(f['value'].shape[0]):
+        if not np.isfinite(f['alpha'][t]) or f['alpha'][t] <= 0:
+            continue
+        b, W = f['value'][t], f['error'][t]**-2.
+        AWA = np.einsum('ji,j,jk->ik', A, W, A)
+        y = np.einsum('ji,j,j->i', A, W, b)
+        for dl in (0.0, -0.2):
+            la = math.log10(f['alpha'][t]) + dl
+            X = AWA + 10.**la * R
+            Cn, kept, cut = exact_solve(X, y)
+            Xs.append(X); ys.append(y); Cs.append(Cn); ranks.append(kept); las.append(la); recs.append(t)
+            chis.append(float(sum((A @ Cn - b)**2 * W)))
+            cuts.append(cut)
+            print('record %d log10 alpha %.5f: rank %d chi2 %.6f  |lambda|/max around the cut %s' % (t, la, kept, chis[-1], cuts[-1]))
+    np.savez_compressed(os.path.join(ROOT, 'tests', 'golden', 'exact_default_c2.npz'), X=np.array(Xs), y=np.array(ys),
+                        C=np.array(Cs), chi2=np.array(chis), rank=np.array(ranks), log10_alpha=np.array(las),
+                        record=np.array(recs), around_cut=np.array(cuts))
+
+
+def trunc_f64(X, y):
+    """The same definition in float64 (numpy eigh): only for the alpha scan."""
+    lam, V = np.linalg.eigh(X)
+    keep = np.abs(lam) > EPS * np.max(np.abs(lam))
+    return V[:, keep] @ ((V[:, keep].T @ y) / lam[keep])
+
+
+def graded(maxk, maxl, out, nrec, jobs, cap=10.0):
+    from volumetricinterp_amd import synth
+    from volumetricinterp_amd import regmat
+    o = oracle.SphHarmLagOracle(maxk=maxk, maxl=maxl, cap_lim_deg=cap)
+    N = o.nbasis
+    lat, lon, alt = synth.beams(*synth.GEOM_C2)
+    A = o.basis(lat, lon, alt)
+    assert np.all(np.isfinite(A)), 'basis not finite at MAXK %d x MAXL %d, CAP_LIM %g' % (maxk, maxl, cap)
+    # the host builder of models.sphharmlag.Model.eval_omega; it reads basis_numbers / nu / cap_lim / max_z_int, which the
+    # oracle defines as the Model does, so no GPU library is needed here
+    R = regmat.eval_omega(o)
+    assert np.all(np.isfinite(R))
+    value, error = synth.synth_records(A, nrec)
+    nu = float(A.shape[0])
+    tasks, meta = [], []
+    for t in range(nrec):
+        b, W = value[t], error[t]**-2.
+        AWA = np.einsum('ji,j,jk->ik', A, W, A)
+        y = np.einsum('ji,j,j->i', A, W, b)
+        chi = {}
+        for k in range(-40, 21):
+            X = AWA + 10.**k * R
+            X = 0.5 * (X + X.T)
+            chi[k] = float(np.sum((A @ trunc_f64(X, y) - b)**2 * W))
+        ks = [k for k in range(-40, 20) if chi[k] < nu <= chi[k + 1]]
+        assert ks, 'no chi^2 = nu crossing in 1e-40 .. 1e20 for record %d: %s' % (t, chi)
+        k0 = ks[0]
+        print('record %d: chi2(1e%d) = %.3f < nu = %g <= chi2(1e%d) = %.3f' % (t, k0, chi[k0], nu, k0 + 1, chi[k0 + 1]))
+        for la in (float(k0), float(k0 + 1)):
+            X = AWA + 10.**la * R
+            X = 0.5 * (X + X.T)
+            tasks.append((X, y))
+            meta.append((t, la, b, W))
+    with Pool(min(jobs, len(tasks), 16)) as p:
+        res = p.map(_exact_task, tasks, chunksize=1)
+    iu = np.triu_indices(N)
+    Xt, ys, Cs, chis, ranks, las, recs, cuts = [], [], [], [], [], [], [], []
+    for (X, y), (t, la, b, W), (Cn, kept, cut) in zip(tasks, meta, res):
+        Xt.append(X[iu]); ys.append(y); Cs.append(Cn); ranks.append(kept); las.append(la); recs.append(t); cuts.append(cut)
+        chis.append(float(np.sum((A @ Cn - b)**2 * W)))
+        print('record %d log10 alpha %.1f: rank %d chi2 %.6f  |lambda|/max around the cut %s' % (t, la, kept, chis[-1], cut))
+    np.savez_compressed(out, N=np.int32(N), maxk=np.int32(maxk), maxl=np.int32(maxl), cap_lim=np.float64(cap),
+                        lat=lat, lon=lon, alt=alt, value=value, W=error**-2., X_triu=np.array(Xt), y=np.array(ys),
+                        C=np.array(Cs), chi2=np.array(chis), rank=np.array(ranks, dtype=np.int32),
+                        log10_alpha=np.array(las), record=np.array(recs, dtype=np.int32), around_cut=np.array(cuts))
+    print('wrote', out, os.path.getsize(out), 'bytes')
+
+
+if __name__ == '__main__':
+    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('--maxk', type=int)
+    ap.add_argument('--maxl', type=int)
+    ap.add_argument('--out')
+    ap.add_argument('--records', type=int, default=2)
+    ap.add_argument('--jobs', type=int, default=8)
+    a = ap.parse_args()
+    if a.maxk is None:
+        default_c2()
+    else:
+        assert a.maxl is not None and a.out, '--maxk needs --maxl and --out'
+        graded(a.maxk, a.maxl, a.out, a.records, a.jobs)

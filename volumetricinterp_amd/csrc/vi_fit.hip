@@ -488,6 +488,17 @@ bool qr_enabled(int N)
 }
 inline size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
 
+// Sweep cap of the cold solves that start from X itself without K3p (N > 144, or VINTERP_QRPRE=0) in vi_solve_trunc_f64 and
+// vi_eigvals_f64, whose rotation logs live in those calls alone.  24 sweeps ended such solves before they converged: 25 on
+// graded X = A^T W A + alpha R at N = 180 and 196 (tests/golden/exact_n180.npz, exact_n196.npz) and on clusters of equal
+// eigenvalues at N = 155, which take 20-25 sweeps from N = 96 on and converge within 25 with a cap of 80
+// (tests/test_gpu_solver_geometry.py).  A solve that converges earlier is the same bit for bit; only the logs grow.
+int cold_max_sweeps(int N)
+{
+    const int v = JACOBI_MAX_SWEEPS;
+    return (qr_enabled(N) || v >= 40) ? v : 40;
+}
+
 }  // namespace
 
 namespace {
@@ -643,10 +654,11 @@ extern "C" int vi_solve_trunc_f64(vi_ctx* c, int64_t B, int32_t N, double* d_X, 
     VI_REQUIRE(B >= 0 && N > 0, "bad size");
     if (B == 0) return VI_OK;
     VI_HIP(hipSetDevice(c->device));
+    const int cap = cold_max_sweeps(N);
     if (!d_H && eig_method() == 2 && vi_jacobi_supported(N)) {
         // in-LDS Jacobi: chunk the batch so that the rotation logs stay within 4 GiB of workspace
         const bool qr = qr_enabled(N);
-        const size_t logb = vi_jacobi_log_bytes(N, JACOBI_MAX_SWEEPS);
+        const size_t logb = vi_jacobi_log_bytes(N, cap);
         const size_t hhb = qr ? up16(vi_qr_hh_bytes(N)) : 0;
         const size_t per = logb + sizeof(double) + (qr ? hhb + (size_t)(N * N + N) * sizeof(double) : 0);
         int64_t Bc = (int64_t)(((size_t)4 << 30) / per);
@@ -672,7 +684,7 @@ extern "C" int vi_solve_trunc_f64(vi_ctx* c, int64_t B, int32_t N, double* d_X, 
                 rcc = nullptr;
             }
             rc = vi_jacobi_solve(c, bc, N, Xc, scl, yc, rcc, rcond, d_C + i0 * N, d_rank ? d_rank + i0 : nullptr, ws,
-                                 JACOBI_MAX_SWEEPS, nullptr, nullptr, 0, nullptr, JACOBI_FLOOR_COLD);
+                                 cap, nullptr, nullptr, 0, nullptr, JACOBI_FLOOR_COLD);
             if (rc != VI_OK) return rc;
             if (qr && (rc = vi_qr_back_vec(c, bc, N, hh, d_C + i0 * N, (int64_t)(hhb / 8))) != VI_OK) return rc;
         }
@@ -682,7 +694,7 @@ extern "C" int vi_solve_trunc_f64(vi_ctx* c, int64_t B, int32_t N, double* d_X, 
         // final solves with H = pinv(X): in-LDS Jacobi (C, eigenvalues, rotation log) -> eigenvectors from the
         // log -> H = V diag(1/lam | kept) V^T
         const bool qr = qr_enabled(N);
-        const size_t logb = vi_jacobi_log_bytes(N, JACOBI_MAX_SWEEPS);
+        const size_t logb = vi_jacobi_log_bytes(N, cap);
         const size_t hhb = qr ? up16(vi_qr_hh_bytes(N)) : 0;
         int64_t Bc = (int64_t)(((size_t)4 << 30) / logb);
         if (Bc < 1) Bc = 1;
@@ -712,9 +724,9 @@ extern "C" int vi_solve_trunc_f64(vi_ctx* c, int64_t B, int32_t N, double* d_X, 
             // its eigenvectors are turned back, V = Q V1, and k_trunc_apply then sees X's own eigenpairs and y
             if (qr && (rc = vi_qr_precond(c, bc, N, Xc, yc, rc_, Xc, y1, hh, Vs, (int64_t)(hhb / 8))) != VI_OK) return rc;
             rc = vi_jacobi_solve(c, bc, N, Xc, scl, qr ? y1 : yc, qr ? nullptr : rc_, rcond, d_C + i0 * N,
-                                 d_rank ? d_rank + i0 : nullptr, ws, JACOBI_MAX_SWEEPS, nullptr, lam, 1, nrd, JACOBI_FLOOR_COLD);
+                                 d_rank ? d_rank + i0 : nullptr, ws, cap, nullptr, lam, 1, nrd, JACOBI_FLOOR_COLD);
             if (rc != VI_OK) return rc;
-            rc = vi_jacobi_vectors(c, bc, N, ws, JACOBI_MAX_SWEEPS, nrd, V);
+            rc = vi_jacobi_vectors(c, bc, N, ws, cap, nrd, V);
             if (rc != VI_OK) return rc;
             if (qr && (rc = vi_qr_back_mat(c, bc, N, hh, V, (int64_t)(hhb / 8))) != VI_OK) return rc;
             constexpr int BS = 256;
@@ -847,7 +859,8 @@ extern "C" int vi_eigvals_f64(vi_ctx* c, int64_t B, int32_t N, double* d_X, doub
     }
     VI_HIP(hipSetDevice(c->device));
     const bool qr = qr_enabled(N);
-    const size_t logb = vi_jacobi_log_bytes(N, JACOBI_MAX_SWEEPS);
+    const int cap = cold_max_sweeps(N);
+    const size_t logb = vi_jacobi_log_bytes(N, cap);
     const size_t hhb = qr ? up16(vi_qr_hh_bytes(N)) : 0;
     void* ws = nullptr;
     int rc = vi_ctx_workspace(c, (size_t)B * logb + (size_t)B * (N + 1) * sizeof(double) * 3 + 256 +
@@ -865,7 +878,7 @@ extern "C" int vi_eigvals_f64(vi_ctx* c, int64_t B, int32_t N, double* d_X, doub
     // the same pre-conditioning as vi_solve_trunc_f64 (X1 = Q^T X Q has X's eigenvalues)
     if (qr && (rc = vi_qr_precond(c, B, N, d_X, yz, nullptr, d_X, y1, hh, scr, (int64_t)(hhb / 8))) != VI_OK) return rc;
     return vi_jacobi_solve(c, B, N, d_X, scl, yz, nullptr, 2.220446049250313e-16, Cz, nullptr, ws,
-                           JACOBI_MAX_SWEEPS, d_sweeps, d_lam, 0, nullptr, JACOBI_FLOOR_COLD);
+                           cap, d_sweeps, d_lam, 0, nullptr, JACOBI_FLOOR_COLD);
 }
 
 // ---- warm-started search -------------------------------------------------------------------------------
@@ -997,6 +1010,8 @@ extern "C" int vi_warm_prepare_f64(vi_ctx* c, int64_t B, int32_t N, const double
 // and the three products - only the one the walk then points at.
 extern "C" size_t vi_rotation_log_bytes(int32_t N) { return log_record_bytes(N); }
 extern "C" int vi_max_sweeps(void) { return JACOBI_MAX_SWEEPS; }
+// the cap of vi_solve_trunc_f64 / vi_eigvals_f64 at order N (their sweep counts are cap + 1 when it ended the iteration)
+extern "C" int vi_cold_max_sweeps(int32_t N) { return cold_max_sweeps(N); }
 double vi_floor_warm() { return JACOBI_FLOOR_WARM; }
 
 // End of the Jacobi iteration in the solves of the bracket walk (vi_basis_solve_f64), whose chi^2 only decides signs - values
