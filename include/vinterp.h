@@ -158,14 +158,23 @@ int  vi_eval_f64(vi_model* model, int64_t Q, const double* d_lat, const double* 
 int  vi_eval_basis_f64(vi_model* model, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt,
                        const double* d_hull_eq, int32_t F, double hull_tol, double* d_Y);
 int  vi_eval_resident_f64(vi_model* model, int64_t Q, int64_t T, const double* d_Y, const double* d_C, double* d_out);
+/* Standard-error maps of many timesteps on the same resident grid (the `calcerr` output of estimate.py:139-145 for a batch of
+ * covariances, e.g. the /Coeffs/dC of a whole fit):
+ *   vi_eval_resident_err_f64  out[t*Q + q] = sqrt( sum_i sum_k d_Y[i*Q + q] * d_dC[t*N*N + i*N + k] * d_Y[k*Q + q] )
+ * with d_Y from vi_eval_basis_f64 and d_dC the T row-major N x N covariances as stored.  The full matrix is evaluated, never
+ * assumed symmetric.  NaN outside the hull through the NaN of d_Y, NaN for every point of a timestep whose covariance holds a
+ * NaN (a failed fit), NaN where the form is negative (as np.sqrt gives it, as vi_eval_err_f64 does).  The matrix-core kernel
+ * K2e takes N <= 144 with Q even and d_Y / d_out 16-byte aligned; other shapes, and VINTERP_EVAL_RESIDENT=blas, go through
+ * the library's product and a row dot, as vi_eval_err_f64 (tests/test_gpu_resident_error.py). */
+int  vi_eval_resident_err_f64(vi_model* model, int64_t Q, int64_t T, const double* d_Y, const double* d_dC, double* d_out);
 /* Arithmetic of the Legendre degree recurrences inside vi_eval_f64 for this model: 0 = fp64 (default; the reference
  * computes in float64 throughout, sphharmlag.py:118-145), 1 = fp32 chains with everything else in fp64 - the variant
  * BASELINE configs[4] sweeps against the 1e-6 tolerance.  Orders with an fp32 kernel: (MAXL, MAXK) = (6,4), (2,8), (12,8);
  * others return VI_ERR_UNSUPPORTED from vi_eval_f64 while the flag is set. */
 int  vi_model_set_eval_precision(vi_model* model, int32_t chain_f32);
-/* device time (ms) of the evaluation kernel launches of the last vi_eval_f64 / vi_eval_resident_f64 call on this context, from
- * HIP events recorded on the context's stream around them (the preparation kernels are excluded).  The events are recorded
- * only while vi_ctx_set_eval_timing(ctx, 1) is in force (default: off - the pair costs a 0.2 ms call about 7 us);
+/* device time (ms) of the evaluation kernel launches of the last vi_eval_f64 / vi_eval_resident_f64 / vi_eval_resident_err_f64
+ * call on this context, from HIP events recorded on the context's stream around them (the preparation kernels are excluded).
+ * The events are recorded only while vi_ctx_set_eval_timing(ctx, 1) is in force (default: off - the pair costs a 0.2 ms call about 7 us);
  * vi_eval_kernel_ms fails with VI_ERR_ARG while it is off or before a call has been timed. */
 int  vi_ctx_set_eval_timing(vi_ctx* ctx, int32_t on);
 int  vi_eval_kernel_ms(vi_ctx* ctx, double* ms);

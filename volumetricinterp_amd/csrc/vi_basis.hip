@@ -1088,6 +1088,8 @@ int vi_eval_sph_mfma(vi_model* m, int64_t Q, const double* lat, const double* lo
 int vi_eval_sph_split(vi_model* m, int64_t Q, const double* lat, const double* lon, const double* alt, int64_t T,
                       const double* Cp, const unsigned char* hull, int F, double* out, int* handled);
 int vi_eval_resident_mfma(vi_ctx* c, int N, int64_t Q, int64_t T, const double* d_Y, const double* d_C, double* d_out, int* handled);
+int vi_eval_resident_err_mfma(vi_ctx* c, int N, int64_t Q, int64_t T, const double* d_Y, const double* d_dC, double* d_out,
+                              int* handled);
 namespace {
 
 bool use_fast_eval()
@@ -1351,6 +1353,59 @@ extern "C" int vi_eval_resident_f64(vi_model* m, int64_t Q, int64_t T, const dou
             // column-major: out(qc x tc, ld Q) = Y(qc x N, ld Q) * C(N x tc, ld N)
             VI_ROCBLAS(rocblas_dgemm(c->blas, rocblas_operation_none, rocblas_operation_none, (rocblas_int)qc, (rocblas_int)tc, N,
                                      &one, d_Y + q0, (rocblas_int)Q, d_C + t0 * N, N, &zero, d_out + t0 * Q + q0, (rocblas_int)Q));
+        }
+    }
+    return VI_OK;
+}
+
+// Standard-error maps of many timesteps on the resident grid: out[t*Q + q] = sqrt(sum_ik Y[i][q] dC[t][i][k] Y[k][q]).  K2e
+// (vi_eval_resident.hip) for N <= 144; other shapes and orders, and VINTERP_EVAL_RESIDENT=blas: per chunk of points the basis
+// columns are turned point-major once into the context workspace, then per timestep the product and the row dot of
+// vi_eval_err_f64 (B = A dC_t by the library, then k_rowdot_sqrt).
+namespace {
+__global__ void k_points_major(int64_t P, int N, const double* __restrict__ Y, int64_t ldy, double* __restrict__ A)
+{
+    const int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;     // e = n * P + q: the reads along the basis rows
+    if (e >= P * N) return;
+    const int64_t n = e / P, q = e - n * P;
+    A[q * N + n] = Y[n * ldy + q];
+}
+}  // namespace
+
+extern "C" int vi_eval_resident_err_f64(vi_model* m, int64_t Q, int64_t T, const double* d_Y, const double* d_dC, double* d_out)
+{
+    VI_REQUIRE(m && d_Y && d_dC && d_out, "null argument");
+    VI_REQUIRE(Q >= 0 && T >= 0, "negative size");
+    if (Q == 0 || T == 0) return VI_OK;
+    vi_ctx* c = m->ctx;
+    VI_HIP(hipSetDevice(c->device));
+    const int N = m->N;
+    {
+        EvalTimer timer(c);
+        int handled = 0;
+        const int rc = vi_eval_resident_err_mfma(c, N, Q, T, d_Y, d_dC, d_out, &handled);      // K2e
+        if (rc != VI_OK || handled) return rc;
+    }
+    // points per chunk: a workspace of at most 512 MB (233 000 points at N = 144)
+    int64_t chunk = ((int64_t)1 << 25) / N;
+    if (chunk > Q) chunk = Q;
+    void* ws = nullptr;
+    int rc = vi_ctx_workspace(c, (size_t)2 * chunk * N * sizeof(double), &ws);
+    if (rc != VI_OK) return rc;
+    double* A = (double*)ws;
+    double* B = A + chunk * N;
+    const double one = 1.0, zero = 0.0;
+    EvalTimer timer(c);
+    for (int64_t q0 = 0; q0 < Q; q0 += chunk) {
+        const int64_t qc = (Q - q0) < chunk ? (Q - q0) : chunk;
+        hipLaunchKernelGGL(k_points_major, dim3(nblocks(qc * N, 256)), dim3(256), 0, c->stream, qc, N, d_Y + q0, Q, A);
+        VI_HIP(hipGetLastError());
+        for (int64_t t = 0; t < T; ++t) {
+            // row-major B (qc x N) = A (qc x N) dC_t^T, B[q][i] = sum_k dC_t[i][k] Y[k][q0 + q] (as in vi_eval_err_f64)
+            VI_ROCBLAS(rocblas_dgemm(c->blas, rocblas_operation_transpose, rocblas_operation_none, N, (rocblas_int)qc, N, &one,
+                                     d_dC + t * N * N, N, A, N, &zero, B, N));
+            hipLaunchKernelGGL(k_rowdot_sqrt, dim3(nblocks(qc, 4)), dim3(256), 0, c->stream, qc, N, A, B, d_out + t * Q + q0);
+            VI_HIP(hipGetLastError());
         }
     }
     return VI_OK;

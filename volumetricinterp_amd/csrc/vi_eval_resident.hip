@@ -156,3 +156,166 @@ int vi_eval_resident_mfma(vi_ctx* c, int N, int64_t Q, int64_t T, const double* 
     *handled = 1;
     return VI_OK;
 }
+
+// K2e: standard-error maps of many timesteps on the same resident grid (the `calcerr` output of estimate.py:139-145, for a
+// batch of covariances):
+//
+//   err[t][q] = sqrt( sum_i sum_k Y[i][q] * dC[t][i][k] * Y[k][q] )
+//
+// The covariances are NOT symmetric (the fit's dC differs from its transpose by up to 1e-5 of its largest entry at the default
+// order) and the form cancels by up to six decades, so the full matrix is what is evaluated.  In 16 x 16 blocks (NB = N / 16
+// rounded up): with S_II = dC_II and S_IJ = dC_IJ + dC_JI^T for I < J, err^2 = sum_{I <= J} y_I^T S_IJ y_J - the same sum up
+// to the rounding of one addition per entry, with NB (NB + 1) / 2 block products instead of NB^2 (45 of 81 at N = 144).
+//  * S of the workgroup's timestep sits in LDS in operand order ([block (I, J)][k-step][lane], 90 KB at N = 144), staged once
+//    per workgroup and reused for `groups` x 256 points; one workgroup of 8 waves per CU, two waves per SIMD.
+//  * A wave takes 32 points as two 16-point column tiles: lane (p = lane & 15, g = lane >> 4) reads the TWO consecutive points
+//    2p, 2p + 1 of basis row 16 J + 4 u + g (one 16-byte load; tile j holds the points 2p + j) - the B operand of k-step u of
+//    block column J.
+//  * Z_I = sum_{J >= I} S_IJ y_J accumulates with J descending, all NB accumulators live at the start (NB x 2 x 8 = 144
+//    registers at N = 144).  Z_I is complete right after block column J = I, whose B registers still hold rows 16 I + 4 u + g:
+//    exactly the rows (lane >> 4) + 4 v of Z_I's accumulator (f64 D layout: col = lane & 15, row = (lane >> 4) + 4 reg), so
+//    y_I^T Z_I is lane-local and every Y value is loaded once per (timestep, point tile).  Two cross-lane adds (lanes p,
+//    p + 16, p + 32, p + 48) and a sqrt finish the point.
+//  * Workgroups in the XCD-aware order of K2r, one timestep each: the timesteps of one group of points run on one XCD together
+//    and read its Y through the same L2.
+// Bound: the fp64 matrix peak, N_p (N_p + 16) flop issued per point-timestep (N_p = 16 NB; 23 040 at N = 144) against
+// 8 (N / T_concurrent + 1) bytes.
+namespace {
+
+typedef double v2f64 __attribute__((ext_vector_type(2)));
+
+constexpr int ERR_WAVES = 8;                              // waves per workgroup
+constexpr int ERR_PTS = ERR_WAVES * 32;                   // points per workgroup and group
+constexpr int ERR_NBMAX = 9;                              // N <= 144
+
+template <int NB>
+__global__ __launch_bounds__(ERR_WAVES * 64) void k_eval_resident_err(int N, int64_t Q, int64_t T, int groups, int64_t npg,
+                                                                      const double* __restrict__ Y, const double* __restrict__ dC,
+                                                                      double* __restrict__ out)
+{
+    constexpr int NBLK = NB * (NB + 1) / 2;
+    extern __shared__ __align__(16) double shS[];         // [block J (J + 1) / 2 + I][k-step u][lane]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int g = lane >> 4;
+    const int64_t bid = blockIdx.x;
+    const int xcd = (int)(bid & 7);
+    const int64_t r = bid >> 3;
+    const int64_t t = r % T;
+    const int64_t pg = (r / T) * 8 + xcd;
+    if (pg >= npg) return;
+    // ---- S of timestep t in operand order: shS[(blk * 4 + u) * 64 + (g * 16 + p)] = S_IJ[16 I + p][16 J + 4 u + g]
+    const double* D = dC + t * N * N;
+    for (int e = tid; e < NBLK * 256; e += ERR_WAVES * 64) {
+        const int l = e & 63, u = (e >> 6) & 3, blk = e >> 8;
+        int J = 0;
+        while ((J + 1) * (J + 2) / 2 <= blk) ++J;
+        const int I = blk - J * (J + 1) / 2;
+        const int i = 16 * I + (l & 15), k = 16 * J + 4 * u + (l >> 4);
+        double v = 0.0;
+        if (i < N && k < N) {
+            v = D[(int64_t)i * N + k];
+            if (I != J) v += D[(int64_t)k * N + i];
+        }
+        shS[e] = v;
+    }
+    __syncthreads();
+    for (int grp = 0; grp < groups; ++grp) {
+        const int64_t qa = (pg * groups + grp) * ERR_PTS + wave * 32 + 2 * (lane & 15);   // this lane's two points
+        const bool valid = qa < Q;                                                         // Q even: both or none
+        if (__ballot(valid) == 0) break;
+        const double* yp = Y + (valid ? qa : 0);
+        const double* yg = yp + (int64_t)g * Q;             // basis row g; row 16 J + 4 u + g is a uniform offset away
+        v4f64 Z[NB][2];
+#pragma unroll
+        for (int I = 0; I < NB; ++I) Z[I][0] = Z[I][1] = (v4f64){0.0, 0.0, 0.0, 0.0};
+        v2f64 y[2][4];                                     // B of block column J (y[J & 1]) and of the next one, in flight
+        auto load = [&](v2f64 (&b)[4], int J) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const double* src = yg + (int64_t)(16 * J + 4 * u) * Q;
+                if (J < NB - 1) {
+                    b[u] = *reinterpret_cast<const v2f64*>(src);
+                } else {                                    // the last block column: rows from N on are zero padding
+                    const bool in = 16 * J + 4 * u + g < N;
+                    const v2f64 v = *reinterpret_cast<const v2f64*>(in ? src : yp);
+                    b[u] = in ? v : (v2f64){0.0, 0.0};
+                }
+            }
+        };
+        double acc0 = 0.0, acc1 = 0.0;
+        load(y[(NB - 1) & 1], NB - 1);
+#pragma unroll
+        for (int J = NB - 1; J >= 0; --J) {
+            if (J > 0) load(y[(J - 1) & 1], J - 1);
+            // scheduling barriers: the next block column's loads and one k-step's LDS reads in flight, not all of them (254 VGPRs
+            // at NB = 9, no scratch)
+            __builtin_amdgcn_sched_barrier(0);
+            const v2f64(&b)[4] = y[J & 1];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+#pragma unroll
+                for (int I = 0; I <= J; ++I) {
+                    const double a = shS[((J * (J + 1) / 2 + I) * 4 + u) * 64 + lane];
+                    Z[I][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b[u].x, Z[I][0], 0, 0, 0);
+                    Z[I][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b[u].y, Z[I][1], 0, 0, 0);
+                }
+                __builtin_amdgcn_sched_barrier(0);        // the LDS reads of one k-step at a time (J + 1 register pairs)
+            }
+            // Z_J is complete; its row g + 4 v is basis row 16 J + 4 v + g, the one b[v] holds
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                acc0 = fma(Z[J][0][v], b[v].x, acc0);
+                acc1 = fma(Z[J][1][v], b[v].y, acc1);
+            }
+        }
+        acc0 += __shfl_xor(acc0, 16);
+        acc1 += __shfl_xor(acc1, 16);
+        acc0 += __shfl_xor(acc0, 32);
+        acc1 += __shfl_xor(acc1, 32);
+        if (valid && g == 0)                                // a negative form gives NaN, as np.sqrt does
+            *reinterpret_cast<v2f64*>(out + t * Q + qa) = (v2f64){sqrt(acc0), sqrt(acc1)};
+    }
+}
+
+template <int NB>
+int launch_eval_resident_err(vi_ctx* c, int N, int64_t Q, int64_t T, const double* d_Y, const double* d_dC, double* d_out,
+                             int* handled)
+{
+    const size_t shm = (size_t)(NB * (NB + 1) / 2) * 4 * 64 * sizeof(double);
+    // points per workgroup: 256 x groups - S (up to 166 KB of covariance through L2) is staged once per workgroup, against
+    // 22 us of matrix-core work per group of 256 points at N = 144
+    int groups = (int)((Q >> 16) < 1 ? 1 : ((Q >> 16) > 8 ? 8 : (Q >> 16)));
+    if (const char* e = getenv("VINTERP_K2E_GROUPS")) { const int gr = atoi(e); if (gr >= 1 && gr <= 256) groups = gr; }  // experiments
+    const int64_t npg = (Q + (int64_t)ERR_PTS * groups - 1) / ((int64_t)ERR_PTS * groups);
+    const int64_t nblk = ((npg + 7) / 8) * 8 * T;
+    if (nblk > 0x7fffffffLL) return VI_OK;
+    VI_HIP(hipFuncSetAttribute((const void*)k_eval_resident_err<NB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+    hipLaunchKernelGGL(k_eval_resident_err<NB>, dim3((unsigned)nblk), dim3(ERR_WAVES * 64), shm, c->stream, N, Q, T, groups, npg,
+                       d_Y, d_dC, d_out);
+    VI_HIP(hipGetLastError());
+    *handled = 1;
+    return VI_OK;
+}
+
+}  // namespace
+
+// out[t*Q + q] = sqrt(sum_ik Y[i*Q + q] dC[t*N*N + i*N + k] Y[k*Q + q]) by K2e; *handled = 0 when the shape is not the kernel's
+// (the caller then uses the library): N <= 144, Q even and Y / out 16-byte aligned (the 16-byte pieces of two points).
+int vi_eval_resident_err_mfma(vi_ctx* c, int N, int64_t Q, int64_t T, const double* d_Y, const double* d_dC, double* d_out,
+                              int* handled)
+{
+    *handled = 0;
+    if (!use_own_kernel()) return VI_OK;
+    if (N < 1 || N > 16 * ERR_NBMAX || (Q & 1) != 0 || (((uintptr_t)d_Y | (uintptr_t)d_out) & 15) != 0) return VI_OK;
+    switch ((N + 15) / 16) {
+    case 1: return launch_eval_resident_err<1>(c, N, Q, T, d_Y, d_dC, d_out, handled);
+    case 2: return launch_eval_resident_err<2>(c, N, Q, T, d_Y, d_dC, d_out, handled);
+    case 3: return launch_eval_resident_err<3>(c, N, Q, T, d_Y, d_dC, d_out, handled);
+    case 4: return launch_eval_resident_err<4>(c, N, Q, T, d_Y, d_dC, d_out, handled);
+    case 5: return launch_eval_resident_err<5>(c, N, Q, T, d_Y, d_dC, d_out, handled);
+    case 6: return launch_eval_resident_err<6>(c, N, Q, T, d_Y, d_dC, d_out, handled);
+    case 7: return launch_eval_resident_err<7>(c, N, Q, T, d_Y, d_dC, d_out, handled);
+    case 8: return launch_eval_resident_err<8>(c, N, Q, T, d_Y, d_dC, d_out, handled);
+    default: return launch_eval_resident_err<9>(c, N, Q, T, d_Y, d_dC, d_out, handled);
+    }
+}

@@ -325,6 +325,54 @@ class ResidentGrid(object):
         C = np.array([np.asarray(self.est.get_C(t)[0], dtype=np.float64) for t in times])
         return self.evaluate_coeffs(C).reshape((len(times),) + tuple(self.shape))
 
+    def evaluate_errors(self, dC, out=None):
+        """out[t] = standard error sqrt(a^T dC[t] a) of the fitted parameter on the grid for each covariance dC[t] (as stored
+        in /Coeffs/dC, not assumed symmetric); (T, Q) host array, NaN outside the hull, for a covariance holding a NaN and
+        where the form is negative.  `out` as in evaluate_coeffs."""
+        dC = np.ascontiguousarray(dC, dtype=np.float64)
+        N = self.est.model.nbasis
+        if dC.ndim != 3 or dC.shape[1:] != (N, N):
+            raise ValueError('covariances must have shape (T, %d, %d)' % (N, N))
+        T = dC.shape[0]
+        if out is None:
+            out = np.empty((T, self.Q), dtype=np.float64)
+        elif out.shape != (T, self.Q) or out.dtype != np.float64 or not out.flags.c_contiguous:
+            raise ValueError('out must be a C-contiguous float64 array of shape (%d, %d)' % (T, self.Q))
+        if T == 0 or self.Q == 0:
+            return out
+        ctx = self.est.model.ctx
+        # timesteps in slabs whose covariances and output fit a quarter of the free device memory
+        free, _ = ctx.mem_info()
+        slab = int(max(1, min(T, (free // 4) // max(1, (self.Q + N * N) * 8))))
+        if self.dY is None:
+            raise ValueError('this ResidentGrid has been closed')
+        dD = dO = None
+        try:
+            dD = ctx.empty((slab, N, N))
+            dO = ctx.empty((slab, self.Q))
+            for t0 in range(0, T, slab):
+                tc = min(slab, T - t0)
+                dD.upload(dC[t0:t0 + tc])
+                _lib.check(_lib.lib.vi_eval_resident_err_f64(self.est.model.handle(), self.Q, tc, self.dY.ptr, dD.ptr, dO.ptr),
+                           'vi_eval_resident_err_f64')
+                _lib.check(_lib.lib.vi_d2h(ctx.handle, out[t0:t0 + tc].ctypes.data_as(_lib.VOIDP), dO.ptr, tc * self.Q * 8), 'd2h')
+        finally:
+            for a in (dD, dO):
+                if a is not None:
+                    a.free()
+        return out
+
+    def error(self, times):
+        """Standard-error maps at the grid for a list of datetimes (the covariance of Estimate.get_C per time, as __call__
+        selects the coefficients): array (len(times),) + grid shape."""
+        if self.est.Covariance is None:
+            raise ValueError('this Estimate holds no covariance (Covariance is None): no standard error to evaluate')
+        N = self.est.model.nbasis
+        dC = np.empty((len(times), N, N))
+        for k, t in enumerate(times):
+            dC[k] = self.est.get_C(t)[1]
+        return self.evaluate_errors(dC).reshape((len(times),) + tuple(self.shape))
+
     def close(self):
         """Give the basis matrix back to the device (idempotent).  Also runs on `with est.resident_grid(...) as g:` exit
         and when the object is collected."""
