@@ -34,6 +34,8 @@ typedef double v4f64 __attribute__((ext_vector_type(4)));
 constexpr int RT = 4;        // row tiles (16 timesteps each) per wave
 constexpr int PF = 4;        // k-steps of B in flight
 
+// PAD: 4 KSp > N, the last k-steps hold rows past the basis
+template <bool PAD>
 __global__ __launch_bounds__(256, 2) void k_eval_resident(int N, int KSp, int64_t Q, int64_t T, int ntt, int groups, int64_t npg,
                                                           const double* __restrict__ Y, const double* __restrict__ C,
                                                           double* __restrict__ out)
@@ -76,7 +78,12 @@ __global__ __launch_bounds__(256, 2) void k_eval_resident(int N, int KSp, int64_
 #pragma unroll
             for (int u = 0; u < PF; ++u) {
                 const int n = 4 * (ks0 + u) + g;
-                y[u] = *reinterpret_cast<const v4f64*>(yp + (int64_t)((ks0 + u < KS && n < N) ? n : 0) * Q);
+                const bool in = ks0 + u < KS && n < N;
+                const v4f64 v = *reinterpret_cast<const v4f64*>(yp + (int64_t)(in ? n : 0) * Q);
+                // the rows from N on read row 0 and are set to zero: their zero coefficients times an infinite basis value
+                // would be NaN.  Without padding (N % 16 == 0, the default order) the kernel has no select at all: with one
+                // it measured 6 - 8 % slower at N = 144.
+                y[u] = (PAD && !in) ? (v4f64){0.0, 0.0, 0.0, 0.0} : v;
             }
         };
         auto mfma_stage = [&](const v4f64 (&y)[PF], int ks0) {
@@ -149,9 +156,15 @@ int vi_eval_resident_mfma(vi_ctx* c, int N, int64_t Q, int64_t T, const double* 
     const int64_t npg = (Q + (int64_t)256 * groups - 1) / ((int64_t)256 * groups);
     const int64_t nblk = ((npg + 7) / 8) * 8 * ntt;
     if (nblk > 0x7fffffffLL) return VI_OK;
-    VI_HIP(hipFuncSetAttribute((const void*)k_eval_resident, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    hipLaunchKernelGGL(k_eval_resident, dim3((unsigned)nblk), dim3(256), shm, c->stream, N, KSp, Q, T, ntt, groups, npg, d_Y, d_C,
-                       d_out);
+    const bool pad = 4 * KSp > N;                                       // N % 16 != 0: rows past the basis
+    VI_HIP(hipFuncSetAttribute(pad ? (const void*)k_eval_resident<true> : (const void*)k_eval_resident<false>,
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+    if (pad)
+        hipLaunchKernelGGL(k_eval_resident<true>, dim3((unsigned)nblk), dim3(256), shm, c->stream, N, KSp, Q, T, ntt, groups, npg,
+                           d_Y, d_C, d_out);
+    else
+        hipLaunchKernelGGL(k_eval_resident<false>, dim3((unsigned)nblk), dim3(256), shm, c->stream, N, KSp, Q, T, ntt, groups, npg,
+                           d_Y, d_C, d_out);
     VI_HIP(hipGetLastError());
     *handled = 1;
     return VI_OK;
