@@ -80,3 +80,35 @@ def test_product_never_imports_the_oracle():
             if f.endswith('.py'):
                 src = open(os.path.join(root, f)).read()
                 assert not re.search(r'^\s*(import|from)\s+oracle\b', src, flags=re.M), os.path.join(root, f)
+
+
+def toplevel_vi_functions(path):
+    """(declared, defined): names of the vi_ functions that a source file declares (prototype ending in ';') and defines (body
+    follows) at file scope - a text scan of the unindented lines, comments removed."""
+    txt = open(path).read()
+    txt = re.sub(r'/\*.*?\*/', '', txt, flags=re.S)
+    txt = re.sub(r'//[^\n]*', '', txt)
+    declared, defined = set(), set()
+    for m in re.finditer(r'^(?:extern "C" )?[A-Za-z_][\w:<>\*& ]*?\b(vi_[a-z0-9_]+)\s*\(', txt, flags=re.M):
+        depth, i = 1, m.end()
+        while depth:
+            depth += {'(': 1, ')': -1}.get(txt[i], 0)
+            i += 1
+        nxt = txt[i:].lstrip()[:1]
+        if nxt == ';':
+            declared.add(m.group(1))
+        elif nxt == '{':
+            defined.add(m.group(1))
+    return declared, defined
+
+
+def test_no_source_file_redeclares_another_files_function():
+    """A function that one vi_*.hip defines and another calls is declared in a header that both include (csrc/vi_solver.h,
+    csrc/vi_common.h, include/vinterp.h), where the compiler holds the definition against the declaration.  A prototype copied
+    into the calling .hip is seen by no definition: a changed parameter or default argument would go unnoticed."""
+    csrc = os.path.join(REPO, 'volumetricinterp_amd', 'csrc')
+    scans = {f: toplevel_vi_functions(os.path.join(csrc, f)) for f in sorted(os.listdir(csrc)) if f.endswith('.hip')}
+    assert len(scans) >= 10 and 'vi_jacobi_solve' in scans['vi_jacobi.hip'][1] and 'vi_solve_trunc_f64' in scans['vi_fit.hip'][1]
+    copied = [(f, n, g) for f, (declared, _) in scans.items() for g, (_, defined) in scans.items() if g != f
+              for n in sorted(declared & defined)]
+    assert not copied, copied

@@ -8,6 +8,7 @@
 // a wave share (recurrence coefficients, coefficient tiles) is addressed wave-uniformly so it is
 // served by the scalar data path / LDS broadcast and never costs per-lane HBM traffic.
 #include "vi_common.h"
+#include "vi_solver.h"
 #include "vi_sph_device.h"
 
 #include <cstdlib>
@@ -1083,23 +1084,12 @@ struct EvalTimer {
 };
 
 }  // namespace
-int vi_eval_sph_mfma(vi_model* m, int64_t Q, const double* lat, const double* lon, const double* alt, int64_t T,
-                     const double* Cp, const unsigned char* hull, int F, double* out, int64_t* done);
-int vi_eval_sph_split(vi_model* m, int64_t Q, const double* lat, const double* lon, const double* alt, int64_t T,
-                      const double* Cp, const unsigned char* hull, int F, double* out, int* handled);
-int vi_eval_resident_mfma(vi_ctx* c, int N, int64_t Q, int64_t T, const double* d_Y, const double* d_C, double* d_out, int* handled);
-int vi_eval_resident_err_mfma(vi_ctx* c, int N, int64_t Q, int64_t T, const double* d_Y, const double* d_dC, double* d_out,
-                              int* handled);
 namespace {
 
 bool use_fast_eval()
 {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("VINTERP_EVAL");
-        v = (e && !strcmp(e, "generic")) ? 0 : 1;
-    }
-    return v == 1;
+    static const bool generic = vi_env_is("VINTERP_EVAL", "generic");
+    return !generic;
 }
 
 }  // namespace
@@ -1280,10 +1270,7 @@ namespace {
 // the hull pass of a call: on the matrix cores (k_hull_mask_mx) unless VINTERP_HULL=fp32 asks for the packed-fp32 loop
 void launch_hull_mask(vi_model* m, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt, int F, double tol)
 {
-    static const bool fp32 = [] {
-        const char* e = getenv("VINTERP_HULL");
-        return e && strcmp(e, "fp32") == 0;
-    }();
+    static const bool fp32 = vi_env_is("VINTERP_HULL", "fp32");
     if (fp32)
         hipLaunchKernelGGL(k_hull_mask, dim3(nblocks(Q, BLOCK * HULL_PP)), dim3(BLOCK), 0, m->ctx->stream, Q, d_lat, d_lon, d_alt,
                            m->d_hull, F, tol, m->d_mask);

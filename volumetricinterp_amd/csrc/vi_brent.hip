@@ -20,6 +20,7 @@
 // path's re-basing next to the root needs eigenvectors and six matrix products per record).
 // A solve that the sweep cap ends before it converges makes the record leave with status 2: the host runs that record's
 // iteration itself (FitEngine: rotated-system solves that did not converge are solved again from X(alpha)).
+#include "vi_solver.h"
 #include "vi_jacobi_device.h"
 #include "vi_jacobi_v2_device.h"
 #include "vi_gemm_device.h"
@@ -28,12 +29,6 @@
 #include <cstdlib>
 #include <cstring>
 
-size_t vi_jacobi_lds_bytes(int N);
-size_t vi_jacobi_log_bytes(int N, int max_sweeps);
-bool vi_jacobi_supported(int N);
-bool vi_jacobi_use_v2(int N);           // vi_jacobi.hip: the role-separated K3 serves this order
-double vi_floor_warm();                  // vi_fit.hip: absolute rotation floor of the rotated-system solves
-extern "C" int vi_max_sweeps(void);
 
 #ifdef VI_STAMPS
 // diagnostic build only (-DVI_STAMPS): cycle sums of thread 0 of every workgroup per part of k_brent_warm; vi_debug_brent_stamps
@@ -478,15 +473,6 @@ extern "C" int vi_exp10_f64(const double* x, double* out, int64_t n)
 // interpreter between a value and the next request (~35 us of each ~135 us a dependent iterate spends outside its solve).
 // h_out: root, other end, iterations, function calls, status (0 converged, 2 a solve hit the sweep cap - the caller runs the
 // record's iteration itself -, 3 maxiter), re-basings.  d_scratch: N + 8 doubles.
-extern "C" int vi_warm_chi2_one_f64(vi_ctx* c, int32_t N, int64_t P, const double* d_D1, const double* d_D2, const double* d_yt,
-                                    const double* d_V, int32_t slot, double alpha, double rcond, const double* d_At, int32_t rec,
-                                    const double* d_W, const double* d_b, double* d_scratch, double* h_chi2);
-extern "C" int vi_warm_rebase_f64(vi_ctx* c, int64_t B, int64_t nplain, int32_t N, const double* d_AWA, const double* d_R,
-                                  const double* d_y, const int32_t* d_rec, const int32_t* d_slot, const double* d_alpha,
-                                  double rcond, double* d_V, double* d_D1, double* d_D2, double* d_yt, double* d_C,
-                                  int32_t* d_rank, int32_t* d_sweeps);
-extern "C" int vi_chi2_f64(vi_ctx* c, int64_t B, int64_t P, int32_t N, const double* d_At, const double* d_C,
-                           const int32_t* d_rec, const double* d_W, const double* d_b, double* d_chi2);
 namespace {
 __global__ void k_set_one_b(double* scratch, double alpha, int slot, int rec)
 {
@@ -605,17 +591,20 @@ extern "C" int vi_brent_warm_f64(vi_ctx* c, int64_t ntask, int32_t N, int64_t P,
     brent_geometry(N, threads, it);
     const int64_t nwg = ntask < c->n_cu ? ntask : c->n_cu;
     const size_t logb = vi_jacobi_log_bytes(N, max_sweeps);
-    void* ws = nullptr;
-    int rc = vi_ctx_workspace(c, (size_t)nwg * (logb + (size_t)(3 * N * N + N) * sizeof(double)) + 256, &ws);
+    double2* logw;
+    double *Xw, *VwW, *VnW, *cw;
+    int* queue;
+    int rc = ws_carve(c, [&](ws_carver& w) {
+        logw = w.take<double2>((size_t)nwg * (logb / sizeof(double2)));
+        Xw = w.take<double>((size_t)nwg * N * N);
+        VwW = w.take<double>((size_t)nwg * N * N);
+        VnW = w.take<double>((size_t)nwg * N * N);
+        cw = w.take<double>((size_t)nwg * N);
+        queue = w.take<int>(1);
+    });
     if (rc != VI_OK) return rc;
-    double2* logw = (double2*)ws;
-    double* Xw = (double*)((char*)ws + (size_t)nwg * logb);
-    double* VwW = Xw + (size_t)nwg * N * N;
-    double* VnW = VwW + (size_t)nwg * N * N;
-    double* cw = VnW + (size_t)nwg * N * N;
     RebaseRule rr;
     if (rule_from_host(h_rebase, rr)) { vi_set_error("vi_brent_warm_f64: at most four re-basing thresholds"); return VI_ERR_INVALID; }
-    int* queue = (int*)(cw + (size_t)nwg * N + 1);
     VI_HIP(hipMemsetAsync(queue, 0, sizeof(int), c->stream));
 #define VI_B(ITV)                                                                                                             \
     do {                                                                                                                      \

@@ -4,6 +4,7 @@
 #include <rocblas/rocblas.h>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -28,6 +29,15 @@ void vi_set_error(const char* fmt, ...);
             vi_set_error("%s:%d: %s -> rocblas status %d", __FILE__, __LINE__, #call, (int)s_); \
             return VI_ERR_ROCBLAS;                                                            \
         }                                                                                     \
+    } while (0)
+
+#define VI_ROCSOLVER(call)                                                                      \
+    do {                                                                                        \
+        rocblas_status s_ = (call);                                                             \
+        if (s_ != rocblas_status_success) {                                                     \
+            vi_set_error("%s:%d: %s -> rocsolver status %d", __FILE__, __LINE__, #call, (int)s_); \
+            return VI_ERR_ROCSOLVER;                                                            \
+        }                                                                                       \
     } while (0)
 
 #define VI_REQUIRE(cond, msg)                                  \
@@ -64,6 +74,71 @@ struct vi_ctx {
 };
 
 int vi_ctx_workspace(vi_ctx* ctx, size_t bytes, void** out);
+
+// Carves consecutive arrays out of one allocation.  On a null base it only counts: ws_carve below runs a layout on both.
+struct ws_carver {
+    char* base;
+    size_t off = 0;
+    template <class T>
+    T* take(size_t n, size_t align = 16)
+    {
+        off = (off + align - 1) / align * align;
+        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+        off += n * sizeof(T);
+        return p;
+    }
+};
+
+// The context workspace laid out by `layout(ws_carver&)`, which takes every array a call keeps there: run once on a null
+// base for the byte count to ask for, then on the workspace for the pointers - the count and the layout cannot disagree.
+template <class L>
+int ws_carve(vi_ctx* ctx, L&& layout)
+{
+    ws_carver count{nullptr};
+    layout(count);
+    void* ws = nullptr;
+    const int rc = vi_ctx_workspace(ctx, count.off, &ws);
+    if (rc != VI_OK) return rc;
+    ws_carver w{static_cast<char*>(ws)};
+    layout(w);
+    return VI_OK;
+}
+
+// A batch in chunks of a workspace budget: the chunk size, budget / per (beyond `whole`: a multiple of it) clamped to [1, B],
+// and f(i0, bc) for every chunk in order until one fails
+inline int64_t chunk_size(size_t budget, size_t per, int64_t B, int64_t whole = 1)
+{
+    int64_t Bc = (int64_t)(budget / per);
+    if (Bc > whole) Bc -= Bc % whole;
+    return Bc < 1 ? 1 : (Bc > B ? B : Bc);
+}
+template <class F>
+int for_chunks(int64_t B, int64_t Bc, F&& f)
+{
+    for (int64_t i0 = 0; i0 < B; i0 += Bc) {
+        const int rc = f(i0, (B - i0) < Bc ? (B - i0) : Bc);
+        if (rc != VI_OK) return rc;
+    }
+    return VI_OK;
+}
+
+// The VINTERP_* switches.  A switch is read once per process into a function-local `static const` where it is used: the
+// language initialises such a variable once and thread-safely, and FitEngine calls in from several host threads.
+inline int vi_env_int(const char* name, int dflt)
+{
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+inline double vi_env_double(const char* name, double dflt)
+{
+    const char* e = getenv(name);
+    return e ? atof(e) : dflt;
+}
+inline bool vi_env_is(const char* name, const char* value)
+{
+    const char* e = getenv(name);
+    return e && !strcmp(e, value);
+}
 
 // ---- device-side model tables ----------------------------------------------------------------
 struct SphGroupDev {

@@ -30,6 +30,7 @@
 // point-timestep.  Tiles of 64 timesteps were measured too: 128 accumulator registers leave one wave per SIMD and
 // the rate is the same, so the widest tile is 32.
 #include "vi_common.h"
+#include "vi_solver.h"
 #include "vi_sph_device.h"
 
 #include <cstdlib>
@@ -311,11 +312,7 @@ int launch_mfma(vi_model* m, int64_t Q, const double* lat, const double* lon, co
         return (size_t)(((nj * L + 1) & ~1) + NT * L * L * KQ * 64) * sizeof(double) + L * sizeof(int) + 16 <= 80 * 1024;
     };
     int64_t t = 0;
-    static int ntmax = -1;             // experiment switch: widest timestep tile (in units of 16)
-    if (ntmax < 0) {
-        const char* e = getenv("VINTERP_MFMA_NT");
-        ntmax = e ? atoi(e) : 2;
-    }
+    static const int ntmax = vi_env_int("VINTERP_MFMA_NT", 2);          // experiment switch: widest timestep tile (in units of 16)
     while (T - t >= 16) {
         int rc;
         if (T - t >= 32 && fits(2) && ntmax >= 2) {
@@ -342,12 +339,8 @@ int vi_eval_sph_mfma(vi_model* m, int64_t Q, const double* lat, const double* lo
                      const double* Cp, const unsigned char* hull, int F, double* out, int64_t* done)
 {
     *done = 0;
-    static int enabled = -1;
-    if (enabled < 0) {
-        const char* e = getenv("VINTERP_EVAL_MFMA");
-        enabled = (e && !strcmp(e, "0")) ? 0 : 1;
-    }
-    if (!enabled || m->sph.ngroups != 1 || T < 16) return VI_OK;
+    static const bool off = vi_env_is("VINTERP_EVAL_MFMA", "0");
+    if (off || m->sph.ngroups != 1 || T < 16) return VI_OK;
     const int L = m->sph.maxl, K = m->sph.maxk;
 #define VI_MFMA(LL, KK) \
     if (L == LL && K == KK) return launch_mfma<LL, (KK + 3) / 4>(m, Q, lat, lon, alt, T, Cp, hull, F, out, done)

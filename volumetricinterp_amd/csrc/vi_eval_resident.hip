@@ -23,6 +23,7 @@
 //    once per call, whatever the number of timesteps.
 // Bound: the fp64 matrix peak (78.6 TF): 2 N flop per point-timestep against 8 (N / T_call + 1) bytes.
 #include "vi_common.h"
+#include "vi_solver.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -128,12 +129,8 @@ __global__ __launch_bounds__(256, 2) void k_eval_resident(int N, int KSp, int64_
 
 bool use_own_kernel()
 {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("VINTERP_EVAL_RESIDENT");
-        v = (e && strcmp(e, "blas") == 0) ? 0 : 1;
-    }
-    return v != 0;
+    static const bool blas = vi_env_is("VINTERP_EVAL_RESIDENT", "blas");
+    return !blas;
 }
 
 }  // namespace

@@ -10,6 +10,7 @@
 // best at MAXK 8 x MAXL 12: 0.73 ms per 128^3 points against 1.93 ms (2.9e9 points/s, 34 % of the 8.6e9 VALU ceiling).
 // Same staging as the fast kernel: recurrence table and coefficient tile in LDS, wave-uniform reads.
 #include "vi_common.h"
+#include "vi_solver.h"
 #include "vi_sph_device.h"
 
 #include <cstdlib>
@@ -254,21 +255,13 @@ int vi_eval_sph_split(vi_model* m, int64_t Q, const double* lat, const double* l
                       const double* Cp, const unsigned char* hull, int F, double* out, int* handled)
 {
     *handled = 0;
-    static int enabled = -1;
-    if (enabled < 0) {
-        const char* e = getenv("VINTERP_EVAL_SPLIT");
-        enabled = (e && !strcmp(e, "0")) ? 0 : 1;
-    }
-    if (!enabled || m->sph.ngroups != 1) return VI_OK;
+    static const bool off = vi_env_is("VINTERP_EVAL_SPLIT", "0");
+    if (off || m->sph.ngroups != 1) return VI_OK;
     const int L = m->sph.maxl, K = m->sph.maxk;
     const int nj = m->nvmax0 + 1;
     if ((size_t)(((nj * L + 1) & ~1) + m->N) * sizeof(double) + 64 > 60 * 1024) return VI_OK;
     int rc = VI_OK;
-    static int nh = -1;
-    if (nh < 0) {
-        const char* e = getenv("VINTERP_SPLIT_NH");
-        nh = e ? atoi(e) : 3;
-    }
+    static const int nh = vi_env_int("VINTERP_SPLIT_NH", 3);
     // measured at MAXK 8 x MAXL 12, 128^3 points: 1.93 ms with all twelve chains at once (k_eval_sph_fast), 1.13 ms in two
     // groups of six (190 VGPRs, two waves per SIMD), 0.73 ms in three groups of four (115 VGPRs, four waves), 0.77 ms in
     // four groups of three

@@ -3,38 +3,12 @@
 // (interpolate.py:255-259).  The basis matrix is shared by all records (geometry is per file, not per
 // record), so T records become one strided-batched contraction instead of T x (#alpha) einsums.
 #include "vi_common.h"
+#include "vi_solver.h"
 #include "vi_gemm_device.h"
 
 #include <rocsolver/rocsolver.h>
 
 #include <cstdlib>
-
-#define VI_ROCSOLVER(call)                                                                      \
-    do {                                                                                        \
-        rocblas_status s_ = (call);                                                             \
-        if (s_ != rocblas_status_success) {                                                     \
-            vi_set_error("%s:%d: %s -> rocsolver status %d", __FILE__, __LINE__, #call, (int)s_); \
-            return VI_ERR_ROCSOLVER;                                                            \
-        }                                                                                       \
-    } while (0)
-
-size_t vi_jacobi_lds_bytes(int N);
-size_t vi_jacobi_log_bytes(int N, int max_sweeps);
-bool vi_jacobi_supported(int N);
-int vi_jacobi_solve(vi_ctx* c, int64_t B, int N, const double* d_X, const double* d_scl, const double* d_y,
-                    const int* d_rec, double rcond, double* d_C, int* d_rank, void* d_log, int max_sweeps,
-                    int* d_sweeps, double* d_lam, int lam_raw, int* d_nround, double abs_floor, int64_t log_stride = 0,
-                    double conv_tol = 0.0);
-bool vi_jacobi_vectors_supported(int N);
-int vi_jacobi_vectors(vi_ctx* c, int64_t B, int N, const void* d_log, int max_sweeps, const int* d_nround, double* d_V,
-                      int64_t log_stride = 0);
-// K3p (vi_qr.hip): X1 = Q^T X Q, y1 = Q^T y by one column-pivoted Householder QR step; back-transformations c <- Q c
-bool vi_qr_supported(int N);
-size_t vi_qr_hh_bytes(int N);
-int vi_qr_precond(vi_ctx* c, int64_t B, int N, const double* d_X, const double* d_y, const int* d_rec, double* d_X1,
-                  double* d_y1, double* d_hh, double* d_scr, int64_t hh_stride = 0);
-int vi_qr_back_vec(vi_ctx* c, int64_t B, int N, const double* d_hh, double* d_C, int64_t hh_stride = 0);
-int vi_qr_back_mat(vi_ctx* c, int64_t B, int N, const double* d_hh, double* d_V, int64_t hh_stride = 0);
 
 namespace {
 
@@ -432,27 +406,14 @@ __global__ __launch_bounds__(BS) void k_atwb(int64_t P, int N, int64_t T, const 
 // gate; both Jacobi variants give <= 1e-8.
 int eig_method()
 {
-    static int m = -1;
-    if (m < 0) {
-        const char* e = getenv("VINTERP_EIG");
-        m = 2;
-        if (e && !strcmp(e, "syevj")) m = 1;
-        if (e && !strcmp(e, "syevd")) m = 0;
-        if (e && !strcmp(e, "jacobi")) m = 2;
-    }
+    static const int m = vi_env_is("VINTERP_EIG", "syevj") ? 1 : vi_env_is("VINTERP_EIG", "syevd") ? 0 : 2;
     return m;
 }
 
 // sweep cap of the in-LDS Jacobi solver (the rotation-log workspace is sized by it); VINTERP_MAX_SWEEPS overrides it
 int jacobi_max_sweeps()
 {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("VINTERP_MAX_SWEEPS");
-        v = e ? atoi(e) : 24;
-        if (v < 4) v = 4;
-        if (v > 200) v = 200;
-    }
+    static const int v = [] { const int s = vi_env_int("VINTERP_MAX_SWEEPS", 24); return s < 4 ? 4 : (s > 200 ? 200 : s); }();
     return v;
 }
 #define JACOBI_MAX_SWEEPS jacobi_max_sweeps()
@@ -464,12 +425,7 @@ constexpr double JACOBI_FLOOR_COLD = 1e-22;
 // (measured, 1000 records 26 x 100: 464 searches redone with the floor at 1e-16, none at 1e-18, for 15 % more rounds)
 double jacobi_floor_warm()
 {
-    static double v = -1.0;
-    if (v < 0.0) {
-        const char* e = getenv("VINTERP_WARM_FLOOR");
-        v = e ? atof(e) : 1e-18;
-        if (!(v > 0.0)) v = 1e-18;
-    }
+    static const double v = [] { const double f = vi_env_double("VINTERP_WARM_FLOOR", 1e-18); return f > 0.0 ? f : 1e-18; }();
     return v;
 }
 #define JACOBI_FLOOR_WARM jacobi_floor_warm()
@@ -479,12 +435,8 @@ double jacobi_floor_warm()
 // VINTERP_QRPRE=0 switches it off.  The rotated systems of the warm / shared-basis solves are nearly diagonal already.
 bool qr_enabled(int N)
 {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("VINTERP_QRPRE");
-        v = (e && !strcmp(e, "0")) ? 0 : 1;
-    }
-    return v == 1 && vi_qr_supported(N);
+    static const bool off = vi_env_is("VINTERP_QRPRE", "0");
+    return !off && vi_qr_supported(N);
 }
 inline size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
 
@@ -600,21 +552,17 @@ extern "C" int vi_normal_eq_f64(vi_ctx* c, int64_t T, int64_t P, int32_t N, cons
     VI_HIP(hipSetDevice(c->device));
     const size_t per_t = (size_t)N * P * sizeof(double);
     const int NN = N * N;
-    int64_t Tc = (int64_t)((size_t)1 << 30) / (int64_t)per_t;      // <= 1 GiB of scaled copies at a time
-    if (Tc < 1) Tc = 1;
-    if (Tc > T) Tc = T;
-    const int64_t Tcp = group_pad(Tc);
-    void* ws = nullptr;
-    int rc = vi_ctx_workspace(c, (size_t)Tc * per_t + (size_t)GEMM_GROUP * NN * sizeof(double) + (size_t)3 * Tcp * sizeof(void*),
-                              &ws);
+    const int64_t Tc = chunk_size((size_t)1 << 30, per_t, T);      // <= 1 GiB of scaled copies at a time
+    double *Bs, *scratch;
+    const double **pA, **pB, **pC;
+    int rc = ws_carve(c, [&](ws_carver& w) {
+        Bs = w.take<double>((size_t)Tc * N * P);
+        scratch = w.take<double>((size_t)GEMM_GROUP * NN);
+        for (auto* pp : {&pA, &pB, &pC}) *pp = w.take<const double*>(group_pad(Tc));
+    });
     if (rc != VI_OK) return rc;
-    double* Bs = (double*)ws;
-    double* scratch = Bs + (size_t)Tc * N * P;
-    const double** pA = (const double**)(scratch + (size_t)GEMM_GROUP * NN);
-    const double** pB = pA + Tcp;
-    const double** pC = pB + Tcp;
-    for (int64_t t0 = 0; t0 < T; t0 += Tc) {
-        const int64_t tc = (T - t0) < Tc ? (T - t0) : Tc;
+    rc = for_chunks(T, Tc, [&](int64_t t0, int64_t tc) -> int {
+        int rc;
         hipLaunchKernelGGL(k_scale_rows, dim3(nblk(P, 256), N, (unsigned)tc), dim3(256), 0, c->stream, P, N, d_At,
                            d_W + t0 * P, Bs, (int)tc);
         VI_HIP(hipGetLastError());
@@ -622,10 +570,9 @@ extern "C" int vi_normal_eq_f64(vi_ctx* c, int64_t T, int64_t P, int32_t N, cons
         if ((rc = group_ptrs(c, tc, d_At, 0, nullptr, 0, pA)) != VI_OK) return rc;
         if ((rc = group_ptrs(c, tc, Bs, (int64_t)N * P, nullptr, 0, pB)) != VI_OK) return rc;
         if ((rc = group_ptrs(c, tc, d_AWA + t0 * NN, NN, scratch, NN, pC)) != VI_OK) return rc;
-        if ((rc = gemm_groups(c, rocblas_operation_transpose, rocblas_operation_none, N, N, (int)P, pA, (int)P, pB, (int)P,
-                              pC, N, tc)) != VI_OK)
-            return rc;
-    }
+        return gemm_groups(c, rocblas_operation_transpose, rocblas_operation_none, N, N, (int)P, pA, (int)P, pB, (int)P, pC, N, tc);
+    });
+    if (rc != VI_OK) return rc;
     hipLaunchKernelGGL(k_atwb<256>, dim3(N, nblk(T, 8)), dim3(256), 0, c->stream, P, N, T, d_At, d_W, d_b, d_y);
     VI_HIP(hipGetLastError());
     return VI_OK;
@@ -646,6 +593,63 @@ extern "C" int vi_form_system_f64(vi_ctx* c, int64_t B, int32_t N, const double*
     return VI_OK;
 }
 
+namespace {
+// Where a cold solve leaves its results, and the scratch it works in
+struct cold_dst {
+    double* C;                   // truncated minimum-norm solutions
+    int* rank;                   // their ranks (may be null)
+    bool C_back;                 // C is a result and is turned back, c <- Q c (false: the caller forms C from the eigenvectors)
+    void* log;                   // rotation logs ...
+    int64_t log_stride;          // ... and the distance between consecutive ones in bytes (0: back to back)
+    double* hh;                  // K3p: Householder reflectors ...
+    int64_t hh_stride;           // ... and the distance between consecutive sets in bytes
+    double *scl, *y1, *scr;      // scales; K3p: Q^T y and N x N doubles of scratch per system
+    double* lam;                 // eigenvalues (may be null), of the scaled system if lam_raw
+    int lam_raw;
+    int *nround, *sweeps;        // rounds the logs hold, sweeps taken (may be null)
+    int cap;                     // sweep cap, which also sizes the logs
+};
+
+// The cold solve - every solve that starts from X(alpha) itself: bc systems X (overwritten) are scaled, pre-conditioned where
+// K3p serves the order (X1 = Q^T X Q in place, y1 = Q^T y), solved by the in-LDS Jacobi kernel down to the cold rotation floor,
+// and the solutions turned back.  y, rec: the right-hand sides as vi_jacobi_solve takes them.
+int cold_solve(vi_ctx* c, int64_t bc, int N, double* X, const double* y, const int* rec, double rcond, const cold_dst& d)
+{
+    const bool qr = qr_enabled(N);
+    hipLaunchKernelGGL(k_scale_system<256>, dim3((unsigned)bc), dim3(256), 0, c->stream, N * N, X, d.scl);
+    VI_HIP(hipGetLastError());
+    int rc;
+    if (qr) {
+        if ((rc = vi_qr_precond(c, bc, N, X, y, rec, X, d.y1, d.hh, d.scr, d.hh_stride / 8)) != VI_OK) return rc;
+        y = d.y1;
+        rec = nullptr;
+    }
+    rc = vi_jacobi_solve(c, bc, N, X, d.scl, y, rec, rcond, d.C, d.rank, d.log, d.cap, d.sweeps, d.lam, d.lam_raw, d.nround,
+                         JACOBI_FLOOR_COLD, d.log_stride / 16);
+    if (rc != VI_OK) return rc;
+    if (qr && d.C_back) return vi_qr_back_vec(c, bc, N, d.hh, d.C, d.hh_stride / 8);
+    return VI_OK;
+}
+
+// From eigenpairs (V, lam of the scaled systems) to the truncated solutions C and, where H is wanted, H = pinv(X) =
+// Vs V^T with Vs = V diag(1/lam | kept) (column-major N x N; symmetric)
+int trunc_from_eigenpairs(vi_ctx* c, int64_t bc, int N, const double* V, const double* lam, const double* scl, const double* y,
+                          const int* rec, double rcond, double* C, int* rank, double pinv_rcond, double* Vs, double* H)
+{
+    constexpr int BS = 256;
+    hipLaunchKernelGGL(k_trunc_apply<BS>, dim3((unsigned)bc), dim3(BS), (size_t)(N + BS) * sizeof(double), c->stream, N, V, lam,
+                       scl, y, rec, rcond, C, rank, pinv_rcond, Vs);
+    VI_HIP(hipGetLastError());
+    if (!H) return VI_OK;
+    const double one = 1.0, zero = 0.0;
+    const rocblas_stride s = (rocblas_stride)N * N;
+    VI_ROCBLAS(rocblas_dgemm_strided_batched(c->blas, rocblas_operation_none, rocblas_operation_transpose, N, N, N, &one, Vs, N,
+                                             s, V, N, s, &zero, H, N, s, (rocblas_int)bc));
+    return VI_OK;
+}
+
+}  // namespace
+
 extern "C" int vi_solve_trunc_f64(vi_ctx* c, int64_t B, int32_t N, double* d_X, const double* d_y,
                                   const int32_t* d_rec, double rcond, double* d_C, int32_t* d_rank,
                                   double pinv_rcond, double* d_H)
@@ -654,147 +658,87 @@ extern "C" int vi_solve_trunc_f64(vi_ctx* c, int64_t B, int32_t N, double* d_X, 
     VI_REQUIRE(B >= 0 && N > 0, "bad size");
     if (B == 0) return VI_OK;
     VI_HIP(hipSetDevice(c->device));
+    const int NN = N * N;
     const int cap = cold_max_sweeps(N);
-    if (!d_H && eig_method() == 2 && vi_jacobi_supported(N)) {
-        // in-LDS Jacobi: chunk the batch so that the rotation logs stay within 4 GiB of workspace
+    if (eig_method() == 2 && (d_H ? vi_jacobi_vectors_supported(N) : vi_jacobi_supported(N))) {
+        // in-LDS Jacobi, the batch in chunks whose rotation logs stay within 4 GiB of workspace.  Final solves, which want
+        // H = pinv(X): C, eigenvalues, rotation log -> eigenvectors from the log -> H = V diag(1/lam | kept) V^T
         const bool qr = qr_enabled(N);
         const size_t logb = vi_jacobi_log_bytes(N, cap);
         const size_t hhb = qr ? up16(vi_qr_hh_bytes(N)) : 0;
-        const size_t per = logb + sizeof(double) + (qr ? hhb + (size_t)(N * N + N) * sizeof(double) : 0);
-        int64_t Bc = (int64_t)(((size_t)4 << 30) / per);
-        if (Bc < 1) Bc = 1;
-        if (Bc > B) Bc = B;
-        void* ws = nullptr;
-        int rc = vi_ctx_workspace(c, (size_t)Bc * per + 256, &ws);
-        if (rc != VI_OK) return rc;
-        double* scl = (double*)((char*)ws + (size_t)Bc * logb);
-        double* hh = scl + Bc + (Bc & 1);
-        double* scr = (double*)((char*)hh + (size_t)Bc * hhb);
-        double* y1 = scr + (size_t)Bc * N * N;
-        for (int64_t i0 = 0; i0 < B; i0 += Bc) {
-            const int64_t bc = (B - i0) < Bc ? (B - i0) : Bc;
-            double* Xc = d_X + i0 * N * N;
-            const double* yc = d_rec ? d_y : d_y + i0 * N;
-            const int* rcc = d_rec ? d_rec + i0 : nullptr;
-            hipLaunchKernelGGL(k_scale_system<256>, dim3((unsigned)bc), dim3(256), 0, c->stream, N * N, Xc, scl);
-            VI_HIP(hipGetLastError());
-            if (qr) {
-                if ((rc = vi_qr_precond(c, bc, N, Xc, yc, rcc, Xc, y1, hh, scr, (int64_t)(hhb / 8))) != VI_OK) return rc;
-                yc = y1;
-                rcc = nullptr;
+        const size_t per = logb + sizeof(double) + (qr ? hhb + (size_t)(NN + N) * sizeof(double) : 0);
+        const int64_t Bc = chunk_size((size_t)4 << 30, d_H ? logb : per, B);
+        cold_dst d{};
+        double *V = nullptr, *Vs = nullptr;
+        int rc = ws_carve(c, [&](ws_carver& w) {
+            d.log = w.take<char>((size_t)Bc * logb);
+            d.scl = w.take<double>(Bc);
+            if (d_H) {
+                d.lam = w.take<double>((size_t)Bc * N);
+                V = w.take<double>((size_t)Bc * NN);
+                Vs = w.take<double>((size_t)Bc * NN);
+                d.nround = w.take<int>(Bc);
             }
-            rc = vi_jacobi_solve(c, bc, N, Xc, scl, yc, rcc, rcond, d_C + i0 * N, d_rank ? d_rank + i0 : nullptr, ws,
-                                 cap, nullptr, nullptr, 0, nullptr, JACOBI_FLOOR_COLD);
-            if (rc != VI_OK) return rc;
-            if (qr && (rc = vi_qr_back_vec(c, bc, N, hh, d_C + i0 * N, (int64_t)(hhb / 8))) != VI_OK) return rc;
-        }
-        return VI_OK;
-    }
-    if (d_H && eig_method() == 2 && vi_jacobi_vectors_supported(N)) {
-        // final solves with H = pinv(X): in-LDS Jacobi (C, eigenvalues, rotation log) -> eigenvectors from the
-        // log -> H = V diag(1/lam | kept) V^T
-        const bool qr = qr_enabled(N);
-        const size_t logb = vi_jacobi_log_bytes(N, cap);
-        const size_t hhb = qr ? up16(vi_qr_hh_bytes(N)) : 0;
-        int64_t Bc = (int64_t)(((size_t)4 << 30) / logb);
-        if (Bc < 1) Bc = 1;
-        if (Bc > B) Bc = B;
-        void* ws = nullptr;
-        const size_t per = logb + (size_t)(N + 1) * sizeof(double) + sizeof(int) + (size_t)2 * N * N * sizeof(double) +
-                           (qr ? hhb + (size_t)N * sizeof(double) : 0);
-        int rc = vi_ctx_workspace(c, (size_t)Bc * per + 1024, &ws);
+            if (qr) {
+                d.hh = w.take<double>((size_t)Bc * (hhb / 8));
+                d.y1 = w.take<double>((size_t)Bc * N);
+                d.scr = d_H ? Vs : w.take<double>((size_t)Bc * NN);      // (Vs is free until k_trunc_apply)
+            }
+        });
         if (rc != VI_OK) return rc;
-        char* wp = (char*)ws + (size_t)Bc * logb;
-        double* scl = (double*)wp;
-        double* lam = scl + Bc;
-        double* V = lam + (size_t)Bc * N;
-        double* Vs = V + (size_t)Bc * N * N;
-        double* y1 = Vs + (size_t)Bc * N * N;
-        double* hh = y1 + (qr ? (size_t)Bc * N : 0);
-        int* nrd = (int*)((char*)hh + (size_t)Bc * hhb);
-        const double one = 1.0, zero = 0.0;
-        for (int64_t i0 = 0; i0 < B; i0 += Bc) {
-            const int64_t bc = (B - i0) < Bc ? (B - i0) : Bc;
-            double* Xc = d_X + i0 * N * N;
+        d.hh_stride = (int64_t)hhb;
+        d.cap = cap;
+        d.lam_raw = d_H ? 1 : 0;
+        d.C_back = !d_H;
+        return for_chunks(B, Bc, [&](int64_t i0, int64_t bc) -> int {
             const double* yc = d_rec ? d_y : d_y + i0 * N;
-            const int* rc_ = d_rec ? d_rec + i0 : nullptr;
-            hipLaunchKernelGGL(k_scale_system<256>, dim3((unsigned)bc), dim3(256), 0, c->stream, N * N, Xc, scl);
-            VI_HIP(hipGetLastError());
-            // pre-conditioned: the Jacobi kernel works on X1 = Q^T X Q (Vs is free until k_trunc_apply: QR scratch);
-            // its eigenvectors are turned back, V = Q V1, and k_trunc_apply then sees X's own eigenpairs and y
-            if (qr && (rc = vi_qr_precond(c, bc, N, Xc, yc, rc_, Xc, y1, hh, Vs, (int64_t)(hhb / 8))) != VI_OK) return rc;
-            rc = vi_jacobi_solve(c, bc, N, Xc, scl, qr ? y1 : yc, qr ? nullptr : rc_, rcond, d_C + i0 * N,
-                                 d_rank ? d_rank + i0 : nullptr, ws, cap, nullptr, lam, 1, nrd, JACOBI_FLOOR_COLD);
-            if (rc != VI_OK) return rc;
-            rc = vi_jacobi_vectors(c, bc, N, ws, cap, nrd, V);
-            if (rc != VI_OK) return rc;
-            if (qr && (rc = vi_qr_back_mat(c, bc, N, hh, V, (int64_t)(hhb / 8))) != VI_OK) return rc;
-            constexpr int BS = 256;
-            hipLaunchKernelGGL(k_trunc_apply<BS>, dim3((unsigned)bc), dim3(BS), (size_t)(N + BS) * sizeof(double), c->stream,
-                               N, V, lam, scl, yc, rc_, rcond, d_C + i0 * N, d_rank ? d_rank + i0 : nullptr, pinv_rcond, Vs);
-            VI_HIP(hipGetLastError());
-            VI_ROCBLAS(rocblas_dgemm_strided_batched(c->blas, rocblas_operation_none, rocblas_operation_transpose, N, N, N,
-                                                     &one, Vs, N, (rocblas_stride)N * N, V, N, (rocblas_stride)N * N, &zero,
-                                                     d_H + i0 * N * N, N, (rocblas_stride)N * N, (rocblas_int)bc));
-        }
-        return VI_OK;
+            const int* recc = d_rec ? d_rec + i0 : nullptr;
+            d.C = d_C + i0 * N;
+            d.rank = d_rank ? d_rank + i0 : nullptr;
+            int r = cold_solve(c, bc, N, d_X + i0 * NN, yc, recc, rcond, d);
+            if (r != VI_OK || !d_H) return r;
+            // pre-conditioned: the Jacobi kernel worked on X1 = Q^T X Q; its eigenvectors are turned back, V = Q V1, and
+            // k_trunc_apply then sees X's own eigenpairs and y
+            if ((r = vi_jacobi_vectors(c, bc, N, d.log, cap, d.nround, V)) != VI_OK) return r;
+            if (qr && (r = vi_qr_back_mat(c, bc, N, d.hh, V, d.hh_stride / 8)) != VI_OK) return r;
+            return trunc_from_eigenpairs(c, bc, N, V, d.lam, d.scl, yc, recc, rcond, d.C, d.rank, pinv_rcond, Vs, d_H + i0 * NN);
+        });
     }
     // The library path in launches of at most 4 GiB of systems (404 at N = 1152): one batched syevd call on 1618 systems of
     // that order - 17 GB, 2.147e9 elements, a hair under 2^31 - ended in a GPU memory access fault inside the library
     // (round 4); up to 392 systems per call is what every earlier round ran.  The cost per system is flat from 64 systems on.
-    {
-        int64_t Bmax = (int64_t)(((size_t)4 << 30) / ((size_t)N * N * sizeof(double)));
-        if (Bmax < 1) Bmax = 1;
-        if (B > Bmax) {
-            for (int64_t i0 = 0; i0 < B; i0 += Bmax) {
-                const int64_t bc = (B - i0) < Bmax ? (B - i0) : Bmax;
-                const int rc2 = vi_solve_trunc_f64(c, bc, N, d_X + i0 * N * N, d_rec ? d_y : d_y + i0 * N, d_rec ? d_rec + i0 : nullptr,
-                                                   rcond, d_C + i0 * N, d_rank ? d_rank + i0 : nullptr, pinv_rcond,
-                                                   d_H ? d_H + i0 * N * N : nullptr);
-                if (rc2 != VI_OK) return rc2;
-            }
-            return VI_OK;
-        }
-    }
-    // workspace: eigenvalues [B][N], E [B][N], info [B], (Vs [B][N][N] when H is wanted)
-    const size_t nD = (size_t)B * N;
-    size_t bytes = 2 * nD * sizeof(double) + (size_t)B * sizeof(double) + (size_t)B * sizeof(int) * 4 + 256;
-    if (d_H) bytes += (size_t)B * N * N * sizeof(double);
-    void* ws = nullptr;
-    int rc = vi_ctx_workspace(c, bytes, &ws);
+    const int64_t Bmax = chunk_size((size_t)4 << 30, (size_t)NN * sizeof(double), B);
+    if (B > Bmax)
+        return for_chunks(B, Bmax, [&](int64_t i0, int64_t bc) -> int {
+            return vi_solve_trunc_f64(c, bc, N, d_X + i0 * NN, d_rec ? d_y : d_y + i0 * N, d_rec ? d_rec + i0 : nullptr, rcond,
+                                      d_C + i0 * N, d_rank ? d_rank + i0 : nullptr, pinv_rcond, d_H ? d_H + i0 * NN : nullptr);
+        });
+    // workspace: eigenvalues [B][N], E [B][N], (Vs [B][N][N] when H is wanted), info and sweep counts [B]
+    double *D, *E, *scl, *Vs = nullptr;
+    int *info, *nsweeps;
+    int rc = ws_carve(c, [&](ws_carver& w) {
+        D = w.take<double>((size_t)B * N);
+        E = w.take<double>((size_t)B * N);
+        scl = w.take<double>(B);
+        if (d_H) Vs = w.take<double>((size_t)B * NN);
+        info = w.take<int>(B);
+        nsweeps = w.take<int>(B);
+    });
     if (rc != VI_OK) return rc;
-    double* D = (double*)ws;
-    double* E = D + nD;
-    double* scl = E + nD;
-    double* Vs = d_H ? scl + B : nullptr;
-    int* info = (int*)((char*)ws + (2 * nD + (size_t)B) * sizeof(double) + (d_H ? (size_t)B * N * N * sizeof(double) : 0));
-    hipLaunchKernelGGL(k_scale_system<256>, dim3((unsigned)B), dim3(256), 0, c->stream, N * N, d_X, scl);
+    hipLaunchKernelGGL(k_scale_system<256>, dim3((unsigned)B), dim3(256), 0, c->stream, NN, d_X, scl);
     VI_HIP(hipGetLastError());
     // orders beyond the in-LDS solver (N > ~200): divide and conquer.  Measured at N = 1152 (configs[4]): syevd 10.6 ms
     // per system against 295 ms for rocSOLVER's Jacobi (syevj), which is only used when asked for (VINTERP_EIG=syevj).
     if (eig_method() == 1) {
-        int* nsweeps = info + B;
         double* resid = E;
         VI_ROCSOLVER(rocsolver_dsyevj_strided_batched(c->blas, rocblas_esort_ascending, rocblas_evect_original,
-                                                      rocblas_fill_upper, N, d_X, N, (rocblas_stride)N * N, 0.0, resid,
+                                                      rocblas_fill_upper, N, d_X, N, (rocblas_stride)NN, 0.0, resid,
                                                       100, nsweeps, D, N, info, (rocblas_int)B));
     } else {
         VI_ROCSOLVER(rocsolver_dsyevd_strided_batched(c->blas, rocblas_evect_original, rocblas_fill_upper, N, d_X, N,
-                                                      (rocblas_stride)N * N, D, N, E, N, info, (rocblas_int)B));
+                                                      (rocblas_stride)NN, D, N, E, N, info, (rocblas_int)B));
     }
-    constexpr int BS = 256;
-    const size_t shm = (size_t)(N + BS) * sizeof(double);
-    hipLaunchKernelGGL(k_trunc_apply<BS>, dim3((unsigned)B), dim3(BS), shm, c->stream, N, d_X, D, scl, d_y, d_rec, rcond,
-                       d_C, d_rank, pinv_rcond, Vs);
-    VI_HIP(hipGetLastError());
-    if (d_H) {
-        const double one = 1.0, zero = 0.0;
-        // H = Vs V^T (column-major N x N; symmetric)
-        VI_ROCBLAS(rocblas_dgemm_strided_batched(c->blas, rocblas_operation_none, rocblas_operation_transpose, N, N, N,
-                                                 &one, Vs, N, (rocblas_stride)N * N, d_X, N, (rocblas_stride)N * N,
-                                                 &zero, d_H, N, (rocblas_stride)N * N, (rocblas_int)B));
-    }
-    return VI_OK;
+    return trunc_from_eigenpairs(c, B, N, d_X, D, scl, d_y, d_rec, rcond, d_C, d_rank, pinv_rcond, Vs, d_H);
 }
 
 extern "C" int vi_chi2_f64(vi_ctx* c, int64_t B, int64_t P, int32_t N, const double* d_At, const double* d_C,
@@ -859,26 +803,28 @@ extern "C" int vi_eigvals_f64(vi_ctx* c, int64_t B, int32_t N, double* d_X, doub
     }
     VI_HIP(hipSetDevice(c->device));
     const bool qr = qr_enabled(N);
-    const int cap = cold_max_sweeps(N);
-    const size_t logb = vi_jacobi_log_bytes(N, cap);
     const size_t hhb = qr ? up16(vi_qr_hh_bytes(N)) : 0;
-    void* ws = nullptr;
-    int rc = vi_ctx_workspace(c, (size_t)B * logb + (size_t)B * (N + 1) * sizeof(double) * 3 + 256 +
-                                     (qr ? (size_t)B * (hhb + (size_t)N * N * sizeof(double)) : 0), &ws);
+    cold_dst d{};
+    d.cap = cold_max_sweeps(N);
+    double* yz;                      // zero right-hand sides
+    int rc = ws_carve(c, [&](ws_carver& w) {
+        d.log = w.take<char>((size_t)B * vi_jacobi_log_bytes(N, d.cap));
+        d.scl = w.take<double>(B);
+        yz = w.take<double>((size_t)B * N);
+        d.C = w.take<double>((size_t)B * N);
+        if (qr) {
+            d.y1 = w.take<double>((size_t)B * N);
+            d.hh = w.take<double>((size_t)B * (hhb / 8));
+            d.scr = w.take<double>((size_t)B * N * N);
+        }
+    });
     if (rc != VI_OK) return rc;
-    double* scl = (double*)((char*)ws + (size_t)B * logb);
-    double* yz = scl + B + (B & 1);  // zero right-hand sides
-    double* Cz = yz + (size_t)B * N;
-    double* y1 = Cz + (size_t)B * N;
-    double* hh = y1 + (size_t)B * N + ((B * N) & 1);
-    double* scr = (double*)((char*)hh + (size_t)B * hhb);
+    d.hh_stride = (int64_t)hhb;
+    d.sweeps = d_sweeps;
+    d.lam = d_lam;
     VI_HIP(hipMemsetAsync(yz, 0, (size_t)B * N * sizeof(double), c->stream));
-    hipLaunchKernelGGL(k_scale_system<256>, dim3((unsigned)B), dim3(256), 0, c->stream, N * N, d_X, scl);
-    VI_HIP(hipGetLastError());
     // the same pre-conditioning as vi_solve_trunc_f64 (X1 = Q^T X Q has X's eigenvalues)
-    if (qr && (rc = vi_qr_precond(c, B, N, d_X, yz, nullptr, d_X, y1, hh, scr, (int64_t)(hhb / 8))) != VI_OK) return rc;
-    return vi_jacobi_solve(c, B, N, d_X, scl, yz, nullptr, 2.220446049250313e-16, Cz, nullptr, ws,
-                           cap, d_sweeps, d_lam, 0, nullptr, JACOBI_FLOOR_COLD);
+    return cold_solve(c, B, N, d_X, yz, nullptr, 2.220446049250313e-16, d);
 }
 
 // ---- warm-started search -------------------------------------------------------------------------------
@@ -894,42 +840,70 @@ size_t log_record_bytes(int N)
     return vi_jacobi_log_bytes(N, JACOBI_MAX_SWEEPS) + (qr_enabled(N) ? up16(vi_qr_hh_bytes(N)) : 0);
 }
 
-// phase 1 of setting up rotated systems: X(alpha0) of bc records formed, scaled, pre-conditioned (y1, scr: N and N x N
-// doubles of scratch per system) and decomposed (cold), the truncated solution to Cc, the rotation logs (+ reflectors) to
-// the records at `log`, the rounds they hold to nrd
+// Workspace of the two phases, for n systems at a time
+struct prep_ws {
+    double *scl, *lam, *y1;      // phase 1: scales, eigenvalues, K3p's Q^T y
+    double *T0, *T1;             // N x N per system: X0, later AWA[rec]; K3p's scratch, later products
+    double *scrT, *scrD;         // phase 2: results of the padding entries of the last product group
+    const double** parr;         // ... and 6 pointer arrays of np = group_pad(n) entries
+    int64_t np;
+    void decompose(ws_carver& w, int64_t n, int N)
+    {
+        scl = w.take<double>(n);
+        lam = w.take<double>((size_t)n * N);
+        y1 = w.take<double>((size_t)n * N);
+    }
+    void matrices(ws_carver& w, int64_t n, int N)
+    {
+        T0 = w.take<double>((size_t)n * N * N);
+        T1 = w.take<double>((size_t)n * N * N);
+    }
+    void finish(ws_carver& w, int64_t n, int N)
+    {
+        scrT = w.take<double>((size_t)GEMM_GROUP * N * N);
+        scrD = w.take<double>((size_t)GEMM_GROUP * N * N);
+        np = group_pad(n);
+        parr = w.take<const double*>((size_t)6 * np);
+    }
+};
+
+// phase 1 of setting up rotated systems: X(alpha0) of bc records formed and decomposed (cold), the truncated solution to
+// Cc, the rotation logs (+ reflectors) to the records at `log`, the rounds they hold to nrd
 int prep_decompose(vi_ctx* c, int64_t bc, int N, const double* d_AWA, const int32_t* recc, const double* alpha0c,
-                   const double* d_R, const double* d_y, double rcond, double* Cc, int32_t* rankc, void* log, double* scl,
-                   double* lam, double* T0, int* nrd, double* y1, double* scr)
+                   const double* d_R, const double* d_y, double rcond, double* Cc, int32_t* rankc, void* log, int* nrd,
+                   const prep_ws& p)
 {
-    const int NN = N * N;
-    const bool qr = qr_enabled(N);
-    const size_t logb = vi_jacobi_log_bytes(N, JACOBI_MAX_SWEEPS), recb = log_record_bytes(N);
-    double* hh = (double*)((char*)log + logb);
-    hipLaunchKernelGGL(k_form_system, dim3((unsigned)bc), dim3(256), 0, c->stream, NN, d_AWA, recc, alpha0c, d_R, T0);
-    hipLaunchKernelGGL(k_scale_system<256>, dim3((unsigned)bc), dim3(256), 0, c->stream, NN, T0, scl);
-    VI_HIP(hipGetLastError());
-    int rc;
-    if (qr && (rc = vi_qr_precond(c, bc, N, T0, d_y, recc, T0, y1, hh, scr, (int64_t)(recb / 8))) != VI_OK) return rc;
-    rc = vi_jacobi_solve(c, bc, N, T0, scl, qr ? y1 : d_y, qr ? nullptr : recc, rcond, Cc, rankc, log, JACOBI_MAX_SWEEPS, nullptr,
-                         lam, 1, nrd, JACOBI_FLOOR_COLD, (int64_t)(recb / 16));
-    if (rc != VI_OK) return rc;
-    if (qr) return vi_qr_back_vec(c, bc, N, hh, Cc, (int64_t)(recb / 8));
-    return VI_OK;
+    hipLaunchKernelGGL(k_form_system, dim3((unsigned)bc), dim3(256), 0, c->stream, N * N, d_AWA, recc, alpha0c, d_R, p.T0);
+    cold_dst d{};
+    d.C = Cc;
+    d.rank = rankc;
+    d.C_back = true;
+    d.log = log;
+    d.hh = (double*)((char*)log + vi_jacobi_log_bytes(N, JACOBI_MAX_SWEEPS));
+    d.log_stride = d.hh_stride = (int64_t)log_record_bytes(N);
+    d.scl = p.scl;
+    d.y1 = p.y1;
+    d.scr = p.T1;
+    d.lam = p.lam;
+    d.lam_raw = 1;
+    d.nround = nrd;
+    d.cap = JACOBI_MAX_SWEEPS;
+    return cold_solve(c, bc, N, p.T0, d_y, recc, rcond, d);
 }
 
 // phase 2: eigenvectors from the logs, D1 = V^T (AWA V), D2 = V^T (R V) - four batched products in groups of fixed size
-// (see GEMM_GROUP) - and yt = V^T y.  parr: room for 6 pointer arrays of Bcp entries.
+// (see GEMM_GROUP) - and yt = V^T y
 int prep_finish(vi_ctx* c, int64_t bc, int N, const void* log, const int* nrd, const double* d_AWA, const int32_t* recc,
-                const double* d_R, const double* d_y, double* Vc, double* D1c, double* D2c, double* ytc, double* T0, double* T1,
-                double* scrT, double* scrD, const double** parr, int64_t Bcp)
+                const double* d_R, const double* d_y, double* Vc, double* D1c, double* D2c, double* ytc, const prep_ws& p)
 {
     const int NN = N * N;
-    const double** pT0 = parr;
-    const double** pV = pT0 + Bcp;
-    const double** pT1 = pV + Bcp;
-    const double** pR = pT1 + Bcp;
-    const double** pD1 = pR + Bcp;
-    const double** pD2 = pD1 + Bcp;
+    double *T0 = p.T0, *T1 = p.T1, *scrT = p.scrT, *scrD = p.scrD;
+    const double** pT0 = p.parr;
+    const double** pV = pT0 + p.np;
+    const double** pT1 = pV + p.np;
+    const double** pR = pT1 + p.np;
+    const double** pD1 = pR + p.np;
+    const double** pD2 = pD1 + p.np;
     const size_t recb = log_record_bytes(N);
     int rc = vi_jacobi_vectors(c, bc, N, log, JACOBI_MAX_SWEEPS, nrd, Vc, (int64_t)(recb / 16));
     if (rc != VI_OK) return rc;
@@ -970,38 +944,29 @@ extern "C" int vi_warm_prepare_f64(vi_ctx* c, int64_t B, int32_t N, const double
     }
     VI_HIP(hipSetDevice(c->device));
     const int NN = N * N;
-    const size_t logb = log_record_bytes(N);
-    const size_t per = logb + (size_t)(2 * N + 1) * sizeof(double) + sizeof(int) + (size_t)2 * NN * sizeof(double) + 6 * sizeof(void*);
+    const size_t recb = log_record_bytes(N);
+    const size_t per = recb + (size_t)(2 * N + 1) * sizeof(double) + sizeof(int) + (size_t)2 * NN * sizeof(double) + 6 * sizeof(void*);
     // chunks of records, so that the rotation logs and temporaries stay within 4 GiB of workspace (4.3 MB per record at
     // N = 144: 10 000 records at once would ask for 43 GB)
-    int64_t Bc = (int64_t)(((size_t)4 << 30) / per);
-    if (Bc < 1) Bc = 1;
-    if (Bc > B) Bc = B;
-    const int64_t Bcp = group_pad(Bc);
-    void* ws = nullptr;
-    int rc = vi_ctx_workspace(c, (size_t)Bc * per + (size_t)2 * GEMM_GROUP * NN * sizeof(double) + 6 * GEMM_GROUP * sizeof(void*) + 1024,
-                              &ws);
+    const int64_t Bc = chunk_size((size_t)4 << 30, per, B);
+    void* log;
+    int* nrd;
+    prep_ws p{};
+    int rc = ws_carve(c, [&](ws_carver& w) {
+        log = w.take<char>((size_t)Bc * recb);
+        p.decompose(w, Bc, N);
+        p.matrices(w, Bc, N);
+        p.finish(w, Bc, N);
+        nrd = w.take<int>(Bc);
+    });
     if (rc != VI_OK) return rc;
-    char* wp = (char*)ws + (size_t)Bc * logb;
-    double* scl = (double*)wp;
-    double* lam = scl + Bc;
-    double* T0 = lam + (size_t)Bc * N;     // X0, later AWA[rec]
-    double* T1 = T0 + (size_t)Bc * NN;
-    double* scrT = T1 + (size_t)Bc * NN;   // results of the padding entries of the last product group
-    double* scrD = scrT + (size_t)GEMM_GROUP * NN;
-    const double** parr = (const double**)(scrD + (size_t)GEMM_GROUP * NN);
-    double* y1 = (double*)(parr + 6 * Bcp);
-    int* nrd = (int*)(y1 + (size_t)Bc * N);
-    for (int64_t i0 = 0; i0 < B; i0 += Bc) {
-        const int64_t bc = (B - i0) < Bc ? (B - i0) : Bc;
-        rc = prep_decompose(c, bc, N, d_AWA, d_rec + i0, d_alpha0 + i0, d_R, d_y, rcond, d_C + i0 * N,
-                            d_rank ? d_rank + i0 : nullptr, ws, scl, lam, T0, nrd, y1, T1);
-        if (rc != VI_OK) return rc;
-        rc = prep_finish(c, bc, N, ws, nrd, d_AWA, d_rec + i0, d_R, d_y, d_V + i0 * NN, d_D1 + i0 * NN, d_D2 + i0 * NN,
-                         d_yt + i0 * N, T0, T1, scrT, scrD, parr, Bcp);
-        if (rc != VI_OK) return rc;
-    }
-    return VI_OK;
+    return for_chunks(B, Bc, [&](int64_t i0, int64_t bc) -> int {
+        const int r = prep_decompose(c, bc, N, d_AWA, d_rec + i0, d_alpha0 + i0, d_R, d_y, rcond, d_C + i0 * N,
+                                     d_rank ? d_rank + i0 : nullptr, log, nrd, p);
+        if (r != VI_OK) return r;
+        return prep_finish(c, bc, N, log, nrd, d_AWA, d_rec + i0, d_R, d_y, d_V + i0 * NN, d_D1 + i0 * NN, d_D2 + i0 * NN,
+                           d_yt + i0 * N, p);
+    });
 }
 
 // The two phases of vi_warm_prepare_f64 as separate calls, with the rotation logs in a buffer of the caller
@@ -1025,10 +990,7 @@ double vi_floor_warm() { return JACOBI_FLOOR_WARM; }
 namespace {
 double walk_tolerance()
 {
-    static const double v = [] {
-        const char* e = getenv("VINTERP_WALK_TOL");
-        return e ? atof(e) : 1e-6;
-    }();
+    static const double v = vi_env_double("VINTERP_WALK_TOL", 1e-6);
     return v;
 }
 }  // namespace
@@ -1045,16 +1007,13 @@ extern "C" int vi_decompose_f64(vi_ctx* c, int64_t B, int32_t N, const double* d
         return VI_ERR_UNSUPPORTED;
     }
     VI_HIP(hipSetDevice(c->device));
-    const int NN = N * N;
-    void* ws = nullptr;
-    int rc = vi_ctx_workspace(c, (size_t)B * ((size_t)(2 * N + 1 + 2 * NN) * sizeof(double)) + 1024, &ws);
+    prep_ws p{};
+    int rc = ws_carve(c, [&](ws_carver& w) {
+        p.decompose(w, B, N);
+        p.matrices(w, B, N);
+    });
     if (rc != VI_OK) return rc;
-    double* scl = (double*)ws;
-    double* lam = scl + B;
-    double* T0 = lam + (size_t)B * N;
-    double* scr = T0 + (size_t)B * NN;
-    double* y1 = scr + (size_t)B * NN;
-    return prep_decompose(c, B, N, d_AWA, d_rec, d_alpha0, d_R, d_y, rcond, d_C, d_rank, d_log, scl, lam, T0, d_nround, y1, scr);
+    return prep_decompose(c, B, N, d_AWA, d_rec, d_alpha0, d_R, d_y, rcond, d_C, d_rank, d_log, d_nround, p);
 }
 
 extern "C" int vi_warm_finish_f64(vi_ctx* c, int64_t B, int32_t N, const void* d_log, const int32_t* d_nround,
@@ -1069,17 +1028,13 @@ extern "C" int vi_warm_finish_f64(vi_ctx* c, int64_t B, int32_t N, const void* d
         return VI_ERR_UNSUPPORTED;
     }
     VI_HIP(hipSetDevice(c->device));
-    const int NN = N * N;
-    const int64_t Bp = group_pad(B);
-    void* ws = nullptr;
-    int rc = vi_ctx_workspace(c, (size_t)(2 * B + 2 * GEMM_GROUP) * NN * sizeof(double) + (size_t)6 * Bp * sizeof(void*) + 1024, &ws);
+    prep_ws p{};
+    int rc = ws_carve(c, [&](ws_carver& w) {
+        p.matrices(w, B, N);
+        p.finish(w, B, N);
+    });
     if (rc != VI_OK) return rc;
-    double* T0 = (double*)ws;
-    double* T1 = T0 + (size_t)B * NN;
-    double* scrT = T1 + (size_t)B * NN;
-    double* scrD = scrT + (size_t)GEMM_GROUP * NN;
-    const double** parr = (const double**)(scrD + (size_t)GEMM_GROUP * NN);
-    return prep_finish(c, B, N, d_log, d_nround, d_AWA, d_rec, d_R, d_y, d_V, d_D1, d_D2, d_yt, T0, T1, scrT, scrD, parr, Bp);
+    return prep_finish(c, B, N, d_log, d_nround, d_AWA, d_rec, d_R, d_y, d_V, d_D1, d_D2, d_yt, p);
 }
 
 extern "C" int vi_warm_solve_f64(vi_ctx* c, int64_t B, int32_t N, const double* d_D1, const double* d_D2,
@@ -1096,29 +1051,27 @@ extern "C" int vi_warm_solve_f64(vi_ctx* c, int64_t B, int32_t N, const double* 
     VI_HIP(hipSetDevice(c->device));
     const int NN = N * N;
     const size_t logb = vi_jacobi_log_bytes(N, JACOBI_MAX_SWEEPS);
-    int64_t Bc = (int64_t)(((size_t)4 << 30) / logb);
-    if (Bc < 1) Bc = 1;
-    if (Bc > B) Bc = B;
-    void* ws = nullptr;
-    const size_t per = logb + sizeof(double) + (size_t)NN * sizeof(double) + (size_t)N * sizeof(double);
-    int rc = vi_ctx_workspace(c, (size_t)Bc * per + 1024, &ws);
+    const int64_t Bc = chunk_size((size_t)4 << 30, logb, B);
+    void* log;
+    double *scl, *X, *cp;
+    int rc = ws_carve(c, [&](ws_carver& w) {
+        log = w.take<char>((size_t)Bc * logb);
+        scl = w.take<double>(Bc);
+        X = w.take<double>((size_t)Bc * NN);
+        cp = w.take<double>((size_t)Bc * N);
+    });
     if (rc != VI_OK) return rc;
-    char* wp = (char*)ws + (size_t)Bc * logb;
-    double* scl = (double*)wp;
-    double* X = scl + Bc;
-    double* cp = X + (size_t)Bc * NN;
-    for (int64_t i0 = 0; i0 < B; i0 += Bc) {
-        const int64_t bc = (B - i0) < Bc ? (B - i0) : Bc;
+    return for_chunks(B, Bc, [&](int64_t i0, int64_t bc) -> int {
         form_pair_scaled(c, bc, NN, d_D1, d_D2, d_slot + i0, d_slot + i0, d_alpha + i0, X, scl);
         VI_HIP(hipGetLastError());
-        rc = vi_jacobi_solve(c, bc, N, X, scl, d_yt, d_slot + i0, rcond, cp, d_rank ? d_rank + i0 : nullptr, ws,
-                             JACOBI_MAX_SWEEPS, d_sweeps ? d_sweeps + i0 : nullptr, nullptr, 0, nullptr, JACOBI_FLOOR_WARM);
-        if (rc != VI_OK) return rc;
+        const int r = vi_jacobi_solve(c, bc, N, X, scl, d_yt, d_slot + i0, rcond, cp, d_rank ? d_rank + i0 : nullptr, log,
+                                      JACOBI_MAX_SWEEPS, d_sweeps ? d_sweeps + i0 : nullptr, nullptr, 0, nullptr, JACOBI_FLOOR_WARM);
+        if (r != VI_OK) return r;
         hipLaunchKernelGGL(k_v_vec, dim3((unsigned)bc), dim3(256), (size_t)N * sizeof(double), c->stream, N, d_V,
                            d_slot + i0, cp, d_C + i0 * N);
         VI_HIP(hipGetLastError());
-    }
-    return VI_OK;
+        return VI_OK;
+    });
 }
 
 namespace {
@@ -1197,26 +1150,26 @@ extern "C" int vi_basis_solve_f64(vi_ctx* c, int64_t B, int32_t N, const double*
     const int NN = N * N;
     const size_t logb = vi_jacobi_log_bytes(N, JACOBI_MAX_SWEEPS);
     const size_t per = logb + sizeof(double) + (size_t)2 * NN * sizeof(double) + (size_t)2 * N * sizeof(double) + 4 * sizeof(void*);
-    int64_t Bc = (int64_t)(((size_t)8 << 30) / per);
-    if (Bc > 256) Bc &= ~(int64_t)255;            // whole rounds of the 256 CUs
-    if (Bc < 1) Bc = 1;
-    if (Bc > B) Bc = B;
-    void* ws = nullptr;
-    int rc = vi_ctx_workspace(c, (size_t)Bc * per + 1024, &ws);
+    const int64_t Bc = chunk_size((size_t)8 << 30, per, B, 256);            // whole rounds of the 256 CUs
+    void* log;
+    double *scl, *T1, *D1, *yt, *cp;
+    const double **pA, **pV;
+    double **pT, **pD;
+    int rc = ws_carve(c, [&](ws_carver& w) {
+        log = w.take<char>((size_t)Bc * logb);
+        scl = w.take<double>(Bc);
+        T1 = w.take<double>((size_t)Bc * NN);
+        D1 = w.take<double>((size_t)Bc * NN);            // D1, then the scaled system in place
+        yt = w.take<double>((size_t)Bc * N);
+        cp = w.take<double>((size_t)Bc * N);
+        pA = w.take<const double*>(Bc);
+        pV = w.take<const double*>(Bc);
+        pT = w.take<double*>(Bc);
+        pD = w.take<double*>(Bc);
+    });
     if (rc != VI_OK) return rc;
-    char* wp = (char*)ws + (size_t)Bc * logb;
-    double* scl = (double*)wp;
-    double* T1 = scl + Bc;
-    double* D1 = T1 + (size_t)Bc * NN;            // D1, then the scaled system in place
-    double* yt = D1 + (size_t)Bc * NN;
-    double* cp = yt + (size_t)Bc * N;
-    const double** pA = (const double**)(cp + (size_t)Bc * N);
-    const double** pV = pA + Bc;
-    double** pT = (double**)(pV + Bc);
-    double** pD = pT + Bc;
     const double one = 1.0, zero = 0.0;
-    for (int64_t i0 = 0; i0 < B; i0 += Bc) {
-        const int64_t bc = (B - i0) < Bc ? (B - i0) : Bc;
+    return for_chunks(B, Bc, [&](int64_t i0, int64_t bc) -> int {
         hipLaunchKernelGGL(k_basis_ptrs, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, c->stream, bc, NN, d_AWA,
                            d_rec + i0, d_V, d_basis + i0, T1, D1, pA, pV, pT, pD);
         VI_HIP(hipGetLastError());
@@ -1227,15 +1180,15 @@ extern "C" int vi_basis_solve_f64(vi_ctx* c, int64_t B, int32_t N, const double*
         hipLaunchKernelGGL(k_vt_vec, dim3((unsigned)bc), dim3(256), 0, c->stream, N, d_V, d_basis + i0, d_y, d_rec + i0, yt);
         form_pair_scaled(c, bc, NN, D1, d_D2, nullptr, d_basis + i0, d_alpha + i0, D1, scl);
         VI_HIP(hipGetLastError());
-        rc = vi_jacobi_solve(c, bc, N, D1, scl, yt, nullptr, rcond, cp, d_rank ? d_rank + i0 : nullptr, ws,
-                             JACOBI_MAX_SWEEPS, d_sweeps ? d_sweeps + i0 : nullptr, nullptr, 0, nullptr, JACOBI_FLOOR_WARM, 0,
-                             walk_tolerance());
-        if (rc != VI_OK) return rc;
+        const int r = vi_jacobi_solve(c, bc, N, D1, scl, yt, nullptr, rcond, cp, d_rank ? d_rank + i0 : nullptr, log,
+                                      JACOBI_MAX_SWEEPS, d_sweeps ? d_sweeps + i0 : nullptr, nullptr, 0, nullptr,
+                                      JACOBI_FLOOR_WARM, 0, walk_tolerance());
+        if (r != VI_OK) return r;
         hipLaunchKernelGGL(k_v_vec, dim3((unsigned)bc), dim3(256), (size_t)N * sizeof(double), c->stream, N, d_V,
                            d_basis + i0, cp, d_C + i0 * N);
         VI_HIP(hipGetLastError());
-    }
-    return VI_OK;
+        return VI_OK;
+    });
 }
 
 // Re-basing of rotated systems.  Brent's iterates close in on the root within a few steps, and the cost of a warm solve
@@ -1267,8 +1220,7 @@ extern "C" int vi_warm_rebase_f64(vi_ctx* c, int64_t B, int64_t nplain, int32_t 
     const size_t logb = vi_jacobi_log_bytes(N, JACOBI_MAX_SWEEPS);
     const size_t per = logb + sizeof(double) + sizeof(int) + (size_t)3 * NN * sizeof(double) + (size_t)N * sizeof(double) +
                        8 * sizeof(void*);
-    int64_t Bc = (int64_t)(((size_t)4 << 30) / per);
-    if (Bc < 1) Bc = 1;
+    const int64_t Bc = chunk_size((size_t)4 << 30, per, B);
     if (nplain > 0 && B > Bc) {
         // more than one workspace chunk: the plain solves on their own, then the re-basing ones
         int rc0 = vi_warm_solve_f64(c, nplain, N, d_D1, d_D2, d_yt, d_V, d_slot, d_alpha, rcond, d_C, d_rank, d_sweeps);
@@ -1277,44 +1229,38 @@ extern "C" int vi_warm_rebase_f64(vi_ctx* c, int64_t B, int64_t nplain, int32_t 
                                   d_V, d_D1, d_D2, d_yt, d_C + nplain * N, d_rank ? d_rank + nplain : nullptr,
                                   d_sweeps ? d_sweeps + nplain : nullptr);
     }
-    if (Bc > B) Bc = B;
     const int64_t Bcp = group_pad(Bc);
-    void* ws = nullptr;
-    int rc = vi_ctx_workspace(c, (size_t)Bc * per + (size_t)2 * GEMM_GROUP * NN * sizeof(double) + 8 * GEMM_GROUP * sizeof(void*) + 1024,
-                              &ws);
+    char* log;
+    double *scl, *X, *Vw, *Vn, *cp, *scrA, *scrB;
+    const double **pX, **pVold, **pVw, **pVn, **pR, **pD1, **pD2;
+    int* nrd;
+    int rc = ws_carve(c, [&](ws_carver& w) {
+        log = w.take<char>((size_t)Bc * logb);
+        scl = w.take<double>(Bc);
+        X = w.take<double>((size_t)Bc * NN);            // the scaled rotated system, later AWA[rec]
+        Vw = w.take<double>((size_t)Bc * NN);           // eigenvectors of the rotated system, later a product
+        Vn = w.take<double>((size_t)Bc * NN);           // V Vw
+        cp = w.take<double>((size_t)Bc * N);
+        scrA = w.take<double>((size_t)GEMM_GROUP * NN);
+        scrB = w.take<double>((size_t)GEMM_GROUP * NN);
+        for (auto* pp : {&pX, &pVold, &pVw, &pVn, &pR, &pD1, &pD2}) *pp = w.take<const double*>(Bcp);
+        nrd = w.take<int>(Bc);
+    });
     if (rc != VI_OK) return rc;
-    char* wp = (char*)ws + (size_t)Bc * logb;
-    double* scl = (double*)wp;
-    double* X = scl + Bc;                       // the scaled rotated system, later AWA[rec]
-    double* Vw = X + (size_t)Bc * NN;           // eigenvectors of the rotated system, later a product
-    double* Vn = Vw + (size_t)Bc * NN;          // V Vw
-    double* cp = Vn + (size_t)Bc * NN;
-    double* scrA = cp + (size_t)Bc * N;
-    double* scrB = scrA + (size_t)GEMM_GROUP * NN;
-    const double** pX = (const double**)(scrB + (size_t)GEMM_GROUP * NN);
-    const double** pVold = pX + Bcp;
-    const double** pVw = pVold + Bcp;
-    const double** pVn = pVw + Bcp;
-    const double** pR = pVn + Bcp;
-    const double** pD1 = pR + Bcp;
-    const double** pD2 = pD1 + Bcp;
-    const double** pVslot = pD2 + Bcp;
-    int* nrd = (int*)(pVslot + Bcp);
-    for (int64_t i0 = 0; i0 < B; i0 += Bc) {
-        int64_t bc = (B - i0) < Bc ? (B - i0) : Bc;
+    return for_chunks(B, Bc, [&](int64_t i0, int64_t bc) -> int {
         const int32_t* slotc = d_slot + i0;
         const int32_t* recc = d_rec + i0;
         form_pair_scaled(c, bc, NN, d_D1, d_D2, slotc, slotc, d_alpha + i0, X, scl);
         VI_HIP(hipGetLastError());
-        rc = vi_jacobi_solve(c, bc, N, X, scl, d_yt, slotc, rcond, cp, d_rank ? d_rank + i0 : nullptr, ws, JACOBI_MAX_SWEEPS,
-                             d_sweeps ? d_sweeps + i0 : nullptr, nullptr, 0, nrd, JACOBI_FLOOR_WARM);
+        int rc = vi_jacobi_solve(c, bc, N, X, scl, d_yt, slotc, rcond, cp, d_rank ? d_rank + i0 : nullptr, log, JACOBI_MAX_SWEEPS,
+                                 d_sweeps ? d_sweeps + i0 : nullptr, nullptr, 0, nrd, JACOBI_FLOOR_WARM);
         if (rc != VI_OK) return rc;
         hipLaunchKernelGGL(k_v_vec, dim3((unsigned)bc), dim3(256), (size_t)N * sizeof(double), c->stream, N, d_V, slotc, cp,
                            d_C + i0 * N);
         VI_HIP(hipGetLastError());
         // from here on only the systems that re-base (nplain > 0 implies a single chunk, i0 = 0)
         const int64_t skip = i0 == 0 ? nplain : 0;
-        rc = vi_jacobi_vectors(c, bc - skip, N, (const char*)ws + (size_t)skip * logb, JACOBI_MAX_SWEEPS, nrd + skip, Vw);
+        rc = vi_jacobi_vectors(c, bc - skip, N, log + (size_t)skip * logb, JACOBI_MAX_SWEEPS, nrd + skip, Vw);
         if (rc != VI_OK) return rc;
         slotc += skip;
         recc += skip;
@@ -1339,8 +1285,8 @@ extern "C" int vi_warm_rebase_f64(vi_ctx* c, int64_t B, int64_t nplain, int32_t 
         if ((rc = wg_gemm_batched(c, true, N, pVn, pVw, pD2, bc)) != VI_OK) return rc;
         hipLaunchKernelGGL(k_vt_vec_slot, dim3((unsigned)bc), dim3(256), 0, c->stream, N, Vn, d_y, recc, slotc, d_yt);
         VI_HIP(hipGetLastError());
-    }
-    return VI_OK;
+        return VI_OK;
+    });
 }
 
 // One root-finder iterate of ONE record in a single call (the latency path of a single-record fit: ~14 dependent
@@ -1398,26 +1344,23 @@ extern "C" int vi_gcv_terms_f64(vi_ctx* c, int64_t np, int64_t P, int32_t N, con
     const int NN = N * N;
     // systems are formed and solved in chunks; X / y / C live in a private allocation because
     // vi_solve_trunc_f64 uses the context workspace itself
-    int64_t Bc = (int64_t)(((size_t)1 << 30) / ((size_t)NN * sizeof(double)));
-    if (Bc < 1) Bc = 1;
-    if (Bc > np) Bc = np;
+    const int64_t Bc = chunk_size((size_t)1 << 30, (size_t)NN * sizeof(double), np);
     double* buf = nullptr;
     VI_HIP(hipMalloc((void**)&buf, (size_t)Bc * (NN + 2 * (size_t)N) * sizeof(double)));
     double* X = buf;
     double* yl = X + (size_t)Bc * NN;
     double* Cl = yl + (size_t)Bc * N;
-    int rc = VI_OK;
-    for (int64_t i0 = 0; i0 < np && rc == VI_OK; i0 += Bc) {
-        const int64_t bc = (np - i0) < Bc ? (np - i0) : Bc;
+    const int rc = for_chunks(np, Bc, [&](int64_t i0, int64_t bc) -> int {
         hipLaunchKernelGGL(k_form_loo, dim3((unsigned)bc), dim3(256), (size_t)N * sizeof(double), c->stream, N, P, d_At,
                            d_pidx + i0, d_AWA, d_y, d_W, d_b, alpha, d_R, X, yl);
-        if (hipGetLastError() != hipSuccess) { vi_set_error("k_form_loo launch failed"); rc = VI_ERR_HIP; break; }
-        rc = vi_solve_trunc_f64(c, bc, N, X, yl, nullptr, rcond, Cl, nullptr, 0.0, nullptr);
-        if (rc != VI_OK) break;
+        if (hipGetLastError() != hipSuccess) { vi_set_error("k_form_loo launch failed"); return VI_ERR_HIP; }
+        const int r = vi_solve_trunc_f64(c, bc, N, X, yl, nullptr, rcond, Cl, nullptr, 0.0, nullptr);
+        if (r != VI_OK) return r;
         hipLaunchKernelGGL(k_loo_resid, dim3((unsigned)((bc + 3) / 4)), dim3(256), 0, c->stream, bc, N, P, d_At, d_pidx + i0,
                            Cl, d_W, d_b, d_res + i0);
-        if (hipGetLastError() != hipSuccess) { vi_set_error("k_loo_resid launch failed"); rc = VI_ERR_HIP; }
-    }
+        if (hipGetLastError() != hipSuccess) { vi_set_error("k_loo_resid launch failed"); return VI_ERR_HIP; }
+        return VI_OK;
+    });
     (void)hipStreamSynchronize(c->stream);
     (void)hipFree(buf);
     return rc;

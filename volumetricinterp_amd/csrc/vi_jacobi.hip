@@ -34,6 +34,7 @@
 //    going to drop anyway; after every sweep all pairs are tested in place and the iteration ends when none would
 //    rotate.
 #include "vi_common.h"
+#include "vi_solver.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -171,22 +172,18 @@ void jacobi_geometry(int N, int& threads, int& it)
 }  // namespace
 
 // The role-separated kernel serves the orders with one super-block per thread that leave room for the set-up wave in a
-// 768-thread workgroup, from 24 matches on (N = 93 ... 148: the benchmarked order 144 with 704 threads; below, the fixed cost of
-// its counters outweighs what it overlaps);
+// 768-thread workgroup, from 24 matches on: M(M - 1)/2 super-blocks fill at most 704 threads up to M = 38 matches (703), so
+// M = 24 ... 38, N = 93 ... 152 (the benchmarked order 144 with 704 threads; below, the fixed cost of its counters outweighs
+// what it overlaps; VINTERP_K3_MINM moves the lower end);
 // VINTERP_K3=v1 keeps the two-barrier kernel everywhere.  Same bits either way (tests/test_gpu_search_stages.py).
 bool vi_jacobi_use_v2(int N)
 {
-    static int forced = -1;
-    if (forced < 0) {
-        const char* e = getenv("VINTERP_K3");
-        forced = (e && !strcmp(e, "v1")) ? 1 : 0;
-    }
-    if (forced) return false;
+    static const bool v1 = vi_env_is("VINTERP_K3", "v1");
+    if (v1) return false;
     int threads, it;
     jacobi_geometry(N, threads, it);
     const int M = ((N + 3) & ~3) / 4;
-    static int minm = -1;
-    if (minm < 0) { const char* e2 = getenv("VINTERP_K3_MINM"); minm = e2 ? atoi(e2) : 24; if (minm < 3) minm = 3; }
+    static const int minm = [] { const int v = vi_env_int("VINTERP_K3_MINM", 24); return v < 3 ? 3 : v; }();
     return it == 1 && M >= minm && M <= 64 && threads + 64 <= 768;     // (from N = 93: measured -2 % at N = 100, -9 % at 144, +2 % at 32)
 }
 

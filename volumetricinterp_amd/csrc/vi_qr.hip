@@ -24,6 +24,7 @@
 //     R P^T: every octet loads its two rows and takes all reflectors; y1 = Q^T y the same way.
 // The reflectors leave in packed form (v_k, then the N taus) for the back-transformation kernels.
 #include "vi_common.h"
+#include "vi_solver.h"
 
 #include <type_traits>
 
@@ -566,11 +567,12 @@ extern "C" int vi_qr_similarity_f64(vi_ctx* c, int64_t B, int32_t N, const doubl
         return VI_ERR_UNSUPPORTED;
     }
     VI_HIP(hipSetDevice(c->device));
-    void* ws = nullptr;
-    int rc = vi_ctx_workspace(c, (size_t)B * (vi_qr_hh_bytes(N) + (size_t)N * N * sizeof(double)) + 256, &ws);
+    double *hhp, *scr;
+    int rc = ws_carve(c, [&](ws_carver& w) {
+        hhp = w.take<double>((size_t)B * (vi_qr_hh_bytes(N) / sizeof(double)));
+        scr = w.take<double>((size_t)B * N * N);
+    });
     if (rc != VI_OK) return rc;
-    double* hhp = (double*)ws;
-    double* scr = hhp + (size_t)B * (vi_qr_hh_bytes(N) / sizeof(double));
     if ((rc = vi_qr_precond(c, B, N, d_X, d_y, nullptr, d_X1, d_y1, hhp, scr, 0)) != VI_OK) return rc;
     // explicit Q: the back-transformation of the identity
     std::vector<double> eye((size_t)N * N, 0.0);

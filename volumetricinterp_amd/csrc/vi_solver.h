@@ -1,0 +1,38 @@
+// Host interface of the solver and evaluation translation units of libvinterp.so: every function that one vi_*.hip defines
+// and another calls is declared here, once, and this header is included by both sides - a definition that drifts from its
+// declaration does not compile.
+#pragma once
+#include "vi_common.h"
+
+// ---- K3, the in-LDS Jacobi solver (vi_jacobi.hip) ----
+size_t vi_jacobi_lds_bytes(int N);
+size_t vi_jacobi_log_bytes(int N, int max_sweeps);
+bool vi_jacobi_supported(int N);
+bool vi_jacobi_use_v2(int N);            // the role-separated kernel serves this order
+int vi_jacobi_solve(vi_ctx* c, int64_t B, int N, const double* d_X, const double* d_scl, const double* d_y,
+                    const int* d_rec, double rcond, double* d_C, int* d_rank, void* d_log, int max_sweeps,
+                    int* d_sweeps, double* d_lam, int lam_raw, int* d_nround, double abs_floor, int64_t log_stride = 0,
+                    double conv_tol = 0.0);
+bool vi_jacobi_vectors_supported(int N);
+int vi_jacobi_vectors(vi_ctx* c, int64_t B, int N, const void* d_log, int max_sweeps, const int* d_nround, double* d_V,
+                      int64_t log_stride = 0);
+
+// ---- K3p (vi_qr.hip): X1 = Q^T X Q, y1 = Q^T y by one column-pivoted Householder QR step; back-transformations c <- Q c ----
+bool vi_qr_supported(int N);
+size_t vi_qr_hh_bytes(int N);
+int vi_qr_precond(vi_ctx* c, int64_t B, int N, const double* d_X, const double* d_y, const int* d_rec, double* d_X1,
+                  double* d_y1, double* d_hh, double* d_scr, int64_t hh_stride = 0);
+int vi_qr_back_vec(vi_ctx* c, int64_t B, int N, const double* d_hh, double* d_C, int64_t hh_stride = 0);
+int vi_qr_back_mat(vi_ctx* c, int64_t B, int N, const double* d_hh, double* d_V, int64_t hh_stride = 0);
+
+// ---- vi_fit.hip ----
+double vi_floor_warm();                  // absolute rotation floor of the rotated-system solves
+
+// ---- evaluation on the matrix cores / in column groups (vi_eval_mfma.hip, vi_eval_split.hip, vi_eval_resident.hip) ----
+int vi_eval_sph_mfma(vi_model* m, int64_t Q, const double* lat, const double* lon, const double* alt, int64_t T,
+                     const double* Cp, const unsigned char* hull, int F, double* out, int64_t* done);
+int vi_eval_sph_split(vi_model* m, int64_t Q, const double* lat, const double* lon, const double* alt, int64_t T,
+                      const double* Cp, const unsigned char* hull, int F, double* out, int* handled);
+int vi_eval_resident_mfma(vi_ctx* c, int N, int64_t Q, int64_t T, const double* d_Y, const double* d_C, double* d_out, int* handled);
+int vi_eval_resident_err_mfma(vi_ctx* c, int N, int64_t Q, int64_t T, const double* d_Y, const double* d_dC, double* d_out,
+                              int* handled);
