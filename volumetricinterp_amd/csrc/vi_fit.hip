@@ -1113,7 +1113,7 @@ extern "C" int vi_reg_floor_f64(vi_ctx* c, int64_t T, int32_t N, const double* d
 }
 
 namespace {
-// pointer arrays of the two batched products of vi_basis_solve_f64
+// pointer arrays of the two batched products of the VINTERP_WALK_FORM=blas path of vi_basis_solve_f64
 __global__ void k_basis_ptrs(int64_t B, int NN, const double* AWA, const int* __restrict__ rec, const double* V,
                              const int* __restrict__ basis, double* T1, double* D1, const double** pA, const double** pV,
                              double** pT, double** pD)
@@ -1125,6 +1125,20 @@ __global__ void k_basis_ptrs(int64_t B, int NN, const double* AWA, const int* __
     pT[i] = T1 + i * NN;
     pD[i] = D1 + i * NN;
 }
+
+// How vi_basis_solve_f64 forms its rotated systems: K_walk (vi_walk.hip), or with VINTERP_WALK_FORM=blas the chain it
+// replaced - two batched rocBLAS products through HBM, k_vt_vec, k_form_pair_scaled - kept for A/B runs and as the fallback.
+bool walk_form_blas()
+{
+    static const bool v = vi_env_is("VINTERP_WALK_FORM", "blas");
+    return v;
+}
+// experiments and tests: at most this many systems per chunk of vi_basis_solve_f64 (0 = what the workspace budget gives)
+int walk_chunk_cap()
+{
+    static const int v = vi_env_int("VINTERP_WALK_CHUNK", 0);
+    return v;
+}
 }  // namespace
 
 // The bracket walk in SHARED bases.  The records of one geometry differ in their weights, not in their basis functions
@@ -1133,7 +1147,9 @@ __global__ void k_basis_ptrs(int64_t B, int NN, const double* AWA, const int* __
 // vi_warm_prepare_f64, which also gives D2_k = V_k^T R V_k) the system of every other record is nearly diagonal and
 // the Jacobi iteration needs 1-4 sweeps instead of 8 (alpha >= 1e-22) or 19-24 (below) - measured on the BASELINE
 // configs[2] geometry, tools/exp_shared_basis.py: 1349 -> 197 sweeps over 28 decades x 3 records.  For B (record, basis,
-// alpha) triples: D1 = V^T AWA V (two batched rocBLAS products, 8 N^3 flop), (D1 + alpha D2) c' = V^T y, C = V c'.
+// alpha) triples: D1 = V^T AWA V, (D1 + alpha D2) c' = V^T y, C = V c'.  K_walk forms the scaled system and V^T y in one
+// kernel on the fp64 matrix cores (4 N^3 flop, of which it leaves out the tiles above the block diagonal of D1, which K3
+// never reads), so a round is three launches: K_walk, K3, k_v_vec.
 // Any orthonormal V gives the same solution in exact arithmetic - a poor reference costs sweeps, not correctness.
 extern "C" int vi_basis_solve_f64(vi_ctx* c, int64_t B, int32_t N, const double* d_AWA, const double* d_y,
                                   const int32_t* d_rec, const int32_t* d_basis, const double* d_alpha, const double* d_V,
@@ -1148,39 +1164,49 @@ extern "C" int vi_basis_solve_f64(vi_ctx* c, int64_t B, int32_t N, const double*
     }
     VI_HIP(hipSetDevice(c->device));
     const int NN = N * N;
+    const bool blas = walk_form_blas();
     const size_t logb = vi_jacobi_log_bytes(N, JACOBI_MAX_SWEEPS);
-    const size_t per = logb + sizeof(double) + (size_t)2 * NN * sizeof(double) + (size_t)2 * N * sizeof(double) + 4 * sizeof(void*);
-    const int64_t Bc = chunk_size((size_t)8 << 30, per, B, 256);            // whole rounds of the 256 CUs
+    size_t per = logb + sizeof(double) + (size_t)NN * sizeof(double) + (size_t)2 * N * sizeof(double);
+    if (blas) per += (size_t)NN * sizeof(double) + 4 * sizeof(void*);
+    int64_t Bc = chunk_size((size_t)8 << 30, per, B, 256);            // whole rounds of the 256 CUs
+    if (walk_chunk_cap() > 0 && Bc > walk_chunk_cap()) Bc = walk_chunk_cap();
     void* log;
-    double *scl, *T1, *D1, *yt, *cp;
-    const double **pA, **pV;
-    double **pT, **pD;
+    double *scl, *T1 = nullptr, *X, *yt, *cp;
+    const double **pA = nullptr, **pV = nullptr;
+    double **pT = nullptr, **pD = nullptr;
     int rc = ws_carve(c, [&](ws_carver& w) {
         log = w.take<char>((size_t)Bc * logb);
         scl = w.take<double>(Bc);
-        T1 = w.take<double>((size_t)Bc * NN);
-        D1 = w.take<double>((size_t)Bc * NN);            // D1, then the scaled system in place
+        X = w.take<double>((size_t)Bc * NN);             // the scaled system (blas: D1 first, scaled in place)
         yt = w.take<double>((size_t)Bc * N);
         cp = w.take<double>((size_t)Bc * N);
-        pA = w.take<const double*>(Bc);
-        pV = w.take<const double*>(Bc);
-        pT = w.take<double*>(Bc);
-        pD = w.take<double*>(Bc);
+        if (blas) {
+            T1 = w.take<double>((size_t)Bc * NN);
+            pA = w.take<const double*>(Bc);
+            pV = w.take<const double*>(Bc);
+            pT = w.take<double*>(Bc);
+            pD = w.take<double*>(Bc);
+        }
     });
     if (rc != VI_OK) return rc;
     const double one = 1.0, zero = 0.0;
     return for_chunks(B, Bc, [&](int64_t i0, int64_t bc) -> int {
-        hipLaunchKernelGGL(k_basis_ptrs, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, c->stream, bc, NN, d_AWA,
-                           d_rec + i0, d_V, d_basis + i0, T1, D1, pA, pV, pT, pD);
-        VI_HIP(hipGetLastError());
-        VI_ROCBLAS(rocblas_dgemm_batched(c->blas, rocblas_operation_none, rocblas_operation_none, N, N, N, &one, pA, N,
-                                         pV, N, &zero, pT, N, (rocblas_int)bc));
-        VI_ROCBLAS(rocblas_dgemm_batched(c->blas, rocblas_operation_transpose, rocblas_operation_none, N, N, N, &one, pV, N,
-                                         (const double* const*)pT, N, &zero, pD, N, (rocblas_int)bc));
-        hipLaunchKernelGGL(k_vt_vec, dim3((unsigned)bc), dim3(256), 0, c->stream, N, d_V, d_basis + i0, d_y, d_rec + i0, yt);
-        form_pair_scaled(c, bc, NN, D1, d_D2, nullptr, d_basis + i0, d_alpha + i0, D1, scl);
-        VI_HIP(hipGetLastError());
-        const int r = vi_jacobi_solve(c, bc, N, D1, scl, yt, nullptr, rcond, cp, d_rank ? d_rank + i0 : nullptr, log,
+        if (blas) {
+            hipLaunchKernelGGL(k_basis_ptrs, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, c->stream, bc, NN, d_AWA,
+                               d_rec + i0, d_V, d_basis + i0, T1, X, pA, pV, pT, pD);
+            VI_HIP(hipGetLastError());
+            VI_ROCBLAS(rocblas_dgemm_batched(c->blas, rocblas_operation_none, rocblas_operation_none, N, N, N, &one, pA, N,
+                                             pV, N, &zero, pT, N, (rocblas_int)bc));
+            VI_ROCBLAS(rocblas_dgemm_batched(c->blas, rocblas_operation_transpose, rocblas_operation_none, N, N, N, &one, pV,
+                                             N, (const double* const*)pT, N, &zero, pD, N, (rocblas_int)bc));
+            hipLaunchKernelGGL(k_vt_vec, dim3((unsigned)bc), dim3(256), 0, c->stream, N, d_V, d_basis + i0, d_y, d_rec + i0, yt);
+            form_pair_scaled(c, bc, NN, X, d_D2, nullptr, d_basis + i0, d_alpha + i0, X, scl);
+            VI_HIP(hipGetLastError());
+        } else {
+            const int r = vi_walk_rotate(c, bc, N, d_AWA, d_rec + i0, d_V, d_D2, d_basis + i0, d_y, d_alpha + i0, X, scl, yt);
+            if (r != VI_OK) return r;
+        }
+        const int r = vi_jacobi_solve(c, bc, N, X, scl, yt, nullptr, rcond, cp, d_rank ? d_rank + i0 : nullptr, log,
                                       JACOBI_MAX_SWEEPS, d_sweeps ? d_sweeps + i0 : nullptr, nullptr, 0, nullptr,
                                       JACOBI_FLOOR_WARM, 0, walk_tolerance());
         if (r != VI_OK) return r;

@@ -25,6 +25,10 @@ int vi_qr_precond(vi_ctx* c, int64_t B, int N, const double* d_X, const double* 
 int vi_qr_back_vec(vi_ctx* c, int64_t B, int N, const double* d_hh, double* d_C, int64_t hh_stride = 0);
 int vi_qr_back_mat(vi_ctx* c, int64_t B, int N, const double* d_hh, double* d_V, int64_t hh_stride = 0);
 
+// ---- K_walk (vi_walk.hip): X = f (V AWA V^T + alpha D2), scl = 1 / f, yt = V y of the bracket walk in shared bases ----
+int vi_walk_rotate(vi_ctx* c, int64_t B, int N, const double* d_AWA, const int* d_rec, const double* d_V, const double* d_D2,
+                   const int* d_basis, const double* d_y, const double* d_alpha, double* d_X, double* d_scl, double* d_yt);
+
 // ---- vi_fit.hip ----
 double vi_floor_warm();                  // absolute rotation floor of the rotated-system solves
 
