@@ -21,7 +21,9 @@
 //    in a cache.  Workgroups go round-robin over the 8 XCDs (each with its own L2): block b runs on XCD b % 8, so the
 //    timestep tiles of one group of points get the block indices 8 apart - same XCD, launched together - and Y leaves HBM
 //    once per call, whatever the number of timesteps.
-// Bound: the fp64 matrix peak (78.6 TF): 2 N flop per point-timestep against 8 (N / T_call + 1) bytes.
+//  * Points outside the hull are NaN columns of Y.  The 32-byte pieces that hold nothing else are not multiplied: live list,
+//    see k_eval_resident below (VINTERP_K2R_LIVE=0: every piece is).
+// Bound: the fp64 matrix peak (78.6 TF): 2 N flop per point-timestep of the live pieces against 8 (N / T_call + 1) bytes.
 #include "vi_common.h"
 #include "vi_solver.h"
 
@@ -34,9 +36,98 @@ typedef double v4f64 __attribute__((ext_vector_type(4)));
 
 constexpr int RT = 4;        // row tiles (16 timesteps each) per wave
 constexpr int PF = 4;        // k-steps of B in flight
+constexpr int LIVE_BATCH = 32;                       // groups of 256 points per live list
+constexpr int LIVE_PIECES = LIVE_BATCH * 64;         // 32-byte pieces per live list (16-bit local indices)
 
-// PAD: 4 KSp > N, the last k-steps hold rows past the basis
+// coefficient tile in operand order: shA[(ks * RT + i) * 64 + (g * 16 + p)] = C[t0 + 16 i + p][4 ks + g]
+// (read along the coefficient rows - contiguous -, written to where the operand order wants them)
+__device__ __forceinline__ void stage_coeffs(double* shA, int tid, int N, int KSp, int64_t T, int64_t t0, const double* __restrict__ C)
+{
+    const int Np = 4 * KSp;
+    for (int e = tid; e < 16 * RT * Np; e += 256) {
+        const int tl = e / Np, n = e - tl * Np;
+        const int64_t t = t0 + tl;
+        shA[((n >> 2) * RT + (tl >> 4)) * 64 + ((n & 3) * 16 + (tl & 15))] = (t < T && n < N) ? C[t * N + n] : 0.0;
+    }
+}
+
+// 64 timesteps x 16 pieces of four points: lane (p, g) holds the piece at qa (valid: it exists; the others read the first
+// points of Y and store nothing)
 template <bool PAD>
+__device__ __forceinline__ void tile_product(const double* shA, int lane, int g, int N, int KS, int KSp, int64_t Q, int64_t T,
+                                             int64_t t0, int64_t qa, bool valid, const double* __restrict__ Y,
+                                             double* __restrict__ out)
+{
+    const double* yp = Y + (valid ? qa : 0);
+    v4f64 D[RT][4];
+#pragma unroll
+    for (int i = 0; i < RT; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) D[i][j] = (v4f64){0.0, 0.0, 0.0, 0.0};
+    // B in two named buffers of PF k-steps: while the MFMAs of one run, the loads of the next stage are in flight (written
+    // as a ring of registers replaced one by one, the compiler moved every load next to its use: no distance at all)
+    v4f64 yA[PF], yB[PF];
+    auto load_stage = [&](v4f64 (&y)[PF], int ks0) {
+#pragma unroll
+        for (int u = 0; u < PF; ++u) {
+            const int n = 4 * (ks0 + u) + g;
+            const bool in = ks0 + u < KS && n < N;
+            const v4f64 v = *reinterpret_cast<const v4f64*>(yp + (int64_t)(in ? n : 0) * Q);
+            // the rows from N on read row 0 and are set to zero: their zero coefficients times an infinite basis value
+            // would be NaN.  Without padding (N % 16 == 0, the default order) the kernel has no select at all: with one
+            // it measured 6 - 8 % slower at N = 144.
+            y[u] = (PAD && !in) ? (v4f64){0.0, 0.0, 0.0, 0.0} : v;
+        }
+    };
+    auto mfma_stage = [&](const v4f64 (&y)[PF], int ks0) {
+#pragma unroll
+        for (int u = 0; u < PF; ++u) {
+            double a[RT];
+#pragma unroll
+            for (int i = 0; i < RT; ++i) a[i] = shA[((ks0 + u) * RT + i) * 64 + lane];
+#pragma unroll
+            for (int i = 0; i < RT; ++i) {
+                D[i][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], y[u].x, D[i][0], 0, 0, 0);
+                D[i][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], y[u].y, D[i][1], 0, 0, 0);
+                D[i][2] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], y[u].z, D[i][2], 0, 0, 0);
+                D[i][3] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], y[u].w, D[i][3], 0, 0, 0);
+            }
+        }
+    };
+    load_stage(yA, 0);
+    int ks0 = 0;
+    for (; ks0 + PF < KSp; ks0 += 2 * PF) {
+        load_stage(yB, ks0 + PF);
+        asm volatile("" ::: "memory");
+        mfma_stage(yA, ks0);
+        if (ks0 + 2 * PF < KSp) load_stage(yA, ks0 + 2 * PF);
+        asm volatile("" ::: "memory");
+        mfma_stage(yB, ks0 + PF);
+    }
+    if (ks0 < KSp) mfma_stage(yA, ks0);
+    // D[i][j][v]: timestep t0 + 16 i + g + 4 v, point qa + j
+    if (valid) {
+#pragma unroll
+        for (int i = 0; i < RT; ++i)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                const int64_t t = t0 + 16 * i + g + 4 * v;
+                if (t < T)
+                    *reinterpret_cast<v4f64*>(out + t * Q + qa) = (v4f64){D[i][0][v], D[i][1][v], D[i][2][v], D[i][3][v]};
+            }
+    }
+}
+
+// PAD: 4 KSp > N, the last k-steps hold rows past the basis.
+// LIVE: the product runs over the 32-byte pieces (four consecutive points) that carry a point inside the hull.  A piece whose
+// four values of basis row 0 are all NaN gives NaN at every timestep whatever the coefficients are (the first product of the
+// chain is NaN): it is dead, gets its NaNs stored directly and costs neither matrix-core work nor reads of the other N - 1
+// rows.  Liveness is read from row 0 of THIS call's Y, per batch of LIVE_BATCH groups; the indices of the live pieces are
+// compacted into LDS in ascending order, and the waves take chunks of 16 of them round-robin where they took their 64 points of
+// a group.  Every other piece (all inside, or mixed) runs exactly the chain of the plain loop: same bits.  A dead piece holds the
+// bits the chain gives for the NaN that vi_eval_basis_f64 writes (0x7FF8000000000000); for a row-0 NaN of another payload or
+// sign in a caller's own Y the plain loop carries that NaN through and the list stores the canonical one - NaN either way.
+template <bool PAD, bool LIVE>
 __global__ __launch_bounds__(256, 2) void k_eval_resident(int N, int KSp, int64_t Q, int64_t T, int ntt, int groups, int64_t npg,
                                                           const double* __restrict__ Y, const double* __restrict__ C,
                                                           double* __restrict__ out)
@@ -49,82 +140,112 @@ __global__ __launch_bounds__(256, 2) void k_eval_resident(int N, int KSp, int64_
     const int xcd = (int)(bid & 7);
     const int64_t r = bid >> 3;
     const int tt = (int)(r % ntt);
-    const int64_t pg = (r / ntt) * 8 + xcd;
+    // (with the live list the eight groups of points of a row of blocks rotate over the XCDs from row to row: on a grid whose
+    // altitude-longitude planes are a multiple of eight groups - 256^3: eight groups per latitude - XCD k would otherwise
+    // always get the k-th eighth of the longitudes, the outer ones mostly outside the hull, the inner ones mostly inside:
+    // 1.24 times the mean live work on the busiest XCD of the bench grid, 1.002 rotated)
+    const int64_t row = r / ntt;
+    const int64_t pg = row * 8 + (LIVE ? (int)((xcd + row) & 7) : xcd);
     if (pg >= npg) return;
     const int64_t t0 = (int64_t)tt * (16 * RT);
-    // ---- coefficient tile in operand order: shA[(ks * RT + i) * 64 + (g * 16 + p)] = C[t0 + 16 i + p][4 ks + g]
-    // (read along the coefficient rows - contiguous -, written to where the operand order wants them)
-    const int Np = 4 * KSp;
-    for (int e = tid; e < 16 * RT * Np; e += 256) {
-        const int tl = e / Np, n = e - tl * Np;
-        const int64_t t = t0 + tl;
-        shA[((n >> 2) * RT + (tl >> 4)) * 64 + ((n & 3) * 16 + (tl & 15))] = (t < T && n < N) ? C[t * N + n] : 0.0;
-    }
-    __syncthreads();
     const int KS = (N + 3) >> 2;                              // k-steps that carry basis functions (the rest is padding)
-    for (int grp = 0; grp < groups; ++grp) {
-        const int64_t qa = (pg * groups + grp) * 256 + wave * 64 + 4 * p;      // this lane's four points
-        const bool valid = qa < Q;                                              // Q % 4 == 0: all four or none
-        if (__ballot(valid) == 0) break;
-        const double* yp = Y + (valid ? qa : 0);
-        v4f64 D[RT][4];
-#pragma unroll
-        for (int i = 0; i < RT; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) D[i][j] = (v4f64){0.0, 0.0, 0.0, 0.0};
-        // B in two named buffers of PF k-steps: while the MFMAs of one run, the loads of the next stage are in flight (written
-        // as a ring of registers replaced one by one, the compiler moved every load next to its use: no distance at all)
-        v4f64 yA[PF], yB[PF];
-        auto load_stage = [&](v4f64 (&y)[PF], int ks0) {
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                const int n = 4 * (ks0 + u) + g;
-                const bool in = ks0 + u < KS && n < N;
-                const v4f64 v = *reinterpret_cast<const v4f64*>(yp + (int64_t)(in ? n : 0) * Q);
-                // the rows from N on read row 0 and are set to zero: their zero coefficients times an infinite basis value
-                // would be NaN.  Without padding (N % 16 == 0, the default order) the kernel has no select at all: with one
-                // it measured 6 - 8 % slower at N = 144.
-                y[u] = (PAD && !in) ? (v4f64){0.0, 0.0, 0.0, 0.0} : v;
-            }
-        };
-        auto mfma_stage = [&](const v4f64 (&y)[PF], int ks0) {
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                double a[RT];
-#pragma unroll
-                for (int i = 0; i < RT; ++i) a[i] = shA[((ks0 + u) * RT + i) * 64 + lane];
-#pragma unroll
-                for (int i = 0; i < RT; ++i) {
-                    D[i][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], y[u].x, D[i][0], 0, 0, 0);
-                    D[i][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], y[u].y, D[i][1], 0, 0, 0);
-                    D[i][2] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], y[u].z, D[i][2], 0, 0, 0);
-                    D[i][3] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], y[u].w, D[i][3], 0, 0, 0);
-                }
-            }
-        };
-        load_stage(yA, 0);
-        int ks0 = 0;
-        for (; ks0 + PF < KSp; ks0 += 2 * PF) {
-            load_stage(yB, ks0 + PF);
-            asm volatile("" ::: "memory");
-            mfma_stage(yA, ks0);
-            if (ks0 + 2 * PF < KSp) load_stage(yA, ks0 + 2 * PF);
-            asm volatile("" ::: "memory");
-            mfma_stage(yB, ks0 + PF);
+    if constexpr (!LIVE) {
+        stage_coeffs(shA, tid, N, KSp, T, t0, C);
+        __syncthreads();
+        for (int grp = 0; grp < groups; ++grp) {
+            const int64_t qa = (pg * groups + grp) * 256 + wave * 64 + 4 * p;      // this lane's four points
+            const bool valid = qa < Q;                                              // Q % 4 == 0: all four or none
+            if (__ballot(valid) == 0) break;
+            tile_product<PAD>(shA, lane, g, N, KS, KSp, Q, T, t0, qa, valid, Y, out);
         }
-        if (ks0 < KSp) mfma_stage(yA, ks0);
-        // D[i][j][v]: timestep t0 + 16 i + g + 4 v, point qa + j
-        if (valid) {
+    } else {
+        __shared__ unsigned short shList[LIVE_PIECES];       // local indices of the live pieces of the batch, ascending
+        __shared__ int shCnt[4];                              // live pieces per wave's share of the batch
+        const int wv = __builtin_amdgcn_readfirstlane(wave);                       // uniform: the loops below are scalar
+        const int nt = (int)((T - t0) < 16 * RT ? (T - t0) : 16 * RT);             // timesteps of this tile
+        const v4f64 nan4 = {__builtin_nan(""), __builtin_nan(""), __builtin_nan(""), __builtin_nan("")};
+        bool staged = false;
+        for (int gb0 = 0; gb0 < groups; gb0 += LIVE_BATCH) {
+            const int64_t q0 = (pg * groups + gb0) * 256;                           // first point of the batch
+            if (q0 >= Q) break;
+            const int ng = groups - gb0 < LIVE_BATCH ? groups - gb0 : LIVE_BATCH;
+            const int64_t left = (Q - q0) >> 2;
+            const int np = left < (int64_t)ng * 64 ? (int)left : ng * 64;          // pieces of the batch (Q % 4 == 0)
+            // (the lane index behind an empty asm: nothing of the list phase is hoisted out of the batch loop and kept in
+            // registers across the product, which has none to spare)
+            int ln = lane;
+            asm volatile("" : "+v"(ln));
+            // ---- row 0 of the batch: wave w looks at the pieces [512 w, 512 w + 512), 64 per round
+            unsigned lv = 0, dd = 0;                                                // bit `it`: this lane's piece is live / dead
+            int cnt = 0;
 #pragma unroll
-            for (int i = 0; i < RT; ++i)
+            for (int it = 0; it < LIVE_PIECES / 256; ++it) {
+                const int pc = wv * (LIVE_PIECES / 4) + it * 64 + ln;
+                const bool ex = pc < np;
+                const v4f64 y = *reinterpret_cast<const v4f64*>(Y + q0 + 4 * (ex ? pc : 0));
+                const bool dead = y.x != y.x && y.y != y.y && y.z != y.z && y.w != y.w;
+                const bool live = ex && !dead;
+                lv |= (unsigned)live << it;
+                dd |= (unsigned)(ex && dead) << it;
+                cnt += __popcll(__ballot(live));
+            }
+            if (ln == 0) shCnt[wv] = cnt;
+            __syncthreads();
+            int base = 0, nlive = 0;
 #pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    const int64_t t = t0 + 16 * i + g + 4 * v;
-                    if (t < T)
-                        *reinterpret_cast<v4f64*>(out + t * Q + qa) = (v4f64){D[i][0][v], D[i][1][v], D[i][2][v], D[i][3][v]};
-                }
+            for (int w = 0; w < 4; ++w) {
+                const int c = shCnt[w];
+                base += w < wv ? c : 0;
+                nlive += c;
+            }
+#pragma unroll
+            for (int it = 0; it < LIVE_PIECES / 256; ++it) {
+                const bool live = (lv >> it) & 1;
+                const unsigned long long m = __ballot(live);
+                if (live) shList[base + __popcll(m & ((1ull << ln) - 1))] = (unsigned short)(wv * (LIVE_PIECES / 4) + it * 64 + ln);
+                base += __popcll(m);
+            }
+            __syncthreads();
+            // ---- dead pieces: NaN at the timesteps of this tile (the bits the product gives for a column of NaNs as
+            // k_mask_basis writes them; a row-0 NaN of another payload or sign in a caller's own Y gives this NaN too, where the
+            // plain loop carries the caller's through), by the wave that looked at them, before the product (measured: after
+            // it, or a round after each chunk, 4 % slower)
+            for (int it = 0; it < LIVE_PIECES / 256; ++it) {
+                const bool dead = (dd >> it) & 1;
+                if (__ballot(dead) == 0) continue;
+                double* o = out + t0 * Q + q0 + 4 * (wv * (LIVE_PIECES / 4) + it * 64 + ln);
+                if (dead)
+                    for (int tl = 0; tl < nt; ++tl) *reinterpret_cast<v4f64*>(o + (int64_t)tl * Q) = nan4;
+            }
+            if (nlive == 0) continue;
+            if (!staged) {                                                          // a workgroup without a live piece never needs it
+                int td = tid;
+                asm volatile("" : "+v"(td));                                     // as ln above
+                stage_coeffs(shA, td, N, KSp, T, t0, C);
+                __syncthreads();
+                staged = true;
+            }
+            // ---- live pieces: chunks of 16, the waves round-robin; lane (p, g) takes piece 16 chunk + p of the list
+            const int nchunks = (nlive + 15) >> 4;
+            for (int ch = wv; ch < nchunks; ch += 4) {
+                const int idx = 16 * ch + p;
+                const bool valid = idx < nlive;                                     // past the end of the list: no piece
+                const int64_t qa = q0 + 4 * (int64_t)shList[valid ? idx : 0];
+                // (the row group behind an empty asm, as ln above: the 16 row offsets t Q of the stores are formed per chunk,
+                // not kept across the product; & 3 tells the compiler that it is not negative - one select per load address)
+                int gc = g;
+                asm volatile("" : "+v"(gc));
+                gc &= 3;
+                tile_product<PAD>(shA, lane, gc, N, KS, KSp, Q, T, t0, qa, valid, Y, out);
+            }
         }
     }
+}
+
+bool use_live_list()
+{
+    static const bool plain = vi_env_is("VINTERP_K2R_LIVE", "0");
+    return !plain;
 }
 
 bool use_own_kernel()
@@ -154,14 +275,12 @@ int vi_eval_resident_mfma(vi_ctx* c, int N, int64_t Q, int64_t T, const double* 
     const int64_t nblk = ((npg + 7) / 8) * 8 * ntt;
     if (nblk > 0x7fffffffLL) return VI_OK;
     const bool pad = 4 * KSp > N;                                       // N % 16 != 0: rows past the basis
-    VI_HIP(hipFuncSetAttribute(pad ? (const void*)k_eval_resident<true> : (const void*)k_eval_resident<false>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    if (pad)
-        hipLaunchKernelGGL(k_eval_resident<true>, dim3((unsigned)nblk), dim3(256), shm, c->stream, N, KSp, Q, T, ntt, groups, npg,
-                           d_Y, d_C, d_out);
-    else
-        hipLaunchKernelGGL(k_eval_resident<false>, dim3((unsigned)nblk), dim3(256), shm, c->stream, N, KSp, Q, T, ntt, groups, npg,
-                           d_Y, d_C, d_out);
+    // VINTERP_K2R_LIVE=0: the plain loop over every point (the live list: 4 KB + counters of LDS next to the tile)
+    const bool live = use_live_list();
+    auto kern = pad ? (live ? k_eval_resident<true, true> : k_eval_resident<true, false>)
+                    : (live ? k_eval_resident<false, true> : k_eval_resident<false, false>);
+    VI_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(256), shm, c->stream, N, KSp, Q, T, ntt, groups, npg, d_Y, d_C, d_out);
     VI_HIP(hipGetLastError());
     *handled = 1;
     return VI_OK;
