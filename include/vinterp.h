@@ -121,7 +121,8 @@ void vi_model_destroy(vi_model* model);
 int  vi_basis_f64(vi_model* model, int64_t P, const double* d_lat, const double* d_lon,
                   const double* d_alt, double* d_A, int64_t ld_p, int64_t ld_n);
 /* gradient basis: replaces Model.grad_basis (sphharmlag.py:148-184; next row N1 - the reference never calls it).
- * G[p*ld_p + c*ld_c + n*ld_n], c = 0,1,2 = components along z, theta, phi.  sphharmlag only. */
+ * G[p*ld_p + c*ld_c + n*ld_n], c = 0,1,2 = components along z, theta, phi.  sphharmlag only, (MAXL, MAXK) within (6, 4),
+ * (12, 8) or (2, 12); other orders return VI_ERR_UNSUPPORTED (here and in vi_eval_grad_f64 / vi_eval_grad_basis_f64). */
 int  vi_grad_basis_f64(vi_model* model, int64_t P, const double* d_lat, const double* d_lon,
                        const double* d_alt, double* d_G, int64_t ld_p, int64_t ld_c, int64_t ld_n);
 /* gradient of the fitted parameter, out[q*3 + c] = sum_n grad_basis[q][c][n] * C[n] (c = z, theta, phi components as
@@ -154,10 +155,25 @@ int  vi_eval_f64(vi_model* model, int64_t Q, const double* d_lat, const double* 
  *                         entries of a point that fails the hull test (as in vi_eval_f64) are NaN
  *   vi_eval_resident_f64  out[t*Q + q] = sum_n d_Y[n*Q + q] * C[t*N + n]  - NaN outside the hull through the NaN of d_Y,
  *                         NaN for a timestep whose coefficients are NaN (a failed fit), as vi_eval_f64 gives them.
- * Agrees with vi_eval_f64 to rounding (the sum over n is taken in the library's order; tests/test_gpu_eval_resident.py). */
+ * Agrees with vi_eval_f64 to rounding (the sum over n is taken in the library's order; tests/test_gpu_eval_resident.py).
+ * vi_eval_resident_f64 multiplies ANY matrix of N rows and Q columns laid out like d_Y: with the gradient basis of
+ * vi_eval_grad_basis_f64 (below) and 3Q for Q it gives the gradient maps of the T timesteps, out[(t*3 + c)*Q + q].  The
+ * matrix-core kernel K2r takes the shapes with Q a multiple of 4, Q >= 256 and d_Y / d_out 32-byte aligned (for the gradient:
+ * 3Q >= 256 and the number of points a multiple of 4, which also keeps every component plane 32-byte aligned); other shapes,
+ * and VINTERP_EVAL_RESIDENT=blas, go through the library's product. */
 int  vi_eval_basis_f64(vi_model* model, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt,
                        const double* d_hull_eq, int32_t F, double hull_tol, double* d_Y);
 int  vi_eval_resident_f64(vi_model* model, int64_t Q, int64_t T, const double* d_Y, const double* d_C, double* d_out);
+/* Gradient maps of many timesteps on the same resident grid: the gradient is linear in the coefficients, so its basis is kept
+ * like d_Y and multiplied by the same call.
+ *   d_G[(n*3 + c)*Q + q]: component c of the gradient of basis function n at point q; N x 3Q doubles.
+ * c = z, theta, phi (VI_FRAME_MODEL, as vi_grad_basis_f64) or east, north, up (VI_FRAME_ENU: the local geodetic directions,
+ * `up` the ellipsoid's normal; the per-point rotation is folded into d_G, so the frame costs nothing per timestep).
+ * With hull_eq != NULL every entry of a point that fails the hull test (as in vi_eval_basis_f64) is NaN.  Orders and models as
+ * vi_grad_basis_f64; others return VI_ERR_UNSUPPORTED. */
+enum { VI_FRAME_MODEL = 0, VI_FRAME_ENU = 1 };
+int  vi_eval_grad_basis_f64(vi_model* model, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt,
+                            const double* d_hull_eq, int32_t F, double hull_tol, int32_t frame, double* d_G);
 /* Standard-error maps of many timesteps on the same resident grid (the `calcerr` output of estimate.py:139-145 for a batch of
  * covariances, e.g. the /Coeffs/dC of a whole fit):
  *   vi_eval_resident_err_f64  out[t*Q + q] = sqrt( sum_i sum_k d_Y[i*Q + q] * d_dC[t*N*N + i*N + k] * d_Y[k*Q + q] )

@@ -129,21 +129,69 @@ __global__ __launch_bounds__(BLOCK) void k_basis_sph(SphDev M, int64_t P, const 
 //   phat = e L0 Pmv dAz / (y (z/100+1) RE),
 // with L1 = eval_genlaguerre(k-1, 1, z), Pmv1 = lpmv(m, v+1, x).  Same chains as the basis, run one degree
 // further: when the chain has reached degree nu_l + 1, prev holds P at nu_l and cur at nu_l + 1.
-// CONTRACT = false: store the (P, 3, N) gradient basis.  CONTRACT = true: contract it on the fly with one coefficient
+// GRAD_STORE: store the gradient basis at the caller's strides.  GRAD_CONTRACT: contract it on the fly with one coefficient
 // vector Cv (N) and store only the three gradient components per point (ld_p = 3, ld_c = 1): the gradient of the fitted
-// parameter, never materialising 3N values per point.
-template <int LCAP, int KCAP, bool CONTRACT>
+// parameter, never materialising 3N values per point.  GRAD_RESIDENT: the store of GRAD_STORE for the matrix a resident grid
+// keeps (vi_eval_grad_basis_f64: planar strides, a lane is a point and every store of a wave is 64 consecutive doubles) with
+// the hull mask - a lane outside stores NaN into its 3N entries and a wave without a lane inside leaves before the chains -
+// and, with ENU, every (z, theta, phi) triple turned into east, north, up by the point's matrix (enu_frame) before the stores.
+enum { GRAD_STORE = 0, GRAD_CONTRACT = 1, GRAD_RESIDENT = 2 };
+
+// F[3 i + c] = (east, north, up)_i . (model direction z, theta, phi)_c at the point.  The local geodetic unit vectors are
+// rotated as sph_geom rotates the position (Rodrigues, +theta0) and meet the unit vectors of the rotated spherical coordinates
+// there: r' = (s c_phi, s s_phi, x), theta' = (x c_phi, x s_phi, -s), phi' = (-s_phi, c_phi, 0) with s = rho / r.  `up` is the
+// geodetic normal, not the radial direction.
+__device__ __forceinline__ void enu_frame(const SphDev& M, const Geom& g, double lat, double lon, double* F)
+{
+    double sl, cl, so, co;
+    sincos(lat * DEG2RAD, &sl, &cl);
+    sincos(lon * DEG2RAD, &so, &co);
+    const double enu[3][3] = {{-so, co, 0.0}, {-sl * co, -sl * so, cl}, {cl * co, cl * so, sl}};
+    const double st = sqrt(g.Rx * g.Rx + g.Ry * g.Ry) / (M.RE * (g.z / 100.0 + 1.0));
+    const double omc = 1.0 - M.rc;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const double vx = enu[i][0], vy = enu[i][1], vz = enu[i][2];
+        const double kd = M.kx * vx + M.ky * vy;
+        const double wx = vx * M.rc + (M.ky * vz) * M.rs + M.kx * kd * omc;
+        const double wy = vy * M.rc + (-M.kx * vz) * M.rs + M.ky * kd * omc;
+        const double wz = vz * M.rc + (M.kx * vy - M.ky * vx) * M.rs;
+        const double wh = wx * g.cphi + wy * g.sphi;            // component along the horizontal direction of azimuth phi'
+        F[3 * i] = st * wh + g.x * wz;
+        F[3 * i + 1] = g.x * wh - st * wz;
+        F[3 * i + 2] = wy * g.cphi - wx * g.sphi;
+    }
+}
+
+template <int LCAP, int KCAP, int MODE, bool ENU>
 __global__ __launch_bounds__(BLOCK) void k_grad_sph(SphDev M, int64_t P, const double* __restrict__ lat,
                                                     const double* __restrict__ lon, const double* __restrict__ alt,
-                                                    const double* __restrict__ Cv, double* __restrict__ Gout,
-                                                    int64_t ld_p, int64_t ld_c, int64_t ld_n)
+                                                    const double* __restrict__ Cv, const unsigned char* __restrict__ mask,
+                                                    double* __restrict__ Gout, int64_t ld_p, int64_t ld_c, int64_t ld_n)
 {
+    constexpr bool CONTRACT = MODE == GRAD_CONTRACT;
     double az = 0.0, at = 0.0, ap = 0.0;
     const int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     const int64_t pc = p < P ? p : P - 1;
-    const bool active = p < P;
-    const Geom g = sph_geom(M, lat[pc], lon[pc], alt[pc]);
+    bool active = p < P;
     double* Gp = Gout + pc * ld_p;
+    if (MODE == GRAD_RESIDENT && mask) {
+        const bool in = mask[pc] != 0;
+        if (active && !in) {
+            const double nan = __builtin_nan("");
+            for (int n = 0; n < M.N; ++n) {
+                double* o = Gp + (int64_t)n * ld_n;
+                o[0] = nan;
+                o[ld_c] = nan;
+                o[2 * ld_c] = nan;
+            }
+        }
+        active = active && in;
+        if (!__any(active)) return;           // whole wave outside the hull: skip the chains
+    }
+    const Geom g = sph_geom(M, lat[pc], lon[pc], alt[pc]);
+    double F[9];
+    if (ENU) enu_frame(M, g, lat[pc], lon[pc], F);
     const int maxl = M.maxl, maxk = M.maxk, L2 = maxl * maxl;
     double L0[KCAP], L1[KCAP];          // L_k(z) and L^(1)_{k-1}(z)
     laguerre<KCAP>(maxk, g.z, L0);
@@ -226,9 +274,16 @@ __global__ __launch_bounds__(BLOCK) void k_grad_sph(SphDev M, int64_t P, const d
                                     }
                                 } else if (k < maxk && active) {
                                     double* o = Gp + (int64_t)(k * L2 + r) * ld_n;
-                                    o[0] = tz * (L0[k] + 2.0 * L1[k]);
-                                    o[ld_c] = tt * L0[k];
-                                    o[2 * ld_c] = tp * L0[k];
+                                    const double gz = tz * (L0[k] + 2.0 * L1[k]), gt = tt * L0[k], gp = tp * L0[k];
+                                    if (ENU) {
+                                        o[0] = fma(F[0], gz, fma(F[1], gt, F[2] * gp));
+                                        o[ld_c] = fma(F[3], gz, fma(F[4], gt, F[5] * gp));
+                                        o[2 * ld_c] = fma(F[6], gz, fma(F[7], gt, F[8] * gp));
+                                    } else {
+                                        o[0] = gz;
+                                        o[ld_c] = gt;
+                                        o[2 * ld_c] = gp;
+                                    }
                                 }
                             }
                         }
@@ -1116,31 +1171,43 @@ extern "C" int vi_basis_f64(vi_model* m, int64_t P, const double* d_lat, const d
     return VI_OK;
 }
 
-extern "C" int vi_grad_basis_f64(vi_model* m, int64_t P, const double* d_lat, const double* d_lon, const double* d_alt,
-                                 double* d_G, int64_t ld_p, int64_t ld_c, int64_t ld_n)
+// The gradient kernel at the compiled order that holds the model's: (MAXL, MAXK) up to (6, 4), (12, 8) or (2, 12).
+namespace {
+template <int MODE, bool ENU>
+int launch_grad_sph(vi_model* m, const char* who, int64_t P, const double* d_lat, const double* d_lon, const double* d_alt,
+                    const double* d_C, const unsigned char* d_mask, double* d_G, int64_t ld_p, int64_t ld_c, int64_t ld_n)
 {
-    VI_REQUIRE(m && d_lat && d_lon && d_alt && d_G, "null argument");
-    VI_REQUIRE(P >= 0, "negative point count");
     if (m->kind != VI_MODEL_SPHHARMLAG || !m->sph.scale1 || !m->sph.nu) {
-        vi_set_error("vi_grad_basis_f64: only the sphharmlag model provides a gradient basis");
+        vi_set_error("%s: only the sphharmlag model provides a gradient basis", who);
         return VI_ERR_UNSUPPORTED;
     }
     if (P == 0) return VI_OK;
     VI_HIP(hipSetDevice(m->ctx->device));
     const int L = m->sph.maxl, K = m->sph.maxk;
     const dim3 grid(nblocks(P, BLOCK)), block(BLOCK);
-    if (L <= 6 && K <= 4)
-        hipLaunchKernelGGL((k_grad_sph<6, 4, false>), grid, block, 0, m->ctx->stream, m->sph, P, d_lat, d_lon, d_alt, nullptr,
-                           d_G, ld_p, ld_c, ld_n);
-    else if (L <= 12 && K <= 8)
-        hipLaunchKernelGGL((k_grad_sph<12, 8, false>), grid, block, 0, m->ctx->stream, m->sph, P, d_lat, d_lon, d_alt, nullptr,
-                           d_G, ld_p, ld_c, ld_n);
+#define VI_GRAD(LL, KK)                                                                                                    \
+    hipLaunchKernelGGL((k_grad_sph<LL, KK, MODE, ENU>), grid, block, 0, m->ctx->stream, m->sph, P, d_lat, d_lon, d_alt, d_C, \
+                       d_mask, d_G, ld_p, ld_c, ld_n)
+    if (L <= 6 && K <= 4) VI_GRAD(6, 4);
+    else if (L <= 12 && K <= 8) VI_GRAD(12, 8);
+    else if (L <= 2 && K <= 12) VI_GRAD(2, 12);
     else {
-        vi_set_error("vi_grad_basis_f64: order MAXL=%d MAXK=%d beyond the compiled limits (12, 8)", L, K);
+        vi_set_error("%s: order MAXL=%d MAXK=%d beyond the compiled limits (6, 4), (12, 8) and (2, 12)", who, L, K);
         return VI_ERR_UNSUPPORTED;
     }
+#undef VI_GRAD
     VI_HIP(hipGetLastError());
     return VI_OK;
+}
+}  // namespace
+
+extern "C" int vi_grad_basis_f64(vi_model* m, int64_t P, const double* d_lat, const double* d_lon, const double* d_alt,
+                                 double* d_G, int64_t ld_p, int64_t ld_c, int64_t ld_n)
+{
+    VI_REQUIRE(m && d_lat && d_lon && d_alt && d_G, "null argument");
+    VI_REQUIRE(P >= 0, "negative point count");
+    return launch_grad_sph<GRAD_STORE, false>(m, "vi_grad_basis_f64", P, d_lat, d_lon, d_alt, nullptr, nullptr, d_G, ld_p, ld_c,
+                                              ld_n);
 }
 
 // Gradient of the fitted parameter: out[q][c] = sum_n grad_basis[q][c][n] * C[n], c = z, theta, phi components
@@ -1150,26 +1217,7 @@ extern "C" int vi_eval_grad_f64(vi_model* m, int64_t Q, const double* d_lat, con
 {
     VI_REQUIRE(m && d_lat && d_lon && d_alt && d_C && d_out, "null argument");
     VI_REQUIRE(Q >= 0, "negative point count");
-    if (m->kind != VI_MODEL_SPHHARMLAG || !m->sph.scale1 || !m->sph.nu) {
-        vi_set_error("vi_eval_grad_f64: only the sphharmlag model provides a gradient basis");
-        return VI_ERR_UNSUPPORTED;
-    }
-    if (Q == 0) return VI_OK;
-    VI_HIP(hipSetDevice(m->ctx->device));
-    const int L = m->sph.maxl, K = m->sph.maxk;
-    const dim3 grid(nblocks(Q, BLOCK)), block(BLOCK);
-    if (L <= 6 && K <= 4)
-        hipLaunchKernelGGL((k_grad_sph<6, 4, true>), grid, block, 0, m->ctx->stream, m->sph, Q, d_lat, d_lon, d_alt, d_C, d_out,
-                           (int64_t)3, (int64_t)1, (int64_t)0);
-    else if (L <= 12 && K <= 8)
-        hipLaunchKernelGGL((k_grad_sph<12, 8, true>), grid, block, 0, m->ctx->stream, m->sph, Q, d_lat, d_lon, d_alt, d_C, d_out,
-                           (int64_t)3, (int64_t)1, (int64_t)0);
-    else {
-        vi_set_error("vi_eval_grad_f64: order MAXL=%d MAXK=%d beyond the compiled limits (12, 8)", L, K);
-        return VI_ERR_UNSUPPORTED;
-    }
-    VI_HIP(hipGetLastError());
-    return VI_OK;
+    return launch_grad_sph<GRAD_CONTRACT, false>(m, "vi_eval_grad_f64", Q, d_lat, d_lon, d_alt, d_C, nullptr, d_out, 3, 1, 0);
 }
 
 // Standard error of the fitted parameter from the coefficient covariance: err[q] = sqrt(a_q^T dC a_q), a_q = basis row
@@ -1280,15 +1328,11 @@ void launch_hull_mask(vi_model* m, int64_t Q, const double* d_lat, const double*
 }
 }  // namespace
 
-extern "C" int vi_eval_basis_f64(vi_model* m, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt,
-                                 const double* d_hull_eq, int32_t F, double hull_tol, double* d_Y)
+namespace {
+// m->d_mask[q] <- 1 where point q passes the hull test of the F facet equations, else 0 (grows the model's hull buffer and mask)
+int hull_pass(vi_model* m, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt, const double* d_hull_eq,
+              int32_t F, double hull_tol)
 {
-    VI_REQUIRE(m && d_lat && d_lon && d_alt && d_Y, "null argument");
-    VI_REQUIRE(Q >= 0 && F >= 0, "negative size");
-    VI_REQUIRE(F == 0 || d_hull_eq, "hull facet count given without facet equations");
-    if (Q == 0) return VI_OK;
-    int rc = vi_basis_f64(m, Q, d_lat, d_lon, d_alt, d_Y, 1, Q);
-    if (rc != VI_OK || F == 0) return rc;
     const size_t need = hull_buf_bytes((size_t)F);
     if (need > m->hull_bytes) {
         VI_HIP(hipStreamSynchronize(m->ctx->stream));
@@ -1309,9 +1353,49 @@ extern "C" int vi_eval_basis_f64(vi_model* m, int64_t Q, const double* d_lat, co
         m->mask_bytes = (size_t)Q;
     }
     launch_hull_mask(m, Q, d_lat, d_lon, d_alt, (int)F, hull_tol);
+    VI_HIP(hipGetLastError());
+    return VI_OK;
+}
+}  // namespace
+
+extern "C" int vi_eval_basis_f64(vi_model* m, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt,
+                                 const double* d_hull_eq, int32_t F, double hull_tol, double* d_Y)
+{
+    VI_REQUIRE(m && d_lat && d_lon && d_alt && d_Y, "null argument");
+    VI_REQUIRE(Q >= 0 && F >= 0, "negative size");
+    VI_REQUIRE(F == 0 || d_hull_eq, "hull facet count given without facet equations");
+    if (Q == 0) return VI_OK;
+    int rc = vi_basis_f64(m, Q, d_lat, d_lon, d_alt, d_Y, 1, Q);
+    if (rc != VI_OK || F == 0) return rc;
+    rc = hull_pass(m, Q, d_lat, d_lon, d_alt, d_hull_eq, F, hull_tol);
+    if (rc != VI_OK) return rc;
     hipLaunchKernelGGL(k_mask_basis, dim3(nblocks(Q, 256)), dim3(256), 0, m->ctx->stream, Q, m->N, m->d_mask, d_Y);
     VI_HIP(hipGetLastError());
     return VI_OK;
+}
+
+// The gradient basis of a resident grid: d_G[(n*3 + c)*Q + q], N x 3Q doubles, the matrix vi_eval_resident_f64 multiplies with
+// the coefficients of many timesteps (Q -> 3Q).  Planar so that every 32-byte piece of K2r holds one component of four
+// neighbouring points - dead exactly when the four are outside the hull - and every component of the product is a contiguous
+// map.  The hull pass runs first: the kernel stores the NaNs itself and skips the chains of a wave without a point inside.
+extern "C" int vi_eval_grad_basis_f64(vi_model* m, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt,
+                                      const double* d_hull_eq, int32_t F, double hull_tol, int32_t frame, double* d_G)
+{
+    VI_REQUIRE(m && d_lat && d_lon && d_alt && d_G, "null argument");
+    VI_REQUIRE(Q >= 0 && F >= 0, "negative size");
+    VI_REQUIRE(F == 0 || d_hull_eq, "hull facet count given without facet equations");
+    VI_REQUIRE(frame == VI_FRAME_MODEL || frame == VI_FRAME_ENU, "frame must be VI_FRAME_MODEL or VI_FRAME_ENU");
+    if (Q > 0 && F > 0 && m->kind == VI_MODEL_SPHHARMLAG) {          // (the launcher refuses the other model)
+        VI_HIP(hipSetDevice(m->ctx->device));
+        const int rc = hull_pass(m, Q, d_lat, d_lon, d_alt, d_hull_eq, F, hull_tol);
+        if (rc != VI_OK) return rc;
+    }
+    const unsigned char* d_mask = F > 0 ? m->d_mask : nullptr;
+    if (frame == VI_FRAME_ENU)
+        return launch_grad_sph<GRAD_RESIDENT, true>(m, "vi_eval_grad_basis_f64", Q, d_lat, d_lon, d_alt, nullptr, d_mask, d_G, 1,
+                                                    Q, 3 * Q);
+    return launch_grad_sph<GRAD_RESIDENT, false>(m, "vi_eval_grad_basis_f64", Q, d_lat, d_lon, d_alt, nullptr, d_mask, d_G, 1, Q,
+                                                 3 * Q);
 }
 
 extern "C" int vi_eval_resident_f64(vi_model* m, int64_t Q, int64_t T, const double* d_Y, const double* d_C, double* d_out)

@@ -57,6 +57,9 @@ def order_facets(eq, hull_vert, nsample=4096, nlead=32):
     return np.ascontiguousarray(eq[np.concatenate([np.array(lead, dtype=np.int64), rest])])
 
 
+GRADIENT_FRAMES = {'model': _lib.VI_FRAME_MODEL, 'enu': _lib.VI_FRAME_ENU}
+
+
 class Estimate(object):
     def __init__(self, coeff_filename, timetol=60., timeinterp=False, ctx=None):
         self.timetol = timetol
@@ -143,19 +146,27 @@ class Estimate(object):
                                              out.ctypes.data_as(P)), 'vi_eval_f64_host')
         return out
 
-    def resident_grid(self, gdlat, gdlon, gdalt, check_hull=True):
+    def resident_grid(self, gdlat, gdlon, gdalt, check_hull=True, gradient=None):
         """The points of a grid that MANY timesteps are going to be evaluated on (the reference calls Estimate.__call__ once
         per timestep and rebuilds the basis of the grid every time, estimate.py:110-115): their basis matrix is assembled once
         and stays in device memory (N x Q doubles - 19 GB at the default order on a 256^3 grid), and every batch of timesteps
-        is one matrix product (ResidentGrid.evaluate_coeffs / ResidentGrid.__call__).  Same values as __call__ to rounding."""
-        return ResidentGrid(self, gdlat, gdlon, gdalt, check_hull)
+        is one matrix product (ResidentGrid.evaluate_coeffs / ResidentGrid.__call__).  Same values as __call__ to rounding.
 
-    def gradient(self, time, gdlat, gdlon, gdalt, check_hull=True):
+        `gradient`: None (no gradient maps, nothing more allocated), 'model' or 'enu' - the grid also keeps its gradient basis
+        (N x 3 x Q doubles, three times the basis matrix: 57 GB of the 76 GB the two take at the default order on 256^3) and
+        ResidentGrid.gradient / evaluate_gradients give the gradient maps of many timesteps as one product, with components
+        along the model coordinates (z, theta, phi, as Estimate.gradient) or along local east, north, up."""
+        return ResidentGrid(self, gdlat, gdlon, gdalt, check_hull, gradient)
+
+    def gradient(self, time, gdlat, gdlon, gdalt, check_hull=True, frame='model'):
         """Gradient of the fitted parameter at the points: array of shape gdlat.shape + (3,), components along the
         model coordinates z, theta, phi exactly as ``Model.grad_basis`` defines them (sphharmlag.py:148-184), NaN outside
         the hull.  This is the output the reference's ``__call__`` advertises as ``calcgrad`` but never computes (the
         code after its ``return`` is dead, estimate.py:125-147); ``__call__`` itself keeps ignoring the flag,
-        as the reference does."""
+        as the reference does.  ``frame='enu'``: the same gradient along local east, north, up (the model-frame result
+        rotated on the host by ``Model.gradient_frame``)."""
+        if frame not in GRADIENT_FRAMES:
+            raise ValueError("frame must be 'model' or 'enu', not %r" % (frame,))
         C, dC = self.get_C(time)
         gdlat = np.asarray(gdlat, dtype=np.float64)
         lat = np.ascontiguousarray(gdlat.ravel())
@@ -182,6 +193,8 @@ class Estimate(object):
                     a.free()
             if check_hull:
                 out[~self.check_hull(lat, lon, alt)] = np.nan
+            if frame == 'enu':
+                out = np.einsum('pic,pc->pi', self.model.gradient_frame(lat, lon, alt), out)
         return out.reshape(gdlat.shape + (3,))
 
     def error(self, time, gdlat, gdlon, gdalt, check_hull=True):
@@ -247,8 +260,11 @@ class Estimate(object):
 class ResidentGrid(object):
     """Basis matrix of a fixed set of points, resident on the device (Estimate.resident_grid)."""
 
-    def __init__(self, est, gdlat, gdlon, gdalt, check_hull=True):
+    def __init__(self, est, gdlat, gdlon, gdalt, check_hull=True, gradient=None):
+        if gradient is not None and gradient not in GRADIENT_FRAMES:
+            raise ValueError("gradient must be None, 'model' or 'enu', not %r" % (gradient,))
         self.est = est
+        self.frame = gradient
         self.shape = np.asarray(gdlat).shape
         lat = np.ascontiguousarray(np.asarray(gdlat, dtype=np.float64).ravel())
         lon = np.ascontiguousarray(np.asarray(gdlon, dtype=np.float64).ravel())
@@ -259,13 +275,17 @@ class ResidentGrid(object):
         ctx = est.model.ctx
         N = est.model.nbasis
         free, _ = ctx.mem_info()
-        if self.Q * N * 8 > 0.9 * free:
-            raise MemoryError('basis matrix of %d points x %d functions (%.1f GB) does not fit the device (%.1f GB free)'
-                              % (self.Q, N, self.Q * N * 8 / 1e9, free / 1e9))
-        self.dY = None
+        nmat = 1 if gradient is None else 4             # the basis matrix, and three times as much for the gradient basis
+        if nmat * self.Q * N * 8 > 0.9 * free:
+            raise MemoryError('basis matrix%s of %d points x %d functions (%.1f GB) does not fit the device (%.1f GB free)'
+                              % ('' if gradient is None else ' and gradient basis', self.Q, N, nmat * self.Q * N * 8 / 1e9,
+                                 free / 1e9))
+        self.dY = self.dG = None
         tmp = []                        # device temporaries of the set-up: freed whatever happens below
         try:
             self.dY = ctx.empty((N, self.Q))
+            if gradient is not None:
+                self.dG = ctx.empty((N, 3, self.Q))
             if self.Q == 0:
                 return
             for a in (lat, lon, alt):
@@ -276,54 +296,99 @@ class ResidentGrid(object):
                 tmp.append(dh)
             else:
                 dh, F, tol = None, 0, 0.
-            _lib.check(_lib.lib.vi_eval_basis_f64(est.model.handle(), self.Q, tmp[0].ptr, tmp[1].ptr, tmp[2].ptr,
-                                                  dh.ptr if dh is not None else None, F, tol, self.dY.ptr), 'vi_eval_basis_f64')
+            hp = dh.ptr if dh is not None else None
+            if gradient is not None:    # first: the call that refuses a model or an order
+                _lib.check(_lib.lib.vi_eval_grad_basis_f64(est.model.handle(), self.Q, tmp[0].ptr, tmp[1].ptr, tmp[2].ptr, hp, F,
+                                                           tol, GRADIENT_FRAMES[gradient], self.dG.ptr), 'vi_eval_grad_basis_f64')
+            _lib.check(_lib.lib.vi_eval_basis_f64(est.model.handle(), self.Q, tmp[0].ptr, tmp[1].ptr, tmp[2].ptr, hp, F, tol,
+                                                  self.dY.ptr), 'vi_eval_basis_f64')
             ctx.sync()
         except BaseException:
-            self.close()                # the basis matrix (19 GB at the default order on 256^3) must not outlive a failed set-up
+            self.close()                # the matrices (19 + 57 GB at the default order on 256^3) must not outlive a failed set-up
             raise
         finally:
             for a in tmp:
                 a.free()
 
-    def evaluate_coeffs(self, C, out=None):
-        """out[t] = density of coefficient row C[t] on the grid; (T, Q) host array."""
+    def _slabs(self, C, out, width):
+        """The checks evaluate_coeffs and evaluate_gradients share: C as (T, N) float64, `out` or a new array of shape
+        (T,) + width, and the timesteps per slab whose output (8 bytes per element of `width`) fits a quarter of the free
+        device memory.  Returns (C, out, slab); slab 0: nothing to compute."""
         C = np.ascontiguousarray(C, dtype=np.float64)
         N = self.est.model.nbasis
         if C.ndim != 2 or C.shape[1] != N:
             raise ValueError('coefficients must have shape (T, %d)' % N)
         T = C.shape[0]
+        shape = (T,) + width
         if out is None:
-            out = np.empty((T, self.Q), dtype=np.float64)
-        elif out.shape != (T, self.Q) or out.dtype != np.float64 or not out.flags.c_contiguous:
-            raise ValueError('out must be a C-contiguous float64 array of shape (%d, %d)' % (T, self.Q))
+            out = np.empty(shape, dtype=np.float64)
+        elif out.shape != shape or out.dtype != np.float64 or not out.flags.c_contiguous:
+            raise ValueError('out must be a C-contiguous float64 array of shape (%s)' % ', '.join('%d' % n for n in shape))
         if T == 0 or self.Q == 0:
-            return out
+            return C, out, 0
+        free, _ = self.est.model.ctx.mem_info()
+        return C, out, int(max(1, min(T, (free // 4) // max(1, int(np.prod(width)) * 8))))
+
+    def _products(self, dM, cols, C, out, slab):
+        """out[t0:t0 + slab] = vi_eval_resident_f64 of the resident matrix dM (N rows, `cols` columns) with C, slab by slab."""
         ctx = self.est.model.ctx
-        # timesteps in slabs whose output fits a quarter of the free device memory
-        free, _ = ctx.mem_info()
-        slab = int(max(1, min(T, (free // 4) // max(1, self.Q * 8))))
-        if self.dY is None:
-            raise ValueError('this ResidentGrid has been closed')
+        N = self.est.model.nbasis
+        T = C.shape[0]
         dC = dO = None
         try:
             dC = ctx.to_device(C)
-            dO = ctx.empty((slab, self.Q))
+            dO = ctx.empty((slab, cols))
             for t0 in range(0, T, slab):
                 tc = min(slab, T - t0)
-                _lib.check(_lib.lib.vi_eval_resident_f64(self.est.model.handle(), self.Q, tc, self.dY.ptr, dC.offset_ptr(t0 * N),
+                _lib.check(_lib.lib.vi_eval_resident_f64(self.est.model.handle(), cols, tc, dM.ptr, dC.offset_ptr(t0 * N),
                                                          dO.ptr), 'vi_eval_resident_f64')
-                _lib.check(_lib.lib.vi_d2h(ctx.handle, out[t0:t0 + tc].ctypes.data_as(_lib.VOIDP), dO.ptr, tc * self.Q * 8), 'd2h')
+                _lib.check(_lib.lib.vi_d2h(ctx.handle, out[t0:t0 + tc].ctypes.data_as(_lib.VOIDP), dO.ptr, tc * cols * 8), 'd2h')
         finally:
             for a in (dC, dO):
                 if a is not None:
                     a.free()
         return out
 
+    def evaluate_coeffs(self, C, out=None):
+        """out[t] = density of coefficient row C[t] on the grid; (T, Q) host array."""
+        C, out, slab = self._slabs(C, out, (self.Q,))
+        if slab == 0:
+            return out
+        if self.dY is None:
+            raise ValueError('this ResidentGrid has been closed')
+        return self._products(self.dY, self.Q, C, out, slab)
+
+    def evaluate_gradients(self, C, out=None):
+        """out[t, c] = component c of the gradient of the parameter with coefficient row C[t] on the grid; (T, 3, Q) host
+        array, c in the grid's frame (see gradient).  The same product as evaluate_coeffs on the gradient basis: 3Q columns."""
+        self._need_gradient_basis()
+        C, out, slab = self._slabs(C, out, (3, self.Q))
+        if slab == 0:
+            return out
+        if self.dG is None:
+            raise ValueError('this ResidentGrid has been closed')
+        return self._products(self.dG, 3 * self.Q, C, out, slab)
+
     def __call__(self, times):
         """Densities at the grid for a list of datetimes (Estimate.get_C per time): array (len(times),) + grid shape."""
         C = np.array([np.asarray(self.est.get_C(t)[0], dtype=np.float64) for t in times])
         return self.evaluate_coeffs(C).reshape((len(times),) + tuple(self.shape))
+
+    def _need_gradient_basis(self):
+        if self.frame is None:
+            raise ValueError("this ResidentGrid holds no gradient basis: build it with resident_grid(..., gradient='model') "
+                             "or gradient='enu'")
+
+    def gradient(self, times):
+        """Gradient maps at the grid for a list of datetimes (coefficients of Estimate.get_C per time, as __call__ takes them):
+        array (len(times), 3) + grid shape.  The components follow the frame the grid was built with: (z, theta, phi) of the
+        model coordinates for gradient='model', (east, north, up) for gradient='enu'; np.moveaxis(x, 1, -1) gives the
+        trailing-3 convention of Estimate.gradient.  NaN outside the hull and for a timestep whose coefficients are NaN, as
+        the density; non-finite at the pole of the cap (sin theta' = 0), where the reference's formula divides by zero, as
+        Estimate.gradient is."""
+        self._need_gradient_basis()
+        C = np.array([np.asarray(self.est.get_C(t)[0], dtype=np.float64) for t in times]).reshape(len(times), self.est.model.nbasis)
+        return self.evaluate_gradients(C).reshape((len(times), 3) + tuple(self.shape))
 
     def evaluate_errors(self, dC, out=None):
         """out[t] = standard error sqrt(a^T dC[t] a) of the fitted parameter on the grid for each covariance dC[t] (as stored
@@ -374,11 +439,13 @@ class ResidentGrid(object):
         return self.evaluate_errors(dC).reshape((len(times),) + tuple(self.shape))
 
     def close(self):
-        """Give the basis matrix back to the device (idempotent).  Also runs on `with est.resident_grid(...) as g:` exit
+        """Give the basis matrix (and the gradient basis) back to the device (idempotent).  Also runs on `with est.resident_grid(...) as g:` exit
         and when the object is collected."""
-        dY, self.dY = getattr(self, 'dY', None), None
-        if dY is not None:
-            dY.free()
+        for name in ('dY', 'dG'):
+            a = getattr(self, name, None)
+            setattr(self, name, None)
+            if a is not None:
+                a.free()
 
     def __enter__(self):
         return self

@@ -218,6 +218,37 @@ class Model(DeviceModel):
                    'vi_grad_basis_f64')
         return dG.download()
 
+    def gradient_frame(self, gdlat, gdlon, gdalt):
+        """(P, 3, 3) matrices M with g_enu = M @ g_model: the components of a gradient along the model coordinates
+        (z, theta, phi of the rotated cap, as grad_basis gives them) turned into local east, north, up - `up` the geodetic
+        normal of the ellipsoid, not the radial direction.  M[i][c] is the dot product of the i-th geodetic unit vector with
+        the c-th unit vector of the rotated spherical coordinates taken back to ECEF by the transpose of the Rodrigues
+        matrix of transform_coord.  Pure NumPy; the device forms the same matrices in vi_eval_grad_basis_f64."""
+        lat = np.radians(np.asarray(gdlat, dtype=np.float64).ravel())
+        lon = np.radians(np.asarray(gdlon, dtype=np.float64).ravel())
+        theta0, kx, ky = self._rotation()
+        Kx = np.array([[0., 0., ky], [0., 0., -kx], [-ky, kx, 0.]])                      # k x .
+        k = np.array([kx, ky, 0.])
+        Rot = np.cos(theta0) * np.eye(3) + np.sin(theta0) * Kx + (1. - np.cos(theta0)) * np.outer(k, k)
+        R = Rot @ np.stack(geodetic2ecef(np.degrees(lat), np.degrees(lon), np.asarray(gdalt, dtype=np.float64).ravel()))
+        rho = np.hypot(R[0], R[1])
+        r = np.sqrt(R[0]**2 + R[1]**2 + R[2]**2)
+        pole = ~(rho > 0.)
+        with np.errstate(invalid='ignore', divide='ignore'):
+            cp = np.where(pole, 1., R[0] / rho)                                         # arctan2(0, 0) = 0
+            sp_ = np.where(pole, 0., R[1] / rho)
+        ct, st = R[2] / r, rho / r
+        zero = np.zeros_like(ct)
+        model = np.stack([np.stack([st * cp, st * sp_, ct]),                            # r', theta', phi' in the rotated frame
+                          np.stack([ct * cp, ct * sp_, -st]),
+                          np.stack([-sp_, cp, zero])])                                  # (c, xyz, P)
+        model = np.einsum('ji,cjp->cip', Rot, model)                                    # Rot^T: back to ECEF
+        sl, cl, so, co = np.sin(lat), np.cos(lat), np.sin(lon), np.cos(lon)
+        enu = np.stack([np.stack([-so, co, zero]),
+                        np.stack([-sl * co, -sl * so, cl]),
+                        np.stack([cl * co, cl * so, sl])])                              # (i, xyz, P)
+        return np.ascontiguousarray(np.einsum('ixp,cxp->pic', enu, model))
+
     # ---- regularisation matrices (host; SURVEY A12) -------------------------------------------
     def eval_omega(self):
         from ..regmat import eval_omega
