@@ -183,13 +183,42 @@ int  vi_eval_grad_basis_f64(vi_model* model, int64_t Q, const double* d_lat, con
  * K2e takes N <= 144 with Q even and d_Y / d_out 16-byte aligned; other shapes, and VINTERP_EVAL_RESIDENT=blas, go through
  * the library's product and a row dot, as vi_eval_err_f64 (tests/test_gpu_resident_error.py). */
 int  vi_eval_resident_err_f64(vi_model* model, int64_t Q, int64_t T, const double* d_Y, const double* d_dC, double* d_out);
+/* Column maps of many timesteps on the same resident grid, without the volume.  The grid is seen as (outer, L, inner), point
+ * q = (o*L + l)*inner + i, column m = o*inner + i: any axis of a C-ordered grid, the last one with inner = 1.  What a user of
+ * Estimate.__call__ (estimate.py:110-123) takes from a (lat, lon, alt) volume per column: the peak of the parameter along
+ * altitude and where it sits, and its vertical integral.
+ *   vi_eval_resident_peak_f64  d_val[t*M + m] = max (kind 0) or min (kind 1) over l of the density of vi_eval_resident_f64 at the
+ *                         points of column m that are not NaN, the bits of the selected element; d_idx[t*M + m] = the lowest l
+ *                         that attains it (+0 and -0 tie, +-inf are ordinary values): np.nanmax / the first np.nanargmax.  A
+ *                         column without a number - wholly outside the hull, or a timestep whose coefficients hold a NaN -
+ *                         gives (NaN, -1).
+ * d_work: vi_eval_resident_peak_work_bytes(model, outer, L, inner, T) bytes, host arithmetic for the path the call will take
+ * PROVIDED d_Y is 32-byte aligned and d_work 8-byte aligned (any hipMalloc pointer is): the size is computed from the shape
+ * alone, and a call whose shape is K2p's but whose pointers are not (or whose launch would exceed 2^31 - 1 blocks) takes the
+ * two-pass path, which needs T x Q doubles or at least Q, and fails with VI_ERR_ARG on a smaller work space.
+ * K2p, the matrix-core kernel, takes inner = 1 with L a multiple of 4 and K2r's shapes (Q a multiple of 4, Q >= 256, d_Y 32-byte
+ * aligned): K2r's product with a reduction in place of the stores, its work space holds partial results only (12 bytes per
+ * timestep and 64-point block or column, twice).  Other shapes, VINTERP_K2P=twopass and VINTERP_EVAL_RESIDENT=blas run
+ * vi_eval_resident_f64 into d_work, a slab of T x Q doubles or as many timesteps of it as work_bytes holds (at least one), and
+ * a column reduction over it.  Same bits either way, and whatever the cut of T into calls.  Asynchronous on the context's
+ * stream; timed for vi_eval_kernel_ms like its siblings.
+ *   vi_reduce_basis_f64   d_Yr[n*M + m] = sum_l d_w[l] * d_Y[n*Q + (o*L + l)*inner + i] over the l whose point is not NaN in
+ *                         ROW 0 of d_Y (K2r's rule for a point outside the hull), in ascending l; NaN where the column has no
+ *                         such point.  The weighted column sum of the density is linear in the coefficients:
+ *                         vi_eval_resident_f64(model, M, T, d_Yr, ...) gives sum_l w[l] * density[t][m][l] over the points inside
+ *                         the hull at 1/L of the cost of the density product (tests/test_gpu_resident_integrate.py). */
+int    vi_eval_resident_peak_f64(vi_model* model, int64_t outer, int64_t L, int64_t inner, int64_t T, const double* d_Y,
+                                 const double* d_C, int32_t kind, double* d_val, int32_t* d_idx, void* d_work, size_t work_bytes);
+size_t vi_eval_resident_peak_work_bytes(vi_model* model, int64_t outer, int64_t L, int64_t inner, int64_t T);
+int    vi_reduce_basis_f64(vi_model* model, int64_t outer, int64_t L, int64_t inner, const double* d_Y, const double* d_w,
+                           double* d_Yr);
 /* Arithmetic of the Legendre degree recurrences inside vi_eval_f64 for this model: 0 = fp64 (default; the reference
  * computes in float64 throughout, sphharmlag.py:118-145), 1 = fp32 chains with everything else in fp64 - the variant
  * BASELINE configs[4] sweeps against the 1e-6 tolerance.  Orders with an fp32 kernel: (MAXL, MAXK) = (6,4), (2,8), (12,8);
  * others return VI_ERR_UNSUPPORTED from vi_eval_f64 while the flag is set. */
 int  vi_model_set_eval_precision(vi_model* model, int32_t chain_f32);
-/* device time (ms) of the evaluation kernel launches of the last vi_eval_f64 / vi_eval_resident_f64 / vi_eval_resident_err_f64
- * call on this context, from HIP events recorded on the context's stream around them (the preparation kernels are excluded).
+/* device time (ms) of the evaluation kernel launches of the last vi_eval_f64 / vi_eval_resident_f64 / vi_eval_resident_err_f64 /
+ * vi_eval_resident_peak_f64 call on this context, from HIP events recorded on the context's stream around them (the preparation kernels are excluded).
  * The events are recorded only while vi_ctx_set_eval_timing(ctx, 1) is in force (default: off - the pair costs a 0.2 ms call about 7 us);
  * vi_eval_kernel_ms fails with VI_ERR_ARG while it is off or before a call has been timed. */
 int  vi_ctx_set_eval_timing(vi_ctx* ctx, int32_t on);

@@ -1398,25 +1398,20 @@ extern "C" int vi_eval_grad_basis_f64(vi_model* m, int64_t Q, const double* d_la
                                                  3 * Q);
 }
 
-extern "C" int vi_eval_resident_f64(vi_model* m, int64_t Q, int64_t T, const double* d_Y, const double* d_C, double* d_out)
+namespace {
+
+// the product of vi_eval_resident_f64 without its timer (vi_eval_resident_peak_f64 runs it per slab inside its own)
+int eval_resident(vi_model* m, int64_t Q, int64_t T, const double* d_Y, const double* d_C, double* d_out)
 {
-    VI_REQUIRE(m && d_Y && d_C && d_out, "null argument");
-    VI_REQUIRE(Q >= 0 && T >= 0, "negative size");
-    if (Q == 0 || T == 0) return VI_OK;
     vi_ctx* c = m->ctx;
-    VI_HIP(hipSetDevice(c->device));
     const int N = m->N;
-    {
-        EvalTimer timer(c);
-        int handled = 0;
-        const int rc = vi_eval_resident_mfma(c, N, Q, T, d_Y, d_C, d_out, &handled);      // K2r (vi_eval_resident.hip)
-        if (rc != VI_OK || handled) return rc;
-    }
+    int handled = 0;
+    const int rc = vi_eval_resident_mfma(c, N, Q, T, d_Y, d_C, d_out, &handled);      // K2r (vi_eval_resident.hip)
+    if (rc != VI_OK || handled) return rc;
     // shapes outside K2r's (Q not a multiple of 4, orders whose coefficient tile exceeds the LDS): the library's product
     const double one = 1.0, zero = 0.0;
     const int64_t TT = 128;                          // timesteps per product
     const int64_t QQ = (int64_t)1 << 30;             // points per product (the library's dimensions are 32-bit)
-    EvalTimer timer(c);
     for (int64_t t0 = 0; t0 < T; t0 += TT) {
         const int64_t tc = (T - t0) < TT ? (T - t0) : TT;
         for (int64_t q0 = 0; q0 < Q; q0 += QQ) {
@@ -1427,6 +1422,70 @@ extern "C" int vi_eval_resident_f64(vi_model* m, int64_t Q, int64_t T, const dou
         }
     }
     return VI_OK;
+}
+
+}  // namespace
+
+extern "C" int vi_eval_resident_f64(vi_model* m, int64_t Q, int64_t T, const double* d_Y, const double* d_C, double* d_out)
+{
+    VI_REQUIRE(m && d_Y && d_C && d_out, "null argument");
+    VI_REQUIRE(Q >= 0 && T >= 0, "negative size");
+    if (Q == 0 || T == 0) return VI_OK;
+    VI_HIP(hipSetDevice(m->ctx->device));
+    EvalTimer timer(m->ctx);
+    return eval_resident(m, Q, T, d_Y, d_C, d_out);
+}
+
+// Peak maps along one axis of a resident grid (include/vinterp.h).  K2p where the shape is its own; else, and with
+// VINTERP_K2P=twopass or VINTERP_EVAL_RESIDENT=blas: the density product of vi_eval_resident_f64 into d_work, a slab of as many
+// timesteps as it holds, and k_peak_columns over the slab.
+extern "C" size_t vi_eval_resident_peak_work_bytes(vi_model* m, int64_t outer, int64_t L, int64_t inner, int64_t T)
+{
+    if (!m || outer <= 0 || L <= 0 || inner <= 0 || T <= 0) return 0;
+    if (vi_peak_fused_shape(m->N, outer, L, inner)) return vi_peak_fused_work_bytes(outer, L, T);
+    return (size_t)T * (size_t)(outer * L * inner) * sizeof(double);
+}
+
+extern "C" int vi_eval_resident_peak_f64(vi_model* m, int64_t outer, int64_t L, int64_t inner, int64_t T, const double* d_Y,
+                                         const double* d_C, int32_t kind, double* d_val, int32_t* d_idx, void* d_work,
+                                         size_t work_bytes)
+{
+    VI_REQUIRE(m && d_Y && d_C && d_val && d_idx, "null argument");
+    VI_REQUIRE(outer >= 0 && L >= 0 && inner >= 0 && T >= 0, "negative size");
+    VI_REQUIRE(kind == 0 || kind == 1, "kind must be 0 (max) or 1 (min)");
+    VI_REQUIRE(L <= 0x7fffffffLL, "the reduced axis is longer than a 32-bit index");
+    const int64_t M = outer * inner, Q = M * L;
+    if (Q == 0 || T == 0) return VI_OK;
+    VI_REQUIRE(d_work, "null work space");
+    vi_ctx* c = m->ctx;
+    VI_HIP(hipSetDevice(c->device));
+    EvalTimer timer(c);
+    if (inner == 1) {
+        int handled = 0;
+        const int rc = vi_eval_resident_peak_mfma(c, m->N, outer, L, T, d_Y, d_C, kind, d_val, d_idx, d_work, work_bytes, &handled);
+        if (rc != VI_OK || handled) return rc;
+    }
+    const int64_t slab = (int64_t)(work_bytes / ((size_t)Q * sizeof(double)));
+    VI_REQUIRE(slab >= 1, "work space smaller than the density map of one timestep");
+    for (int64_t t0 = 0; t0 < T; t0 += slab) {
+        const int64_t tc = (T - t0) < slab ? (T - t0) : slab;
+        int rc = eval_resident(m, Q, tc, d_Y, d_C + t0 * m->N, (double*)d_work);
+        if (rc != VI_OK) return rc;
+        rc = vi_peak_columns(c, outer, L, inner, tc, kind, (const double*)d_work, d_val + t0 * M, d_idx + t0 * M);
+        if (rc != VI_OK) return rc;
+    }
+    return VI_OK;
+}
+
+// The reduced basis of a resident grid along one axis (include/vinterp.h): k_reduce_basis (vi_eval_resident.hip)
+extern "C" int vi_reduce_basis_f64(vi_model* m, int64_t outer, int64_t L, int64_t inner, const double* d_Y, const double* d_w,
+                                   double* d_Yr)
+{
+    VI_REQUIRE(m && d_Y && d_w && d_Yr, "null argument");
+    VI_REQUIRE(outer >= 0 && L >= 0 && inner >= 0, "negative size");
+    if (outer * inner == 0) return VI_OK;
+    VI_HIP(hipSetDevice(m->ctx->device));
+    return vi_reduce_basis(m->ctx, m->N, outer, L, inner, d_Y, d_w, d_Yr);
 }
 
 // Standard-error maps of many timesteps on the resident grid: out[t*Q + q] = sqrt(sum_ik Y[i][q] dC[t][i][k] Y[k][q]).  K2e

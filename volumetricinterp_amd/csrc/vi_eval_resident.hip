@@ -51,15 +51,12 @@ __device__ __forceinline__ void stage_coeffs(double* shA, int tid, int N, int KS
     }
 }
 
-// 64 timesteps x 16 pieces of four points: lane (p, g) holds the piece at qa (valid: it exists; the others read the first
-// points of Y and store nothing)
+// 64 timesteps x 16 pieces of four points, the MFMA chain K2r and K2p share: lane (p, g) holds the piece at yp (row 0 of Y at
+// its four points); on return D[i][j][v] is timestep t0 + 16 i + g + 4 v at point j of the piece
 template <bool PAD>
-__device__ __forceinline__ void tile_product(const double* shA, int lane, int g, int N, int KS, int KSp, int64_t Q, int64_t T,
-                                             int64_t t0, int64_t qa, bool valid, const double* __restrict__ Y,
-                                             double* __restrict__ out)
+__device__ __forceinline__ void tile_accumulate(const double* shA, int lane, int g, int N, int KS, int KSp, int64_t Q,
+                                                const double* __restrict__ yp, v4f64 (&D)[RT][4])
 {
-    const double* yp = Y + (valid ? qa : 0);
-    v4f64 D[RT][4];
 #pragma unroll
     for (int i = 0; i < RT; ++i)
 #pragma unroll
@@ -105,6 +102,16 @@ __device__ __forceinline__ void tile_product(const double* shA, int lane, int g,
         mfma_stage(yB, ks0 + PF);
     }
     if (ks0 < KSp) mfma_stage(yA, ks0);
+}
+
+// K2r's tile: lane (p, g) holds the piece at qa (valid: it exists; the others read the first points of Y and store nothing)
+template <bool PAD>
+__device__ __forceinline__ void tile_product(const double* shA, int lane, int g, int N, int KS, int KSp, int64_t Q, int64_t T,
+                                             int64_t t0, int64_t qa, bool valid, const double* __restrict__ Y,
+                                             double* __restrict__ out)
+{
+    v4f64 D[RT][4];
+    tile_accumulate<PAD>(shA, lane, g, N, KS, KSp, Q, Y + (valid ? qa : 0), D);
     // D[i][j][v]: timestep t0 + 16 i + g + 4 v, point qa + j
     if (valid) {
 #pragma unroll
@@ -254,7 +261,418 @@ bool use_own_kernel()
     return !blas;
 }
 
+
+// ---- K2p: peak maps along the last axis of the grid, K2r with the stores replaced by a reduction ------------------------------
+//
+//   val[t][m] = max (min) over the non-NaN l of out[t][m L + l],  idx[t][m] = the first l that attains it
+//
+// (np.nanmax / first np.nanargmax of the density map along altitude: NmF2 and hmF2 of a (lat, lon, alt) grid), from the same
+// stage_coeffs and the same MFMA chain as K2r - every product has K2r's bits - without a T x Q buffer.  L % 4 == 0: a 32-byte
+// piece never straddles two columns.
+//  * After the k-loop a lane holds four consecutive points x 16 timesteps.  Per timestep it reduces its four points in
+//    registers, ascending with a strict compare (the first occurrence wins; a NaN never does), then the 16 lanes p of its DPP row
+//    - 16 pieces ascending in q - run a segmented inclusive scan (row_shr 1, 2, 4, 8; no LDS), the lower lane winning a tie.
+//    Segments are runs of equal key = column + 64-point block of the grid: the last lane of a run holds its reduction.
+//  * Partials: one slot per (timestep, chunk parity, key).  Keys are unique per (column, block) because both grow along q
+//    (S = M + Q / 64 keys, rounded up).  The live pieces of a 64-point block are contiguous in the ascending live list and at most
+//    16: they fall into at most two consecutive chunks of 16, whose parities differ; batches begin on 256-point boundaries, so a
+//    block never straddles two lists.  Every slot therefore has ONE writer - no atomics, and the result does not depend on the
+//    order the workgroups run in or on how T is cut into calls.  A 0xFF memset marks every slot empty (a NaN, -1); dead pieces
+//    and all-NaN runs store nothing.  Without the list (VINTERP_K2R_LIVE=0) a wave's 64 points are one block: parity 0.
+//  * k_peak_finish folds the slots of a column (two per 64-point block it touches) with the total order "better value, or equal
+//    value and lower index", which does not depend on the folding order.
+// kind = min runs on the negated values (exact, and undone when the value is stored: the bits of the selected element).
+template <int CTRL>
+__device__ __forceinline__ int dpp_i32(int x)
+{
+    return __builtin_amdgcn_update_dpp(0, x, CTRL, 0xF, 0xF, false);
+}
+
+template <int CTRL>
+__device__ __forceinline__ double dpp_f64(double x)
+{
+    return __hiloint2double(dpp_i32<CTRL>(__double2hiint(x)), dpp_i32<CTRL>(__double2loint(x)));
+}
+
+// x takes the place of b: x is a number and b is none, or x is larger
+__device__ __forceinline__ bool peak_better(double x, double b) { return x == x && !(x <= b); }
+
+// ... or x equals b at a lower index (the total order of the cross-lane finish and of k_peak_finish)
+__device__ __forceinline__ bool peak_takes(double x, int xi, double b, int bi)
+{
+    return x == x && (!(x <= b) || (x == b && xi < bi));
+}
+
+constexpr int ROW_SHR = 0x110, ROW_SHL = 0x100;              // DPP controls: lane p reads lane p - n / p + n of its row of 16
+
+template <int OFF>
+__device__ __forceinline__ void peak_scan_step(bool same, double& b, int& bi)
+{
+    const double pb = dpp_f64<ROW_SHR + OFF>(b);
+    const int pi = dpp_i32<ROW_SHR + OFF>(bi);
+    if (same && !peak_better(b, pb)) {                          // the lower lane keeps a tie
+        b = pb;
+        bi = pi;
+    }
+}
+
+// all 64 lanes call this together (DPP reads neighbours): lane (p, g) holds the piece at qa in D, valid: it exists
+__device__ __forceinline__ void peak_epilogue(const v4f64 (&D)[RT][4], int p, int g, int64_t qa, bool valid, int par, int64_t L,
+                                              bool neg, int64_t S, int64_t T, int64_t t0, double* __restrict__ pval,
+                                              int* __restrict__ pidx)
+{
+    const int64_t col = qa / L;
+    const int l0 = (int)(qa - col * L);                        // position of the piece in its column
+    const int key = valid ? (int)(col + (qa >> 6)) : -1;      // (the lanes past the end of the list: runs of their own, never stored)
+    // (every DPP read before its condition: behind `p >= 1 &&` it would run with the lanes it reads from switched off)
+    const int k1 = dpp_i32<ROW_SHR + 1>(key), k2 = dpp_i32<ROW_SHR + 2>(key), k4 = dpp_i32<ROW_SHR + 4>(key);
+    const int k8 = dpp_i32<ROW_SHR + 8>(key), kn = dpp_i32<ROW_SHL + 1>(key);
+    const bool s1 = p >= 1 && k1 == key, s2 = p >= 2 && k2 == key, s4 = p >= 4 && k4 == key, s8 = p >= 8 && k8 == key;
+    const bool last = valid && (p == 15 || kn != key);
+#pragma unroll
+    for (int i = 0; i < RT; ++i)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            double b = neg ? -D[i][0][v] : D[i][0][v];
+            int bi = l0;
+#pragma unroll
+            for (int j = 1; j < 4; ++j) {
+                const double x = neg ? -D[i][j][v] : D[i][j][v];
+                if (peak_better(x, b)) {
+                    b = x;
+                    bi = l0 + j;
+                }
+            }
+            peak_scan_step<1>(s1, b, bi);
+            peak_scan_step<2>(s2, b, bi);
+            peak_scan_step<4>(s4, b, bi);
+            peak_scan_step<8>(s8, b, bi);
+            const int64_t t = t0 + 16 * i + g + 4 * v;
+            if (last && t < T && b == b) {
+                const int64_t s = (t * 2 + par) * S + key;
+                pval[s] = neg ? -b : b;
+                pidx[s] = bi;
+            }
+        }
+}
+
+// the decode, the list and the walk of k_eval_resident (see there); the list is built by a copy of K2r's code, not by a shared
+// function: with the scan in a function of its own the compiler emits another K2r
+template <bool PAD, bool LIVE>
+__global__ __launch_bounds__(256, 2) void k_eval_resident_peak(int N, int KSp, int64_t Q, int64_t T, int ntt, int groups,
+                                                               int64_t npg, const double* __restrict__ Y,
+                                                               const double* __restrict__ C, int64_t L, int neg, int64_t S,
+                                                               double* __restrict__ pval, int* __restrict__ pidx)
+{
+    extern __shared__ __align__(16) double shA[];            // [KSp][RT][64]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int p = lane & 15, g = lane >> 4;
+    const int64_t bid = blockIdx.x;
+    const int xcd = (int)(bid & 7);
+    const int64_t r = bid >> 3;
+    const int tt = (int)(r % ntt);
+    const int64_t row = r / ntt;
+    const int64_t pg = row * 8 + (LIVE ? (int)((xcd + row) & 7) : xcd);
+    if (pg >= npg) return;
+    const int64_t t0 = (int64_t)tt * (16 * RT);
+    const int KS = (N + 3) >> 2;
+    if constexpr (!LIVE) {
+        stage_coeffs(shA, tid, N, KSp, T, t0, C);
+        __syncthreads();
+        for (int grp = 0; grp < groups; ++grp) {
+            const int64_t qa = (pg * groups + grp) * 256 + wave * 64 + 4 * p;
+            const bool valid = qa < Q;
+            if (__ballot(valid) == 0) break;
+            v4f64 D[RT][4];
+            tile_accumulate<PAD>(shA, lane, g, N, KS, KSp, Q, Y + (valid ? qa : 0), D);
+            peak_epilogue(D, p, g, qa, valid, 0, L, neg != 0, S, T, t0, pval, pidx);
+        }
+    } else {
+        __shared__ unsigned short shList[LIVE_PIECES];
+        __shared__ int shCnt[4];
+        const int wv = __builtin_amdgcn_readfirstlane(wave);
+        bool staged = false;
+        for (int gb0 = 0; gb0 < groups; gb0 += LIVE_BATCH) {
+            const int64_t q0 = (pg * groups + gb0) * 256;
+            if (q0 >= Q) break;
+            const int ng = groups - gb0 < LIVE_BATCH ? groups - gb0 : LIVE_BATCH;
+            const int64_t left = (Q - q0) >> 2;
+            const int np = left < (int64_t)ng * 64 ? (int)left : ng * 64;
+            int ln = lane;
+            asm volatile("" : "+v"(ln));
+            unsigned lv = 0;
+            int cnt = 0;
+#pragma unroll
+            for (int it = 0; it < LIVE_PIECES / 256; ++it) {
+                const int pc = wv * (LIVE_PIECES / 4) + it * 64 + ln;
+                const bool ex = pc < np;
+                const v4f64 y = *reinterpret_cast<const v4f64*>(Y + q0 + 4 * (ex ? pc : 0));
+                const bool dead = y.x != y.x && y.y != y.y && y.z != y.z && y.w != y.w;
+                const bool live = ex && !dead;
+                lv |= (unsigned)live << it;
+                cnt += __popcll(__ballot(live));
+            }
+            if (ln == 0) shCnt[wv] = cnt;
+            __syncthreads();
+            int base = 0, nlive = 0;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                const int c = shCnt[w];
+                base += w < wv ? c : 0;
+                nlive += c;
+            }
+#pragma unroll
+            for (int it = 0; it < LIVE_PIECES / 256; ++it) {
+                const bool live = (lv >> it) & 1;
+                const unsigned long long m = __ballot(live);
+                if (live) shList[base + __popcll(m & ((1ull << ln) - 1))] = (unsigned short)(wv * (LIVE_PIECES / 4) + it * 64 + ln);
+                base += __popcll(m);
+            }
+            __syncthreads();
+            if (nlive == 0) continue;                                               // dead pieces store nothing: their slots stay empty
+            if (!staged) {
+                int td = tid;
+                asm volatile("" : "+v"(td));
+                stage_coeffs(shA, td, N, KSp, T, t0, C);
+                __syncthreads();
+                staged = true;
+            }
+            const int nchunks = (nlive + 15) >> 4;
+            for (int ch = wv; ch < nchunks; ch += 4) {
+                const int idx = 16 * ch + p;
+                const bool valid = idx < nlive;
+                const int64_t qa = q0 + 4 * (int64_t)shList[valid ? idx : 0];
+                int gc = g;
+                asm volatile("" : "+v"(gc));
+                gc &= 3;
+                v4f64 D[RT][4];
+                tile_accumulate<PAD>(shA, lane, gc, N, KS, KSp, Q, Y + (valid ? qa : 0), D);
+                peak_epilogue(D, p, gc, qa, valid, ch & 1, L, neg != 0, S, T, t0, pval, pidx);
+            }
+        }
+    }
+}
+
+// val[t][m], idx[t][m] from the slots of column m: the blocks (m L) >> 6 .. ((m + 1) L - 1) >> 6, both parities
+__global__ __launch_bounds__(256) void k_peak_finish(int64_t M, int64_t L, int64_t T, int neg, int64_t S,
+                                                     const double* __restrict__ pval, const int* __restrict__ pidx,
+                                                     double* __restrict__ val, int* __restrict__ idx)
+{
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < T * M; e += stride) {
+        const int64_t t = e / M, m = e - t * M;
+        const int64_t b0 = (m * L) >> 6, b1 = ((m + 1) * L - 1) >> 6;
+        double bx = __builtin_nan(""), bv = __builtin_nan("");
+        int bi = -1;
+        for (int64_t b = b0; b <= b1; ++b)
+            for (int par = 0; par < 2; ++par) {
+                const int64_t s = (t * 2 + par) * S + m + b;
+                const double v = pval[s];
+                const double x = neg ? -v : v;
+                const int i = pidx[s];
+                if (peak_takes(x, i, bx, bi)) {
+                    bx = x;
+                    bv = v;
+                    bi = i;
+                }
+            }
+        val[e] = bv;
+        idx[e] = bi;
+    }
+}
+
+// ---- the two-pass path: columns of a (T, outer, L, inner) slab of densities ---------------------------------------------------
+// inner > 1: one thread per column, neighbouring threads neighbouring i - every load of a wave is contiguous
+__global__ __launch_bounds__(256) void k_peak_columns(int64_t outer, int64_t L, int64_t inner, int64_t T, int neg,
+                                                      const double* __restrict__ in, double* __restrict__ val,
+                                                      int* __restrict__ idx)
+{
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x, M = outer * inner;
+    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < T * M; e += stride) {
+        const int64_t tm = e / inner, i = e - tm * inner;          // tm = t * outer + o
+        const double* src = in + tm * L * inner + i;
+        double bx = __builtin_nan(""), bv = __builtin_nan("");
+        int bi = -1;
+        for (int64_t l = 0; l < L; ++l) {
+            const double v = src[l * inner];
+            const double x = neg ? -v : v;
+            if (peak_better(x, bx)) {
+                bx = x;
+                bv = v;
+                bi = (int)l;
+            }
+        }
+        val[e] = bv;
+        idx[e] = bi;
+    }
+}
+
+// inner == 1: W lanes (a power of two, at most a wave) per column, lane s at l = s, s + W, ... - contiguous loads -, then a
+// butterfly over the W lanes with the total order of peak_takes.  ncol = T * M columns of L contiguous values.
+__global__ __launch_bounds__(256) void k_peak_columns_last(int64_t ncol, int64_t L, int W, int neg, const double* __restrict__ in,
+                                                           double* __restrict__ val, int* __restrict__ idx)
+{
+    const int64_t gt = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    const int sub = (int)(gt & (W - 1));
+    const int64_t grp = gt / W, ngrp = (int64_t)gridDim.x * blockDim.x / W;
+    for (int64_t c0 = 0; c0 < ncol; c0 += ngrp) {                  // the same trip count in every lane: the shuffles below
+        const int64_t c = c0 + grp;
+        double bx = __builtin_nan(""), bv = __builtin_nan("");
+        int bi = -1;
+        if (c < ncol) {
+            const double* src = in + c * L;
+            for (int64_t l = sub; l < L; l += W) {
+                const double v = src[l];
+                const double x = neg ? -v : v;
+                if (peak_better(x, bx)) {
+                    bx = x;
+                    bv = v;
+                    bi = (int)l;
+                }
+            }
+        }
+        for (int off = 1; off < W; off <<= 1) {
+            const double ox = __shfl_xor(bx, off), ov = __shfl_xor(bv, off);
+            const int oi = __shfl_xor(bi, off);
+            if (peak_takes(ox, oi, bx, bi)) {
+                bx = ox;
+                bv = ov;
+                bi = oi;
+            }
+        }
+        if (sub == 0 && c < ncol) {
+            val[c] = bv;
+            idx[c] = bi;
+        }
+    }
+}
+
+// Yr[n][m] = sum_l w[l] Y[n][(o L + l) inner + i] over the l whose point has a number in ROW 0 of Y (K2r's liveness rule:
+// vi_eval_basis_f64 makes every row of a point outside the hull NaN), sequentially in ascending l; NaN for a column without
+// such a point.  One thread per (n, m), neighbouring threads neighbouring columns.
+__global__ __launch_bounds__(256) void k_reduce_basis(int N, int64_t outer, int64_t L, int64_t inner, const double* __restrict__ Y,
+                                                      const double* __restrict__ w, double* __restrict__ Yr)
+{
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x, M = outer * inner, Q = M * L;
+    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < N * M; e += stride) {
+        const int64_t n = e / M, m = e - n * M;
+        const int64_t o = m / inner, i = m - o * inner;
+        const double* y0 = Y + o * L * inner + i;
+        const double* yn = y0 + n * Q;
+        double acc = 0.0;
+        bool any = false;
+        for (int64_t l = 0; l < L; ++l) {
+            const double r0 = y0[l * inner];
+            if (r0 == r0) {
+                acc += w[l] * yn[l * inner];
+                any = true;
+            }
+        }
+        Yr[e] = any ? acc : __builtin_nan("");
+    }
+}
+
+unsigned reduce_blocks(int64_t threads)
+{
+    const int64_t b = (threads + 255) / 256;
+    return (unsigned)(b < 1 ? 1 : (b > (1 << 20) ? (1 << 20) : b));
+}
+
+bool use_fused_peak()
+{
+    static const bool twopass = vi_env_is("VINTERP_K2P", "twopass");
+    return !twopass;
+}
+
+// points per workgroup of K2r and K2p: 256 x groups
+int k2r_groups(int64_t Q)
+{
+    int groups = (int)((Q >> 16) < 1 ? 1 : ((Q >> 16) > 32 ? 32 : (Q >> 16)));
+    if (const char* e = getenv("VINTERP_K2R_GROUPS")) { const int g = atoi(e); if (g >= 1 && g <= 256) groups = g; }      // experiments
+    return groups;
+}
+
 }  // namespace
+
+// K2p takes the reduced axis last (inner == 1) with L % 4 == 0 and K2r's own shapes (Q % 4 == 0, Q >= 256, the coefficient
+// tile within the LDS); 32-bit keys and indices.  Host arithmetic only: what vi_eval_resident_peak_work_bytes rests on.
+bool vi_peak_fused_shape(int N, int64_t outer, int64_t L, int64_t inner)
+{
+    if (!use_own_kernel() || !use_fused_peak()) return false;
+    const int64_t Q = outer * L * inner;
+    const int KSp = (((N + 3) / 4 + PF - 1) / PF) * PF;
+    const size_t shm = (size_t)KSp * RT * 64 * sizeof(double);
+    return inner == 1 && (L & 3) == 0 && (Q & 3) == 0 && Q >= 256 && shm <= 150 * 1024 && outer + (Q + 63) / 64 < 0x7fffffffLL;
+}
+
+// slots of the partials per timestep and parity, and the bytes of T timesteps: values, then indices
+int64_t vi_peak_fused_slots(int64_t outer, int64_t L) { return outer + (outer * L + 63) / 64; }
+
+size_t vi_peak_fused_work_bytes(int64_t outer, int64_t L, int64_t T)
+{
+    return (size_t)T * 2 * (size_t)vi_peak_fused_slots(outer, L) * (sizeof(double) + sizeof(int32_t));
+}
+
+// val / idx (T, outer) by K2p; *handled = 0 when the call is not the kernel's after all (alignment of d_Y, too many blocks): the
+// caller then runs the two-pass path
+int vi_eval_resident_peak_mfma(vi_ctx* c, int N, int64_t outer, int64_t L, int64_t T, const double* d_Y, const double* d_C, int kind,
+                               double* d_val, int32_t* d_idx, void* d_work, size_t work_bytes, int* handled)
+{
+    *handled = 0;
+    const int64_t Q = outer * L;
+    if (!vi_peak_fused_shape(N, outer, L, 1) || ((uintptr_t)d_Y & 31) != 0 || ((uintptr_t)d_work & 7) != 0) return VI_OK;
+    const size_t need = vi_peak_fused_work_bytes(outer, L, T);
+    if (work_bytes < need) return VI_OK;
+    const int KSp = (((N + 3) / 4 + PF - 1) / PF) * PF;
+    const size_t shm = (size_t)KSp * RT * 64 * sizeof(double);
+    const int ntt = (int)((T + 16 * RT - 1) / (16 * RT));
+    const int groups = k2r_groups(Q);
+    const int64_t npg = (Q + (int64_t)256 * groups - 1) / ((int64_t)256 * groups);
+    const int64_t nblk = ((npg + 7) / 8) * 8 * ntt;
+    if (nblk > 0x7fffffffLL) return VI_OK;
+    const int64_t S = vi_peak_fused_slots(outer, L);
+    double* pval = (double*)d_work;
+    int* pidx = (int*)(pval + (size_t)T * 2 * S);
+    VI_HIP(hipMemsetAsync(d_work, 0xFF, need, c->stream));               // every slot empty: (a NaN, -1)
+    const bool pad = 4 * KSp > N;
+    const bool live = use_live_list();
+    auto kern = pad ? (live ? k_eval_resident_peak<true, true> : k_eval_resident_peak<true, false>)
+                    : (live ? k_eval_resident_peak<false, true> : k_eval_resident_peak<false, false>);
+    VI_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(256), shm, c->stream, N, KSp, Q, T, ntt, groups, npg, d_Y, d_C, L,
+                       kind, S, pval, pidx);
+    VI_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_peak_finish, dim3(reduce_blocks(T * outer)), dim3(256), 0, c->stream, outer, L, T, kind, S, pval, pidx,
+                       d_val, d_idx);
+    VI_HIP(hipGetLastError());
+    *handled = 1;
+    return VI_OK;
+}
+
+// val / idx (T, outer * inner) of a slab of densities (T, outer, L, inner): k_peak_columns / k_peak_columns_last
+int vi_peak_columns(vi_ctx* c, int64_t outer, int64_t L, int64_t inner, int64_t T, int kind, const double* d_in, double* d_val,
+                    int32_t* d_idx)
+{
+    if (inner == 1) {
+        int W = 1;
+        while (W < 64 && W < L) W <<= 1;
+        hipLaunchKernelGGL(k_peak_columns_last, dim3(reduce_blocks(T * outer * W)), dim3(256), 0, c->stream, T * outer, L, W, kind,
+                           d_in, d_val, d_idx);
+    } else {
+        hipLaunchKernelGGL(k_peak_columns, dim3(reduce_blocks(T * outer * inner)), dim3(256), 0, c->stream, outer, L, inner, T,
+                           kind, d_in, d_val, d_idx);
+    }
+    VI_HIP(hipGetLastError());
+    return VI_OK;
+}
+
+int vi_reduce_basis(vi_ctx* c, int N, int64_t outer, int64_t L, int64_t inner, const double* d_Y, const double* d_w, double* d_Yr)
+{
+    hipLaunchKernelGGL(k_reduce_basis, dim3(reduce_blocks((int64_t)N * outer * inner)), dim3(256), 0, c->stream, N, outer, L, inner,
+                       d_Y, d_w, d_Yr);
+    VI_HIP(hipGetLastError());
+    return VI_OK;
+}
 
 // out[t*Q + q] = sum_n Y[n*Q + q] C[t*N + n] by K2r; *handled = 0 when the shape is not the kernel's (the caller then uses the
 // library): Q a multiple of 4 and the matrices 32-byte aligned (the 32-byte pieces), the coefficient tile within the LDS.
@@ -269,8 +687,7 @@ int vi_eval_resident_mfma(vi_ctx* c, int N, int64_t Q, int64_t T, const double* 
     // points per workgroup: 256 x groups - the coefficient tile (73 KB through L2) is set up once per workgroup
     // (measured, T = 256: 128^3 points 52 TF with 4 groups, 57 with 32; 256^3 the same from 16 up: as many as leave every CU
     // a few workgroups)
-    int groups = (int)((Q >> 16) < 1 ? 1 : ((Q >> 16) > 32 ? 32 : (Q >> 16)));
-    if (const char* e = getenv("VINTERP_K2R_GROUPS")) { const int g = atoi(e); if (g >= 1 && g <= 256) groups = g; }      // experiments
+    const int groups = k2r_groups(Q);
     const int64_t npg = (Q + (int64_t)256 * groups - 1) / ((int64_t)256 * groups);
     const int64_t nblk = ((npg + 7) / 8) * 8 * ntt;
     if (nblk > 0x7fffffffLL) return VI_OK;

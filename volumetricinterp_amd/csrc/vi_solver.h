@@ -40,3 +40,11 @@ int vi_eval_sph_split(vi_model* m, int64_t Q, const double* lat, const double* l
 int vi_eval_resident_mfma(vi_ctx* c, int N, int64_t Q, int64_t T, const double* d_Y, const double* d_C, double* d_out, int* handled);
 int vi_eval_resident_err_mfma(vi_ctx* c, int N, int64_t Q, int64_t T, const double* d_Y, const double* d_dC, double* d_out,
                               int* handled);
+// peak maps and reduced bases of a resident grid seen as (outer, L, inner) (vi_eval_resident.hip)
+bool vi_peak_fused_shape(int N, int64_t outer, int64_t L, int64_t inner);
+size_t vi_peak_fused_work_bytes(int64_t outer, int64_t L, int64_t T);
+int vi_eval_resident_peak_mfma(vi_ctx* c, int N, int64_t outer, int64_t L, int64_t T, const double* d_Y, const double* d_C, int kind,
+                               double* d_val, int32_t* d_idx, void* d_work, size_t work_bytes, int* handled);
+int vi_peak_columns(vi_ctx* c, int64_t outer, int64_t L, int64_t inner, int64_t T, int kind, const double* d_in, double* d_val,
+                    int32_t* d_idx);
+int vi_reduce_basis(vi_ctx* c, int N, int64_t outer, int64_t L, int64_t inner, const double* d_Y, const double* d_w, double* d_Yr);

@@ -58,6 +58,8 @@ def order_facets(eq, hull_vert, nsample=4096, nlead=32):
 
 
 GRADIENT_FRAMES = {'model': _lib.VI_FRAME_MODEL, 'enu': _lib.VI_FRAME_ENU}
+PEAK_KINDS = {'max': 0, 'min': 1}                 # vi_eval_resident_peak_f64's kind
+REDUCED_BASES = 8                                  # reduced bases a ResidentGrid keeps (evaluate_integrals), oldest out
 
 
 class Estimate(object):
@@ -281,6 +283,7 @@ class ResidentGrid(object):
                               % ('' if gradient is None else ' and gradient basis', self.Q, N, nmat * self.Q * N * 8 / 1e9,
                                  free / 1e9))
         self.dY = self.dG = None
+        self._reduced = {}              # (axis, weight bytes) -> reduced basis on the device (evaluate_integrals)
         tmp = []                        # device temporaries of the set-up: freed whatever happens below
         try:
             self.dY = ctx.empty((N, self.Q))
@@ -438,14 +441,166 @@ class ResidentGrid(object):
             dC[k] = self.est.get_C(t)[1]
         return self.evaluate_errors(dC).reshape((len(times),) + tuple(self.shape))
 
+    def _columns(self, axis):
+        """The grid as (outer, L, inner) about `axis`: point q = (o * L + l) * inner + i, column m = o * inner + i."""
+        nd = len(self.shape)
+        if nd == 0:
+            raise ValueError('a 0-d grid has no axis to reduce')
+        if not isinstance(axis, (int, np.integer)) or isinstance(axis, bool) or not -nd <= axis < nd:
+            raise ValueError('axis must be an integer in [%d, %d), not %r' % (-nd, nd, axis))
+        axis = int(axis) % nd
+        outer = int(np.prod(self.shape[:axis], dtype=np.int64))
+        inner = int(np.prod(self.shape[axis + 1:], dtype=np.int64))
+        return axis, outer, int(self.shape[axis]), inner
+
+    def evaluate_peaks(self, C, axis=-1, kind='max', out=None):
+        """(value, index) of the peak of the density of coefficient row C[t] along `axis` of the grid, column by column:
+        value (T, M) float64 and index (T, M) int32, M = Q / L columns in C order of the remaining axes - np.nanmax
+        (kind='min': np.nanmin) of evaluate_coeffs(C) and the first position that attains it, (NaN, -1) for a column without
+        a number (outside the hull, or NaN coefficients).  Computed on the device from the resident basis; the volume is
+        not copied to the host and, with the reduced axis last, not formed.  `out`: a pair of preallocated arrays."""
+        axis, outer, L, inner = self._columns(axis)
+        if kind not in PEAK_KINDS:
+            raise ValueError("kind must be 'max' or 'min', not %r" % (kind,))
+        M = outer * inner
+        C = np.ascontiguousarray(C, dtype=np.float64)
+        N = self.est.model.nbasis
+        if C.ndim != 2 or C.shape[1] != N:
+            raise ValueError('coefficients must have shape (T, %d)' % N)
+        T = C.shape[0]
+        if out is None:
+            val, idx = np.empty((T, M), dtype=np.float64), np.empty((T, M), dtype=np.int32)
+        else:
+            try:
+                val, idx = out
+            except (TypeError, ValueError):
+                raise ValueError('out must be a pair (value, index) of arrays')
+            for a, dtype in ((val, np.float64), (idx, np.int32)):
+                if not isinstance(a, np.ndarray) or a.shape != (T, M) or a.dtype != dtype or not a.flags.c_contiguous:
+                    raise ValueError('out must be C-contiguous arrays of shape (%d, %d): value float64, index int32' % (T, M))
+        if T == 0 or self.Q == 0:
+            val.fill(np.nan)                # (columns of length zero: nothing to select)
+            idx.fill(-1)
+            return val, idx
+        if self.dY is None:
+            raise ValueError('this ResidentGrid has been closed')
+        ctx = self.est.model.ctx
+        h = self.est.model.handle()
+        work = lambda tc: int(_lib.lib.vi_eval_resident_peak_work_bytes(h, outer, L, inner, tc))
+        # timesteps in slabs whose work space and maps fit a quarter of the free device memory
+        free, _ = ctx.mem_info()
+        slab = int(max(1, min(T, (free // 4) // max(1, work(1) + M * 12))))
+        bufs = []
+        try:
+            dC = ctx.to_device(C)
+            bufs.append(dC)
+            dW = ctx.empty(work(slab), np.uint8)
+            bufs.append(dW)
+            dV, dI = ctx.empty((slab, M)), ctx.empty((slab, M), np.int32)
+            bufs += [dV, dI]
+            for t0 in range(0, T, slab):
+                tc = min(slab, T - t0)
+                _lib.check(_lib.lib.vi_eval_resident_peak_f64(h, outer, L, inner, tc, self.dY.ptr, dC.offset_ptr(t0 * N),
+                                                              PEAK_KINDS[kind], dV.ptr, dI.ptr, dW.ptr, dW.nbytes),
+                           'vi_eval_resident_peak_f64')
+                _lib.check(_lib.lib.vi_d2h(ctx.handle, val[t0:t0 + tc].ctypes.data_as(_lib.VOIDP), dV.ptr, tc * M * 8), 'd2h')
+                _lib.check(_lib.lib.vi_d2h(ctx.handle, idx[t0:t0 + tc].ctypes.data_as(_lib.VOIDP), dI.ptr, tc * M * 4), 'd2h')
+        finally:
+            for a in bufs:
+                a.free()
+        return val, idx
+
+    def peak(self, times, axis=-1, kind='max'):
+        """Peak maps for a list of datetimes (coefficients of Estimate.get_C per time, as __call__ takes them): (value, index),
+        each (len(times),) + the grid shape without `axis`.  On a (lat, lon, alt) grid with the default axis: the peak of the
+        parameter along altitude and the altitude index where it sits."""
+        axis, _, _, _ = self._columns(axis)
+        C = np.array([np.asarray(self.est.get_C(t)[0], dtype=np.float64) for t in times]).reshape(len(times),
+                                                                                                 self.est.model.nbasis)
+        val, idx = self.evaluate_peaks(C, axis=axis, kind=kind)
+        rest = (len(times),) + tuple(self.shape[:axis]) + tuple(self.shape[axis + 1:])
+        return val.reshape(rest), idx.reshape(rest)
+
+    @staticmethod
+    def _weights(L, weights):
+        if weights is None:
+            return np.ones(L)
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.ndim != 1 or w.shape[0] != L:
+            raise ValueError('weights must be a 1-D array of the length of the axis (%d)' % L)
+        if not np.isfinite(w).all():
+            raise ValueError('weights must be finite')
+        return w
+
+    def _reduced_basis(self, axis, outer, L, inner, w):
+        """The device matrix Yr (N, M) of vi_reduce_basis_f64 for (axis, weights), built once and kept until close()."""
+        key = (axis, w.tobytes())
+        dYr = self._reduced.get(key)
+        if dYr is None:
+            ctx = self.est.model.ctx
+            dw = None
+            while len(self._reduced) >= REDUCED_BASES:          # the oldest entry goes: weights that change with every call
+                self._reduced.pop(next(iter(self._reduced))).free()
+            nbytes = self.est.model.nbasis * outer * inner * 8
+            free, _ = ctx.mem_info()
+            if nbytes > 0.9 * free:
+                raise MemoryError('reduced basis of %d columns x %d functions (%.1f GB) does not fit the device (%.1f GB free)'
+                                  % (outer * inner, self.est.model.nbasis, nbytes / 1e9, free / 1e9))
+            dYr = ctx.empty((self.est.model.nbasis, outer * inner))
+            try:
+                dw = ctx.to_device(w)
+                _lib.check(_lib.lib.vi_reduce_basis_f64(self.est.model.handle(), outer, L, inner, self.dY.ptr, dw.ptr, dYr.ptr),
+                           'vi_reduce_basis_f64')
+                ctx.sync()
+            except BaseException:
+                dYr.free()
+                raise
+            finally:
+                if dw is not None:
+                    dw.free()
+            self._reduced[key] = dYr
+        return dYr
+
+    def evaluate_integrals(self, C, weights=None, axis=-1, out=None):
+        """out[t, m] = sum_l weights[l] * density[t, m, l] over the points of column m along `axis` that are inside the hull;
+        (T, M) host array, M as in evaluate_peaks.  weights: length of the axis, default ones (trapezoid weights in metres
+        give a vertical integral).  NaN for a column without a point inside and for a timestep with NaN coefficients.  The
+        sum is linear in the coefficients: the basis is summed along the axis once per (axis, weights) - a matrix 1 / L of
+        the basis, kept on the device until close(), the last REDUCED_BASES of them - and every call is the density product on M points.  "Inside" is read
+        from row 0 of the basis, as the density product reads it."""
+        axis, outer, L, inner = self._columns(axis)
+        w = self._weights(L, weights)
+        M = outer * inner
+        C, out, slab = self._slabs(C, out, (M,))
+        if slab == 0:
+            out.fill(np.nan)                # (columns of length zero: no point inside)
+            return out
+        if self.dY is None:
+            raise ValueError('this ResidentGrid has been closed')
+        return self._products(self._reduced_basis(axis, outer, L, inner, w), M, C, out, slab)
+
+    def integrate(self, times, weights=None, axis=-1):
+        """Weighted column sums for a list of datetimes (coefficients of Estimate.get_C per time): (len(times),) + the grid
+        shape without `axis`; see evaluate_integrals."""
+        axis, _, _, _ = self._columns(axis)
+        C = np.array([np.asarray(self.est.get_C(t)[0], dtype=np.float64) for t in times]).reshape(len(times),
+                                                                                                 self.est.model.nbasis)
+        rest = (len(times),) + tuple(self.shape[:axis]) + tuple(self.shape[axis + 1:])
+        return self.evaluate_integrals(C, weights=weights, axis=axis).reshape(rest)
+
     def close(self):
-        """Give the basis matrix (and the gradient basis) back to the device (idempotent).  Also runs on `with est.resident_grid(...) as g:` exit
-        and when the object is collected."""
+        """Give the basis matrix (the gradient basis, the reduced bases of evaluate_integrals) back to the device (idempotent).  Also runs
+        on `with est.resident_grid(...) as g:` exit and when the object is collected."""
         for name in ('dY', 'dG'):
             a = getattr(self, name, None)
             setattr(self, name, None)
             if a is not None:
                 a.free()
+        red = getattr(self, '_reduced', None)
+        if red:
+            for a in red.values():
+                a.free()
+            red.clear()
 
     def __enter__(self):
         return self
