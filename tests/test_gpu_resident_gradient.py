@@ -264,6 +264,7 @@ def test_gradient_maps_api_edges(monkeypatch):
             g.evaluate_gradients(bad)
     assert g.evaluate_gradients(C[:0]).shape == (0, 3, Q)
     assert g.gradient([]).shape == (0, 3, 4, 4, 4)
+    assert g([]).shape == (0, 4, 4, 4)                  # no times: the empty map, as every other map of the grid gives it
     g.close()
     assert g.dY is None and g.dG is None
     with pytest.raises(ValueError, match='closed'):

@@ -356,8 +356,8 @@ __device__ __forceinline__ void peak_epilogue(const v4f64 (&D)[RT][4], int p, in
         }
 }
 
-// the decode, the list and the walk of k_eval_resident (see there); the list is built by a copy of K2r's code, not by a shared
-// function: with the scan in a function of its own the compiler emits another K2r
+// the decode, the list and the walk of k_eval_resident (see there), launched with its geometry (k2r_plan); the list is built by
+// a copy of K2r's code, not by a shared function: with the scan in a function of its own the compiler emits another K2r
 template <bool PAD, bool LIVE>
 __global__ __launch_bounds__(256, 2) void k_eval_resident_peak(int N, int KSp, int64_t Q, int64_t T, int ntt, int groups,
                                                                int64_t npg, const double* __restrict__ Y,
@@ -584,13 +584,31 @@ bool use_fused_peak()
     return !twopass;
 }
 
-// points per workgroup of K2r and K2p: 256 x groups
-int k2r_groups(int64_t Q)
-{
-    int groups = (int)((Q >> 16) < 1 ? 1 : ((Q >> 16) > 32 ? 32 : (Q >> 16)));
-    if (const char* e = getenv("VINTERP_K2R_GROUPS")) { const int g = atoi(e); if (g >= 1 && g <= 256) groups = g; }      // experiments
-    return groups;
-}
+// The launch of K2r and of K2p for N functions, Q points, T timesteps: K2p's one-writer argument needs K2r's geometry exactly.
+// The environment has a say: `groups` (VINTERP_K2R_GROUPS, read at every construction), `live` (VINTERP_K2R_LIVE, once per process).
+struct k2r_plan {
+    int KSp, ntt, groups;       // k-steps with padding; timestep tiles; points per workgroup: 256 x groups
+    size_t shm;                 // the coefficient tile in LDS
+    int64_t npg, nblk;          // groups of points; workgroups: the groups rounded up to the 8 XCDs, times the timestep tiles
+    bool pad, live;             // the kernel's template arguments
+    bool fits;                  // the shape is the kernel's: the 32-byte pieces, two workgroups per CU, a 32-bit grid
+
+    k2r_plan(int N, int64_t Q, int64_t T)
+    {
+        KSp = (((N + 3) / 4 + PF - 1) / PF) * PF;
+        shm = (size_t)KSp * RT * 64 * sizeof(double);
+        ntt = (int)((T + 16 * RT - 1) / (16 * RT));
+        // the coefficient tile (73 KB through L2) is set up once per workgroup (measured, T = 256: 128^3 points 52 TF with 4
+        // groups, 57 with 32; 256^3 the same from 16 up: as many as leave every CU a few workgroups)
+        groups = (int)((Q >> 16) < 1 ? 1 : ((Q >> 16) > 32 ? 32 : (Q >> 16)));
+        if (const char* e = getenv("VINTERP_K2R_GROUPS")) { const int g = atoi(e); if (g >= 1 && g <= 256) groups = g; }  // experiments
+        npg = (Q + (int64_t)256 * groups - 1) / ((int64_t)256 * groups);
+        nblk = ((npg + 7) / 8) * 8 * ntt;
+        pad = 4 * KSp > N;                                       // N % 16 != 0: rows past the basis
+        live = use_live_list();     // VINTERP_K2R_LIVE=0: the plain loop over every point (the list: 4 KB + counters of LDS)
+        fits = (Q & 3) == 0 && Q >= 256 && shm <= 150 * 1024 && nblk <= 0x7fffffffLL;
+    }
+};
 
 }  // namespace
 
@@ -600,9 +618,8 @@ bool vi_peak_fused_shape(int N, int64_t outer, int64_t L, int64_t inner)
 {
     if (!use_own_kernel() || !use_fused_peak()) return false;
     const int64_t Q = outer * L * inner;
-    const int KSp = (((N + 3) / 4 + PF - 1) / PF) * PF;
-    const size_t shm = (size_t)KSp * RT * 64 * sizeof(double);
-    return inner == 1 && (L & 3) == 0 && (Q & 3) == 0 && Q >= 256 && shm <= 150 * 1024 && outer + (Q + 63) / 64 < 0x7fffffffLL;
+    // (one timestep tile: under the bound on the keys the grid of any one tile is far within 32 bits)
+    return inner == 1 && (L & 3) == 0 && outer + (Q + 63) / 64 < 0x7fffffffLL && k2r_plan(N, Q, 1).fits;
 }
 
 // slots of the partials per timestep and parity, and the bytes of T timesteps: values, then indices
@@ -623,24 +640,17 @@ int vi_eval_resident_peak_mfma(vi_ctx* c, int N, int64_t outer, int64_t L, int64
     if (!vi_peak_fused_shape(N, outer, L, 1) || ((uintptr_t)d_Y & 31) != 0 || ((uintptr_t)d_work & 7) != 0) return VI_OK;
     const size_t need = vi_peak_fused_work_bytes(outer, L, T);
     if (work_bytes < need) return VI_OK;
-    const int KSp = (((N + 3) / 4 + PF - 1) / PF) * PF;
-    const size_t shm = (size_t)KSp * RT * 64 * sizeof(double);
-    const int ntt = (int)((T + 16 * RT - 1) / (16 * RT));
-    const int groups = k2r_groups(Q);
-    const int64_t npg = (Q + (int64_t)256 * groups - 1) / ((int64_t)256 * groups);
-    const int64_t nblk = ((npg + 7) / 8) * 8 * ntt;
-    if (nblk > 0x7fffffffLL) return VI_OK;
+    const k2r_plan pl(N, Q, T);
+    if (!pl.fits) return VI_OK;
     const int64_t S = vi_peak_fused_slots(outer, L);
     double* pval = (double*)d_work;
     int* pidx = (int*)(pval + (size_t)T * 2 * S);
     VI_HIP(hipMemsetAsync(d_work, 0xFF, need, c->stream));               // every slot empty: (a NaN, -1)
-    const bool pad = 4 * KSp > N;
-    const bool live = use_live_list();
-    auto kern = pad ? (live ? k_eval_resident_peak<true, true> : k_eval_resident_peak<true, false>)
-                    : (live ? k_eval_resident_peak<false, true> : k_eval_resident_peak<false, false>);
-    VI_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(256), shm, c->stream, N, KSp, Q, T, ntt, groups, npg, d_Y, d_C, L,
-                       kind, S, pval, pidx);
+    auto kern = pl.pad ? (pl.live ? k_eval_resident_peak<true, true> : k_eval_resident_peak<true, false>)
+                       : (pl.live ? k_eval_resident_peak<false, true> : k_eval_resident_peak<false, false>);
+    VI_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.shm));
+    hipLaunchKernelGGL(kern, dim3((unsigned)pl.nblk), dim3(256), pl.shm, c->stream, N, pl.KSp, Q, T, pl.ntt, pl.groups, pl.npg,
+                       d_Y, d_C, L, kind, S, pval, pidx);
     VI_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_peak_finish, dim3(reduce_blocks(T * outer)), dim3(256), 0, c->stream, outer, L, T, kind, S, pval, pidx,
                        d_val, d_idx);
@@ -680,24 +690,13 @@ int vi_eval_resident_mfma(vi_ctx* c, int N, int64_t Q, int64_t T, const double* 
 {
     *handled = 0;
     if (!use_own_kernel()) return VI_OK;
-    const int KSp = (((N + 3) / 4 + PF - 1) / PF) * PF;
-    const size_t shm = (size_t)KSp * RT * 64 * sizeof(double);
-    if ((Q & 3) != 0 || (((uintptr_t)d_Y | (uintptr_t)d_out) & 31) != 0 || shm > 150 * 1024 || Q < 256) return VI_OK;
-    const int ntt = (int)((T + 16 * RT - 1) / (16 * RT));
-    // points per workgroup: 256 x groups - the coefficient tile (73 KB through L2) is set up once per workgroup
-    // (measured, T = 256: 128^3 points 52 TF with 4 groups, 57 with 32; 256^3 the same from 16 up: as many as leave every CU
-    // a few workgroups)
-    const int groups = k2r_groups(Q);
-    const int64_t npg = (Q + (int64_t)256 * groups - 1) / ((int64_t)256 * groups);
-    const int64_t nblk = ((npg + 7) / 8) * 8 * ntt;
-    if (nblk > 0x7fffffffLL) return VI_OK;
-    const bool pad = 4 * KSp > N;                                       // N % 16 != 0: rows past the basis
-    // VINTERP_K2R_LIVE=0: the plain loop over every point (the live list: 4 KB + counters of LDS next to the tile)
-    const bool live = use_live_list();
-    auto kern = pad ? (live ? k_eval_resident<true, true> : k_eval_resident<true, false>)
-                    : (live ? k_eval_resident<false, true> : k_eval_resident<false, false>);
-    VI_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(256), shm, c->stream, N, KSp, Q, T, ntt, groups, npg, d_Y, d_C, d_out);
+    const k2r_plan pl(N, Q, T);
+    if (!pl.fits || (((uintptr_t)d_Y | (uintptr_t)d_out) & 31) != 0) return VI_OK;
+    auto kern = pl.pad ? (pl.live ? k_eval_resident<true, true> : k_eval_resident<true, false>)
+                       : (pl.live ? k_eval_resident<false, true> : k_eval_resident<false, false>);
+    VI_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.shm));
+    hipLaunchKernelGGL(kern, dim3((unsigned)pl.nblk), dim3(256), pl.shm, c->stream, N, pl.KSp, Q, T, pl.ntt, pl.groups, pl.npg,
+                       d_Y, d_C, d_out);
     VI_HIP(hipGetLastError());
     *handled = 1;
     return VI_OK;

@@ -57,6 +57,14 @@ def order_facets(eq, hull_vert, nsample=4096, nlead=32):
     return np.ascontiguousarray(eq[np.concatenate([np.array(lead, dtype=np.int64), rest])])
 
 
+def ravel_points(gdlat, gdlon, gdalt):
+    """The coordinates of the points as three contiguous 1-D float64 arrays of one size."""
+    lat, lon, alt = (np.ascontiguousarray(np.asarray(a, dtype=np.float64).ravel()) for a in (gdlat, gdlon, gdalt))
+    if not (lat.size == lon.size == alt.size):
+        raise ValueError('gdlat, gdlon, gdalt must have the same shape')
+    return lat, lon, alt
+
+
 GRADIENT_FRAMES = {'model': _lib.VI_FRAME_MODEL, 'enu': _lib.VI_FRAME_ENU}
 PEAK_KINDS = {'max': 0, 'min': 1}                 # vi_eval_resident_peak_f64's kind
 REDUCED_BASES = 8                                  # reduced bases a ResidentGrid keeps (evaluate_integrals), oldest out
@@ -122,11 +130,7 @@ class Estimate(object):
         """out[t] = density of coefficient row C[t] at the points; (T, Q).  `out`: optional C-contiguous float64 (T, Q)
         array to write into (e.g. from _lib.pinned_empty, like the coordinate arrays, for full-rate transfers)."""
         C = np.ascontiguousarray(C, dtype=np.float64)
-        lat = np.ascontiguousarray(np.asarray(gdlat, dtype=np.float64).ravel())
-        lon = np.ascontiguousarray(np.asarray(gdlon, dtype=np.float64).ravel())
-        alt = np.ascontiguousarray(np.asarray(gdalt, dtype=np.float64).ravel())
-        if not (lat.size == lon.size == alt.size):
-            raise ValueError('gdlat, gdlon, gdalt must have the same shape')
+        lat, lon, alt = ravel_points(gdlat, gdlon, gdalt)
         T, Q = C.shape[0], lat.size
         if C.shape[1] != self.model.nbasis:
             raise ValueError('coefficient vector length %d != nbasis %d' % (C.shape[1], self.model.nbasis))
@@ -170,66 +174,39 @@ class Estimate(object):
         if frame not in GRADIENT_FRAMES:
             raise ValueError("frame must be 'model' or 'enu', not %r" % (frame,))
         C, dC = self.get_C(time)
-        gdlat = np.asarray(gdlat, dtype=np.float64)
-        lat = np.ascontiguousarray(gdlat.ravel())
-        lon = np.ascontiguousarray(np.asarray(gdlon, dtype=np.float64).ravel())
-        alt = np.ascontiguousarray(np.asarray(gdalt, dtype=np.float64).ravel())
-        if not (lat.size == lon.size == alt.size):
-            raise ValueError('gdlat, gdlon, gdalt must have the same shape')
-        Q = lat.size
-        out = np.empty((Q, 3))
-        if Q:
-            h = self.model.handle()
-            ctx = self.model._ctx
-            bufs = []                               # freed whatever happens (a failed call must not keep device memory)
-            try:
-                for a in (lat, lon, alt):
-                    bufs.append(ctx.to_device(a))
-                bufs.append(ctx.to_device(np.ascontiguousarray(C, dtype=np.float64)))
-                bufs.append(ctx.empty((Q, 3)))
-                _lib.check(_lib.lib.vi_eval_grad_f64(h, Q, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, bufs[3].ptr, bufs[4].ptr),
-                           'vi_eval_grad_f64')
-                out = bufs[4].download()
-            finally:
-                for a in bufs:
-                    a.free()
-            if check_hull:
-                out[~self.check_hull(lat, lon, alt)] = np.nan
-            if frame == 'enu':
-                out = np.einsum('pic,pc->pi', self.model.gradient_frame(lat, lon, alt), out)
-        return out.reshape(gdlat.shape + (3,))
+        out, lat, lon, alt = self._at_points('vi_eval_grad_f64', C, gdlat, gdlon, gdalt, (3,), check_hull)
+        if frame == 'enu' and lat.size:
+            out = np.einsum('pic,pc->pi', self.model.gradient_frame(lat, lon, alt), out)
+        return out.reshape(np.shape(gdlat) + (3,))
 
     def error(self, time, gdlat, gdlon, gdalt, check_hull=True):
         """Standard error of the fitted parameter at the points, sqrt(a^T dC a) with a the basis row of the point and dC
         the coefficient covariance of the record (first-order error propagation): the ``calcerr`` output the reference
         advertises but never computes (estimate.py:139-145).  Same shape as gdlat, NaN outside the hull."""
         C, dC = self.get_C(time)
-        gdlat = np.asarray(gdlat, dtype=np.float64)
-        lat = np.ascontiguousarray(gdlat.ravel())
-        lon = np.ascontiguousarray(np.asarray(gdlon, dtype=np.float64).ravel())
-        alt = np.ascontiguousarray(np.asarray(gdalt, dtype=np.float64).ravel())
-        if not (lat.size == lon.size == alt.size):
-            raise ValueError('gdlat, gdlon, gdalt must have the same shape')
+        return self._at_points('vi_eval_err_f64', dC, gdlat, gdlon, gdalt, (), check_hull)[0].reshape(np.shape(gdlat))
+
+    def _at_points(self, entry, mat, gdlat, gdlon, gdalt, width, check_hull):
+        """What gradient and error share: the library's `entry` (points and the record's matrix `mat` in, (Q,) + width
+        out) on device copies, NaN outside the hull.  Returns (out, lat, lon, alt), the coordinates raveled."""
+        lat, lon, alt = ravel_points(gdlat, gdlon, gdalt)
         Q = lat.size
-        out = np.empty(Q)
+        out = np.empty((Q,) + width)
         if Q:
-            h = self.model.handle()
-            ctx = self.model._ctx
-            bufs = []
+            ctx = self.model.ctx
+            bufs = []                               # freed whatever happens (a failed call must not keep device memory)
             try:
-                for a in (lat, lon, alt):
+                for a in (lat, lon, alt, np.ascontiguousarray(mat, dtype=np.float64)):
                     bufs.append(ctx.to_device(a))
-                bufs.append(ctx.to_device(np.ascontiguousarray(dC, dtype=np.float64)))
-                bufs.append(ctx.empty((Q,)))
-                _lib.check(_lib.lib.vi_eval_err_f64(h, Q, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, bufs[3].ptr, bufs[4].ptr),
-                           'vi_eval_err_f64')
+                bufs.append(ctx.empty((Q,) + width))
+                _lib.check(getattr(_lib.lib, entry)(self.model.handle(), Q, *(a.ptr for a in bufs)), entry)
                 out = bufs[4].download()
             finally:
                 for a in bufs:
                     a.free()
             if check_hull:
                 out[~self.check_hull(lat, lon, alt)] = np.nan
-        return out.reshape(gdlat.shape)
+        return out, lat, lon, alt
 
     # estimate.py:153-178 (boolean mask, same shape as the inputs)
     def check_hull(self, lat0, lon0, alt0):
@@ -268,11 +245,7 @@ class ResidentGrid(object):
         self.est = est
         self.frame = gradient
         self.shape = np.asarray(gdlat).shape
-        lat = np.ascontiguousarray(np.asarray(gdlat, dtype=np.float64).ravel())
-        lon = np.ascontiguousarray(np.asarray(gdlon, dtype=np.float64).ravel())
-        alt = np.ascontiguousarray(np.asarray(gdalt, dtype=np.float64).ravel())
-        if not (lat.size == lon.size == alt.size):
-            raise ValueError('gdlat, gdlon, gdalt must have the same shape')
+        lat, lon, alt = ravel_points(gdlat, gdlon, gdalt)
         self.Q = lat.size
         ctx = est.model.ctx
         N = est.model.nbasis
@@ -313,53 +286,89 @@ class ResidentGrid(object):
             for a in tmp:
                 a.free()
 
-    def _slabs(self, C, out, width):
-        """The checks evaluate_coeffs and evaluate_gradients share: C as (T, N) float64, `out` or a new array of shape
-        (T,) + width, and the timesteps per slab whose output (8 bytes per element of `width`) fits a quarter of the free
-        device memory.  Returns (C, out, slab); slab 0: nothing to compute."""
+    def _open(self, dM):
+        """dM, a matrix of this grid on the device, unless close() has given it back."""
+        if dM is None:
+            raise ValueError('this ResidentGrid has been closed')
+        return dM
+
+    def _coeffs(self, C):
         C = np.ascontiguousarray(C, dtype=np.float64)
         N = self.est.model.nbasis
         if C.ndim != 2 or C.shape[1] != N:
             raise ValueError('coefficients must have shape (T, %d)' % N)
-        T = C.shape[0]
-        shape = (T,) + width
+        return C
+
+    def _coeffs_at(self, times):
+        """The coefficient rows of Estimate.get_C per time: (len(times), N)."""
+        C = [np.asarray(self.est.get_C(t)[0], dtype=np.float64) for t in times]
+        return np.array(C).reshape(len(times), self.est.model.nbasis)
+
+    @staticmethod
+    def _out(out, shape):
         if out is None:
-            out = np.empty(shape, dtype=np.float64)
-        elif out.shape != shape or out.dtype != np.float64 or not out.flags.c_contiguous:
+            return np.empty(shape, dtype=np.float64)
+        if out.shape != shape or out.dtype != np.float64 or not out.flags.c_contiguous:
             raise ValueError('out must be a C-contiguous float64 array of shape (%s)' % ', '.join('%d' % n for n in shape))
+        return out
+
+    def _slab(self, T, nbytes):
+        """The timesteps per slab: what a timestep takes on the device (`nbytes`) fits a quarter of the free device memory."""
+        free, _ = self.est.model.ctx.mem_info()
+        return int(max(1, min(T, (free // 4) // max(1, nbytes))))
+
+    def _slabs(self, C, out, width):
+        """The checks of the products with coefficients: C as (T, N) float64, `out` or a new array of shape (T,) + width, and
+        the timesteps per slab of that output.  Returns (C, out, slab); slab 0: nothing to compute."""
+        C = self._coeffs(C)
+        T = C.shape[0]
+        out = self._out(out, (T,) + width)
         if T == 0 or self.Q == 0:
             return C, out, 0
-        free, _ = self.est.model.ctx.mem_info()
-        return C, out, int(max(1, min(T, (free // 4) // max(1, int(np.prod(width)) * 8))))
+        return C, out, self._slab(T, int(np.prod(width)) * 8)
+
+    def _run(self, slab, X, outs, call, work=None, once=True):
+        """The slab loop of every map on the grid.  X holds the inputs of the T timesteps row by row: uploaded once, or (once
+        False) slab by slab.  Per slab of tc timesteps from t0: call(tc, pointer to row t0 of X on the device, device
+        outputs..., work buffer of `work` bytes unless None), then the device outputs to outs[k][t0:t0 + tc].  Every device
+        buffer is freed whatever happens."""
+        ctx = self.est.model.ctx
+        T = X.shape[0]
+        bufs = []
+        try:
+            dX = ctx.to_device(X) if once else ctx.empty((slab,) + X.shape[1:])
+            bufs.append(dX)
+            for o in outs:
+                bufs.append(ctx.empty((slab,) + o.shape[1:], o.dtype))
+            if work is not None:
+                bufs.append(ctx.empty(work, np.uint8))
+            for t0 in range(0, T, slab):
+                tc = min(slab, T - t0)
+                if not once:
+                    dX.upload(X[t0:t0 + tc])
+                call(tc, dX.offset_ptr(t0 * X[0].size if once else 0), *bufs[1:])
+                for o, dO in zip(outs, bufs[1:]):
+                    part = o[t0:t0 + tc]
+                    _lib.check(_lib.lib.vi_d2h(ctx.handle, part.ctypes.data_as(_lib.VOIDP), dO.ptr, part.nbytes), 'd2h')
+        finally:
+            for a in bufs:
+                a.free()
+        return outs
 
     def _products(self, dM, cols, C, out, slab):
         """out[t0:t0 + slab] = vi_eval_resident_f64 of the resident matrix dM (N rows, `cols` columns) with C, slab by slab."""
-        ctx = self.est.model.ctx
-        N = self.est.model.nbasis
-        T = C.shape[0]
-        dC = dO = None
-        try:
-            dC = ctx.to_device(C)
-            dO = ctx.empty((slab, cols))
-            for t0 in range(0, T, slab):
-                tc = min(slab, T - t0)
-                _lib.check(_lib.lib.vi_eval_resident_f64(self.est.model.handle(), cols, tc, dM.ptr, dC.offset_ptr(t0 * N),
-                                                         dO.ptr), 'vi_eval_resident_f64')
-                _lib.check(_lib.lib.vi_d2h(ctx.handle, out[t0:t0 + tc].ctypes.data_as(_lib.VOIDP), dO.ptr, tc * cols * 8), 'd2h')
-        finally:
-            for a in (dC, dO):
-                if a is not None:
-                    a.free()
-        return out
+        h = self.est.model.handle()
+
+        def call(tc, dC, dO):
+            _lib.check(_lib.lib.vi_eval_resident_f64(h, cols, tc, dM.ptr, dC, dO.ptr), 'vi_eval_resident_f64')
+        return self._run(slab, C, (out,), call)[0]
 
     def evaluate_coeffs(self, C, out=None):
         """out[t] = density of coefficient row C[t] on the grid; (T, Q) host array."""
         C, out, slab = self._slabs(C, out, (self.Q,))
         if slab == 0:
             return out
-        if self.dY is None:
-            raise ValueError('this ResidentGrid has been closed')
-        return self._products(self.dY, self.Q, C, out, slab)
+        return self._products(self._open(self.dY), self.Q, C, out, slab)
 
     def evaluate_gradients(self, C, out=None):
         """out[t, c] = component c of the gradient of the parameter with coefficient row C[t] on the grid; (T, 3, Q) host
@@ -368,14 +377,11 @@ class ResidentGrid(object):
         C, out, slab = self._slabs(C, out, (3, self.Q))
         if slab == 0:
             return out
-        if self.dG is None:
-            raise ValueError('this ResidentGrid has been closed')
-        return self._products(self.dG, 3 * self.Q, C, out, slab)
+        return self._products(self._open(self.dG), 3 * self.Q, C, out, slab)
 
     def __call__(self, times):
         """Densities at the grid for a list of datetimes (Estimate.get_C per time): array (len(times),) + grid shape."""
-        C = np.array([np.asarray(self.est.get_C(t)[0], dtype=np.float64) for t in times])
-        return self.evaluate_coeffs(C).reshape((len(times),) + tuple(self.shape))
+        return self.evaluate_coeffs(self._coeffs_at(times)).reshape((len(times),) + tuple(self.shape))
 
     def _need_gradient_basis(self):
         if self.frame is None:
@@ -390,8 +396,7 @@ class ResidentGrid(object):
         the density; non-finite at the pole of the cap (sin theta' = 0), where the reference's formula divides by zero, as
         Estimate.gradient is."""
         self._need_gradient_basis()
-        C = np.array([np.asarray(self.est.get_C(t)[0], dtype=np.float64) for t in times]).reshape(len(times), self.est.model.nbasis)
-        return self.evaluate_gradients(C).reshape((len(times), 3) + tuple(self.shape))
+        return self.evaluate_gradients(self._coeffs_at(times)).reshape((len(times), 3) + tuple(self.shape))
 
     def evaluate_errors(self, dC, out=None):
         """out[t] = standard error sqrt(a^T dC[t] a) of the fitted parameter on the grid for each covariance dC[t] (as stored
@@ -402,33 +407,15 @@ class ResidentGrid(object):
         if dC.ndim != 3 or dC.shape[1:] != (N, N):
             raise ValueError('covariances must have shape (T, %d, %d)' % (N, N))
         T = dC.shape[0]
-        if out is None:
-            out = np.empty((T, self.Q), dtype=np.float64)
-        elif out.shape != (T, self.Q) or out.dtype != np.float64 or not out.flags.c_contiguous:
-            raise ValueError('out must be a C-contiguous float64 array of shape (%d, %d)' % (T, self.Q))
+        out = self._out(out, (T, self.Q))
         if T == 0 or self.Q == 0:
             return out
-        ctx = self.est.model.ctx
-        # timesteps in slabs whose covariances and output fit a quarter of the free device memory
-        free, _ = ctx.mem_info()
-        slab = int(max(1, min(T, (free // 4) // max(1, (self.Q + N * N) * 8))))
-        if self.dY is None:
-            raise ValueError('this ResidentGrid has been closed')
-        dD = dO = None
-        try:
-            dD = ctx.empty((slab, N, N))
-            dO = ctx.empty((slab, self.Q))
-            for t0 in range(0, T, slab):
-                tc = min(slab, T - t0)
-                dD.upload(dC[t0:t0 + tc])
-                _lib.check(_lib.lib.vi_eval_resident_err_f64(self.est.model.handle(), self.Q, tc, self.dY.ptr, dD.ptr, dO.ptr),
-                           'vi_eval_resident_err_f64')
-                _lib.check(_lib.lib.vi_d2h(ctx.handle, out[t0:t0 + tc].ctypes.data_as(_lib.VOIDP), dO.ptr, tc * self.Q * 8), 'd2h')
-        finally:
-            for a in (dD, dO):
-                if a is not None:
-                    a.free()
-        return out
+        slab = self._slab(T, (self.Q + N * N) * 8)      # the covariances of a slab go up with it, not all T at once
+        h, dY = self.est.model.handle(), self._open(self.dY)
+
+        def call(tc, dD, dO):
+            _lib.check(_lib.lib.vi_eval_resident_err_f64(h, self.Q, tc, dY.ptr, dD, dO.ptr), 'vi_eval_resident_err_f64')
+        return self._run(slab, dC, (out,), call, once=False)[0]
 
     def error(self, times):
         """Standard-error maps at the grid for a list of datetimes (the covariance of Estimate.get_C per time, as __call__
@@ -463,10 +450,7 @@ class ResidentGrid(object):
         if kind not in PEAK_KINDS:
             raise ValueError("kind must be 'max' or 'min', not %r" % (kind,))
         M = outer * inner
-        C = np.ascontiguousarray(C, dtype=np.float64)
-        N = self.est.model.nbasis
-        if C.ndim != 2 or C.shape[1] != N:
-            raise ValueError('coefficients must have shape (T, %d)' % N)
+        C = self._coeffs(C)
         T = C.shape[0]
         if out is None:
             val, idx = np.empty((T, M), dtype=np.float64), np.empty((T, M), dtype=np.int32)
@@ -482,42 +466,21 @@ class ResidentGrid(object):
             val.fill(np.nan)                # (columns of length zero: nothing to select)
             idx.fill(-1)
             return val, idx
-        if self.dY is None:
-            raise ValueError('this ResidentGrid has been closed')
-        ctx = self.est.model.ctx
-        h = self.est.model.handle()
+        h, dY = self.est.model.handle(), self._open(self.dY)
         work = lambda tc: int(_lib.lib.vi_eval_resident_peak_work_bytes(h, outer, L, inner, tc))
-        # timesteps in slabs whose work space and maps fit a quarter of the free device memory
-        free, _ = ctx.mem_info()
-        slab = int(max(1, min(T, (free // 4) // max(1, work(1) + M * 12))))
-        bufs = []
-        try:
-            dC = ctx.to_device(C)
-            bufs.append(dC)
-            dW = ctx.empty(work(slab), np.uint8)
-            bufs.append(dW)
-            dV, dI = ctx.empty((slab, M)), ctx.empty((slab, M), np.int32)
-            bufs += [dV, dI]
-            for t0 in range(0, T, slab):
-                tc = min(slab, T - t0)
-                _lib.check(_lib.lib.vi_eval_resident_peak_f64(h, outer, L, inner, tc, self.dY.ptr, dC.offset_ptr(t0 * N),
-                                                              PEAK_KINDS[kind], dV.ptr, dI.ptr, dW.ptr, dW.nbytes),
-                           'vi_eval_resident_peak_f64')
-                _lib.check(_lib.lib.vi_d2h(ctx.handle, val[t0:t0 + tc].ctypes.data_as(_lib.VOIDP), dV.ptr, tc * M * 8), 'd2h')
-                _lib.check(_lib.lib.vi_d2h(ctx.handle, idx[t0:t0 + tc].ctypes.data_as(_lib.VOIDP), dI.ptr, tc * M * 4), 'd2h')
-        finally:
-            for a in bufs:
-                a.free()
-        return val, idx
+        slab = self._slab(T, work(1) + M * 12)          # the work space and the two maps
+
+        def call(tc, dC, dV, dI, dW):
+            _lib.check(_lib.lib.vi_eval_resident_peak_f64(h, outer, L, inner, tc, dY.ptr, dC, PEAK_KINDS[kind], dV.ptr, dI.ptr,
+                                                          dW.ptr, dW.nbytes), 'vi_eval_resident_peak_f64')
+        return self._run(slab, C, (val, idx), call, work=work(slab))
 
     def peak(self, times, axis=-1, kind='max'):
         """Peak maps for a list of datetimes (coefficients of Estimate.get_C per time, as __call__ takes them): (value, index),
         each (len(times),) + the grid shape without `axis`.  On a (lat, lon, alt) grid with the default axis: the peak of the
         parameter along altitude and the altitude index where it sits."""
         axis, _, _, _ = self._columns(axis)
-        C = np.array([np.asarray(self.est.get_C(t)[0], dtype=np.float64) for t in times]).reshape(len(times),
-                                                                                                 self.est.model.nbasis)
-        val, idx = self.evaluate_peaks(C, axis=axis, kind=kind)
+        val, idx = self.evaluate_peaks(self._coeffs_at(times), axis=axis, kind=kind)
         rest = (len(times),) + tuple(self.shape[:axis]) + tuple(self.shape[axis + 1:])
         return val.reshape(rest), idx.reshape(rest)
 
@@ -575,18 +538,15 @@ class ResidentGrid(object):
         if slab == 0:
             out.fill(np.nan)                # (columns of length zero: no point inside)
             return out
-        if self.dY is None:
-            raise ValueError('this ResidentGrid has been closed')
+        self._open(self.dY)
         return self._products(self._reduced_basis(axis, outer, L, inner, w), M, C, out, slab)
 
     def integrate(self, times, weights=None, axis=-1):
         """Weighted column sums for a list of datetimes (coefficients of Estimate.get_C per time): (len(times),) + the grid
         shape without `axis`; see evaluate_integrals."""
         axis, _, _, _ = self._columns(axis)
-        C = np.array([np.asarray(self.est.get_C(t)[0], dtype=np.float64) for t in times]).reshape(len(times),
-                                                                                                 self.est.model.nbasis)
         rest = (len(times),) + tuple(self.shape[:axis]) + tuple(self.shape[axis + 1:])
-        return self.evaluate_integrals(C, weights=weights, axis=axis).reshape(rest)
+        return self.evaluate_integrals(self._coeffs_at(times), weights=weights, axis=axis).reshape(rest)
 
     def close(self):
         """Give the basis matrix (the gradient basis, the reduced bases of evaluate_integrals) back to the device (idempotent).  Also runs
