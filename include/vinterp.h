@@ -148,6 +148,25 @@ int  vi_transform_f64(vi_model* model, int64_t P, const double* d_lat, const dou
 int  vi_eval_f64(vi_model* model, int64_t Q, const double* d_lat, const double* d_lon,
                  const double* d_alt, int64_t T, const double* d_C,
                  const double* d_hull_eq, int32_t F, double hull_tol, double* d_out);
+/* Points that each carry their OWN time (a satellite pass, another radar's range gates, a profile every few minutes): one call
+ * for a whole trajectory in place of one vi_eval_f64 call per record.  d_C holds the R coefficient rows of the file (R x N, as
+ * stored), d_rec[q] the row of point q - what Estimate.get_C (estimate.py:180-221) selects for the point's time.
+ *   nearest mode (d_w == NULL):   d_out[q] = D(d_rec[q], q),  D(r, q) = sum_n basis_n(q) * d_C[r*N + n]
+ *   interpolation (d_w != NULL):  d_out[q] = (1 - d_w[q]) * D(d_rec[q], q) + d_w[q] * D(d_rec[q] + 1, q), computed as written:
+ *                                 no shortcut at d_w = 0 or 1, so a NaN in either row of the pair gives NaN, as get_C's blend
+ * NaN where the point fails the hull test (hull_eq != NULL, as in vi_eval_f64), where d_rec[q] < 0 (no record for the time)
+ * and where the row the point needs - d_rec[q], in interpolation mode d_rec[q] + 1 - is >= R.  In nearest mode a NaN in a row
+ * reaches the points of that row only (the row is selected, not multiplied by zero).  d_C is never read outside its R rows.
+ * Correct for ANY order of d_rec, but the cost grows with the span of rows inside a group of 64 consecutive points: a group
+ * evaluates its points once per window of 4 rows (3 in interpolation mode) between its lowest and highest row.  SORT the
+ * points by d_rec: the passes beyond one per group are then at most about R / 3 in the whole call, whatever Q is.
+ * Models and orders as vi_eval_f64 (sphharmlag up to (24, 16), RBF), fp64 chains whatever vi_model_set_eval_precision set.
+ * The orders of vi_eval_f64's fast kernels run the tiled kernel K2t (csrc/vi_basis.hip); other orders, VINTERP_EVAL=generic and the RBF model
+ * read each point's own row(s) from global memory (correct, not tuned).  Asynchronous on the context's stream; timed for
+ * vi_eval_kernel_ms like its siblings (tests/test_gpu_track.py). */
+int  vi_eval_track_f64(vi_model* model, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt,
+                       const int32_t* d_rec, const double* d_w, int64_t R, const double* d_C,
+                       const double* d_hull_eq, int32_t F, double hull_tol, double* d_out);
 /* Many timesteps on ONE grid (BASELINE configs[3]: a GPU's share of 10 000 timesteps, all on the same 256^3 grid - Estimate.__call__
  * (estimate.py:110-123) once per timestep in the reference, which rebuilds the basis of the grid every time): the basis matrix
  * of the grid is assembled once and kept in HBM, and every batch of timesteps is one matrix product.
@@ -217,8 +236,8 @@ int    vi_reduce_basis_f64(vi_model* model, int64_t outer, int64_t L, int64_t in
  * BASELINE configs[4] sweeps against the 1e-6 tolerance.  Orders with an fp32 kernel: (MAXL, MAXK) = (6,4), (2,8), (12,8);
  * others return VI_ERR_UNSUPPORTED from vi_eval_f64 while the flag is set. */
 int  vi_model_set_eval_precision(vi_model* model, int32_t chain_f32);
-/* device time (ms) of the evaluation kernel launches of the last vi_eval_f64 / vi_eval_resident_f64 / vi_eval_resident_err_f64 /
- * vi_eval_resident_peak_f64 call on this context, from HIP events recorded on the context's stream around them (the preparation kernels are excluded).
+/* device time (ms) of the evaluation kernel launches of the last vi_eval_f64 / vi_eval_track_f64 / vi_eval_resident_f64 /
+ * vi_eval_resident_err_f64 / vi_eval_resident_peak_f64 call on this context, from HIP events recorded on the context's stream around them (the preparation kernels are excluded).
  * The events are recorded only while vi_ctx_set_eval_timing(ctx, 1) is in force (default: off - the pair costs a 0.2 ms call about 7 us);
  * vi_eval_kernel_ms fails with VI_ERR_ARG while it is off or before a call has been timed. */
 int  vi_ctx_set_eval_timing(vi_ctx* ctx, int32_t on);

@@ -861,6 +861,62 @@ struct MainSegments {
     }
 };
 
+// One pass of the chains of a point over the tile E.shC, for K2t (k_track_sph_fast below): E.acc[t] = sum_n basis_n(point) *
+// tile[t][n] without the factor exp(-z/2), t = 0 .. TT-1.  shc: the recurrence table [nj][L] in LDS, nvl[l]: the degree at which
+// chain segment l ends.  The contraction, the start-up's consumption and the main segments are the pieces k_eval_sph_fast runs
+// (FastEval, ConsumeAt, MainSegments); the triangular start-up around them is written out here as it is in that kernel, which
+// keeps its own: calling this function from it changed the register allocation of most of its instantiations (e.g. (6, 4) at
+// TT = 1: 95 -> 99 VGPRs, five -> four waves per SIMD), and that kernel is on the benchmarked path.
+template <int L, int K, int TT, typename CT>
+__device__ __forceinline__ void fast_chains(FastEval<L, K, TT>& E, const SphGroupDev& G, const Geom& g, const CT* shc,
+                                            const int* nvl, int nj)
+{
+    laguerre<K>(K, g.z, E.Lk);
+#pragma unroll
+    for (int t = 0; t < TT; ++t) E.acc[t] = 0.0;
+    double cm[L], sm[L];
+    cm[0] = 1.0;
+    sm[0] = 0.0;
+#pragma unroll
+    for (int m = 1; m < L; ++m) {
+        cm[m] = cm[m - 1] * g.cphi - sm[m - 1] * g.sphi;
+        sm[m] = sm[m - 1] * g.cphi + cm[m - 1] * g.sphi;
+    }
+    const CT x = (CT)g.x;
+    const double zz = 0.5 * (1.0 - g.x);
+    const bool intseed = (G.nterms == 0);
+    CT cur[L], prev[L];
+#pragma unroll
+    for (int m = 0; m < L; ++m) { cur[m] = (CT)0.0; prev[m] = (CT)0.0; }
+    double pmm = 1.0, spow = 1.0;
+    // ---- start-up: degrees j = 0 .. L, compile-time triangular structure ------------------------------
+#pragma unroll
+    for (int j = 0; j <= L; ++j) {
+#pragma unroll
+        for (int m = 0; m < L; ++m) {
+            if (j > m + 1) {
+                if (j < nj) {
+                    const CT nw = fma(x, cur[m], -(shc[j * L + m] * prev[m]));
+                    prev[m] = cur[m];
+                    cur[m] = nw;
+                }
+            } else if (j == m) {
+                if (m > 0) { pmm *= -(2.0 * m - 1.0) * g.s; spow *= g.s; }
+                if (intseed) cur[m] = (CT)pmm;
+                else cur[m] = (CT)(G.pref[m] * spow * hyp_series(G.q + (size_t)m * G.nterms, G.nterms, zz));
+            } else if (j == m + 1) {
+                prev[m] = cur[m];
+                if (intseed) cur[m] = (CT)(g.x * (2.0 * m + 1.0) * pmm);
+                else cur[m] = (CT)(G.pref[L + m] * spow * hyp_series(G.q + (size_t)(L + m) * G.nterms, G.nterms, zz));
+            }
+        }
+        ConsumeAt<L, K, TT, 0>::run(E, nvl, j, cur, cm, sm);
+    }
+    // ---- main: all chains in recurrence mode; one segment per degree l --------------------------------
+    int j = L + 1;
+    MainSegments<L, K, TT, 0>::run(E, shc, nvl, j, x, cur, prev, cm, sm);
+}
+
 // CT = arithmetic type of the Legendre chains: double, or float for the fp32 variant of BASELINE configs[4]'s tolerance
 // sweep (seeds, trigonometric and Laguerre factors and the contraction with the coefficients stay fp64)
 template <int L, int K, int TT, typename CT>
@@ -949,6 +1005,131 @@ __global__ __launch_bounds__(BLOCK) void k_eval_sph_fast(SphDev M, int64_t Q, co
         for (int t = 0; t < TT; ++t)
             if (t < tcount) out[(int64_t)t * Q + q] = in ? Ez * E.acc[t] : __builtin_nan("");
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// K2t: densities along a trajectory, every point at its own time (vi_eval_track_f64).  Point q takes prepared coefficient row
+// rec[q] (nearest mode) or the blend (1 - w[q]) D(rec[q]) + w[q] D(rec[q] + 1) of the densities D of two neighbouring rows.
+// The unit is a workgroup of ONE wave (64 points) with its own tile: the wave finds the lowest and highest row its live lanes
+// need (shuffles over rec: nothing assumes sorted input), stages the window of TT prepared rows from the lowest one in LDS -
+// rows past R - 1 zero-filled, never read - and runs the chains of k_eval_sph_fast once for TT accumulators; the epilogue takes
+// each lane's own accumulator (two neighbours when blending) by an unrolled compare-select, never a product with zero: a NaN
+// row touches no other row's points.  Where the wave's rows span more than a window the pass is repeated from the next window
+// - consecutive windows share one row when blending, so that every pair (rec, rec + 1) lies inside one - until the highest row
+// is covered; a lane keeps the value of the one pass whose window holds its rows.  With the points sorted by record the spans
+// of all waves add up to at most R + (number of waves), so the passes beyond one per wave are at most about R / (TT - 1) wave
+// passes in total, whatever Q is; unsorted input is correct and costs up to R / (TT - 1) passes per wave.  A wave without a
+// live lane (outside the hull, no record, rows past R - 1) leaves before the table is staged.  One wave per workgroup: the
+// barriers around the staging are wave barriers, the windows follow the 64 points and not 256, and the LDS need is that of
+// k_eval_sph_fast at the same TT, so the same orders fit.
+constexpr int TRACK_BLOCK = 64;
+constexpr int TRACK_TT = 4;         // the tile width: 3.9e10 / 4 point-rows per second against 1.4e10 at TT = 1 (launch_eval_sph_fast)
+
+// what a point of a track needs to be computed at all: a record, its row(s) inside the R rows, inside the hull
+__device__ __forceinline__ bool track_live(int64_t q, int64_t qc, int64_t Q, int r, int R, int pair,
+                                           const unsigned char* __restrict__ mask, int F)
+{
+    return q < Q && r >= 0 && r <= R - 1 - pair && (F == 0 || mask[qc] != 0);
+}
+
+template <int L, int K, int TT, bool INTERP>
+__global__ __launch_bounds__(TRACK_BLOCK) void k_track_sph_fast(SphDev M, int64_t Q, const double* __restrict__ lat,
+                                                                const double* __restrict__ lon, const double* __restrict__ alt,
+                                                                const int* __restrict__ rec, const double* __restrict__ wgt, int R,
+                                                                const double* __restrict__ Cp,
+                                                                const unsigned char* __restrict__ mask, int F,
+                                                                double* __restrict__ out)
+{
+    constexpr int NB = L * L * K;
+    constexpr int PAIR = INTERP ? 1 : 0;
+    constexpr int STEP = TT - PAIR;                     // rows from one window to the next
+    static_assert(STEP >= 1, "a blending window holds at least two rows");
+    extern __shared__ __align__(16) double sh[];
+    const int64_t q = (int64_t)blockIdx.x * TRACK_BLOCK + threadIdx.x;
+    const int64_t qc = q < Q ? q : Q - 1;
+    const int r = rec[qc];
+    const bool live = track_live(q, qc, Q, r, R, PAIR, mask, F);
+    if (!__any(live)) {                                 // (the whole workgroup: no barrier has been met)
+        if (q < Q) out[q] = __builtin_nan("");
+        return;
+    }
+    int lo = live ? r : 0x7fffffff, hi = live ? r + PAIR : -1;
+#pragma unroll
+    for (int off = TRACK_BLOCK / 2; off > 0; off >>= 1) {
+        lo = min(lo, __shfl_xor(lo, off, TRACK_BLOCK));
+        hi = max(hi, __shfl_xor(hi, off, TRACK_BLOCK));
+    }
+    lo = __builtin_amdgcn_readfirstlane(lo);            // 0 <= lo <= hi <= R - 1
+    hi = __builtin_amdgcn_readfirstlane(hi);
+    const SphGroupDev G = M.groups[0];
+    const int nj = G.nvmax + 1;
+    double* shc = sh;                                   // [nj][L] recurrence table
+    double* shC = sh + ((nj * L + 1) & ~1);             // [TT][NB] the window
+    int* nvl = reinterpret_cast<int*>(shC + TT * NB);   // [L]
+    for (int i = threadIdx.x; i < nj * L; i += TRACK_BLOCK) shc[i] = G.c[i];
+    for (int j = threadIdx.x; j < nj; j += TRACK_BLOCK) {
+        const int l = G.pick[j];
+        if (l >= 0) nvl[l] = j;
+    }
+    const Geom g = sph_geom(M, lat[qc], lon[qc], alt[qc]);
+    const double Ez = exp(-0.5 * g.z);
+    const double w = INTERP ? wgt[qc] : 0.0;
+    double val = __builtin_nan("");
+    for (int base = lo;; base += STEP) {
+        __syncthreads();                                // the pass before has read the window
+        for (int i = threadIdx.x; i < TT * NB; i += TRACK_BLOCK)
+            shC[i] = i / NB < R - base ? Cp[(int64_t)base * NB + i] : 0.0;
+        __syncthreads();
+        FastEval<L, K, TT> E;
+        E.shC = shC;
+        fast_chains<L, K, TT, double>(E, G, g, shc, nvl, nj);
+        const int d = live ? r - base : -1;             // the lane's row in this window
+        double a = 0.0, b = 0.0;
+#pragma unroll
+        for (int t = 0; t < TT; ++t) {
+            if (d == t) a = E.acc[t];
+            if (INTERP && d + 1 == t) b = E.acc[t];
+        }
+        if (d >= 0 && d < STEP) val = INTERP ? (1.0 - w) * (Ez * a) + w * (Ez * b) : Ez * a;
+        if (hi - base <= TT - 1) break;                 // wave-uniform
+    }
+    if (q < Q) out[q] = live ? val : __builtin_nan("");
+}
+
+// The per-lane form for the orders without a fast kernel (and VINTERP_EVAL=generic): the generic sink reads the lane's own
+// prepared row, or its two rows, from global memory.  Correct, not tuned.
+template <int LCAP, int KCAP, bool INTERP>
+__global__ __launch_bounds__(BLOCK) void k_track_sph(SphDev M, int64_t Q, const double* __restrict__ lat,
+                                                     const double* __restrict__ lon, const double* __restrict__ alt,
+                                                     const int* __restrict__ rec, const double* __restrict__ wgt, int R,
+                                                     const double* __restrict__ Cp, const unsigned char* __restrict__ mask,
+                                                     int F, double* __restrict__ out)
+{
+    constexpr int TT = INTERP ? 2 : 1;
+    const int64_t q = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const int64_t qc = q < Q ? q : Q - 1;
+    const int r = rec[qc];
+    const bool live = track_live(q, qc, Q, r, R, TT - 1, mask, F);
+    if (!__any(live)) {
+        if (q < Q) out[q] = __builtin_nan("");
+        return;
+    }
+    const Geom g = sph_geom(M, lat[qc], lon[qc], alt[qc]);
+    EvalSink<KCAP, TT> sink;
+    sink.Cp = Cp + (int64_t)(live ? r : 0) * M.N;      // (a live lane exists: row 0 does)
+    sink.maxk = M.maxk;
+    sink.NB = M.N;
+    laguerre<KCAP>(M.maxk, g.z, sink.Lk);
+#pragma unroll
+    for (int t = 0; t < TT; ++t) sink.acc[t] = 0.0;
+    sph_point<LCAP, KCAP>(M, g, sink);
+    const double E = exp(-0.5 * g.z);
+    double val = E * sink.acc[0];
+    if (INTERP) {
+        const double w = wgt[qc];
+        val = (1.0 - w) * val + w * (E * sink.acc[TT - 1]);
+    }
+    if (q < Q) out[q] = live ? val : __builtin_nan("");
 }
 
 // Cp[t][r*maxk + k] = C[t][k*L2 + r] * scale[r]
@@ -1045,6 +1226,41 @@ __global__ __launch_bounds__(BLOCK) void k_eval_rbf(RbfDev M, int64_t Q, const d
     }
 }
 
+// K2t for the RBF model, per lane: the lane's own coefficient row, or its two rows, from global memory (see k_track_sph)
+template <bool INTERP>
+__global__ __launch_bounds__(BLOCK) void k_track_rbf(RbfDev M, int64_t Q, const double* __restrict__ lat,
+                                                     const double* __restrict__ lon, const double* __restrict__ alt,
+                                                     const int* __restrict__ rec, const double* __restrict__ wgt, int R,
+                                                     const double* __restrict__ C, const unsigned char* __restrict__ mask, int F,
+                                                     double* __restrict__ out)
+{
+    const int64_t q = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const int64_t qc = q < Q ? q : Q - 1;
+    const int r = rec[qc];
+    const bool live = track_live(q, qc, Q, r, R, INTERP ? 1 : 0, mask, F);
+    if (!__any(live)) {
+        if (q < Q) out[q] = __builtin_nan("");
+        return;
+    }
+    double X, Y, Z;
+    geodetic2ecef(lat[qc], lon[qc], alt[qc], X, Y, Z);
+    const double* __restrict__ c = M.centers;
+    const double* __restrict__ Cr = C + (int64_t)(live ? r : 0) * M.N;      // (a live lane exists: row 0 does)
+    double a = 0.0, b = 0.0;
+    for (int n = 0; n < M.N; ++n) {
+        const double dx = X - c[3 * n], dy = Y - c[3 * n + 1], dz = Z - c[3 * n + 2];
+        const double e = exp(-(dx * dx + dy * dy + dz * dz) * M.inv_eps2);
+        a = fma(e, Cr[n], a);
+        if (INTERP) b = fma(e, Cr[M.N + n], b);
+    }
+    double val = a;
+    if (INTERP) {
+        const double w = wgt[qc];
+        val = (1.0 - w) * a + w * b;
+    }
+    if (q < Q) out[q] = live ? val : __builtin_nan("");
+}
+
 __global__ void k_transform_rbf(int64_t P, const double* __restrict__ lat, const double* __restrict__ lon,
                                 const double* __restrict__ alt, double* X, double* Y, double* Z)
 {
@@ -1122,6 +1338,44 @@ int launch_eval_sph_fast(vi_model* m, int64_t Q, const double* lat, const double
         }
         VI_HIP(hipGetLastError());
     }
+    return VI_OK;
+}
+
+// K2t launches (vi_eval_track_f64): w == nullptr is nearest mode.  Cp: the R prepared rows.
+template <int L, int K>
+int launch_track_sph_fast(vi_model* m, int64_t Q, const double* lat, const double* lon, const double* alt, const int* rec,
+                          const double* w, int R, const double* Cp, const unsigned char* hull, int F, double* out)
+{
+    const int nj = m->nvmax0 + 1;
+    const size_t shm = (size_t)(((nj * L + 1) & ~1) + TRACK_TT * m->N) * sizeof(double) + L * sizeof(int) + 16;
+    const dim3 grid(nblocks(Q, TRACK_BLOCK)), block(TRACK_BLOCK);
+    if (w) {
+        VI_HIP(hipFuncSetAttribute((const void*)k_track_sph_fast<L, K, TRACK_TT, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   64 * 1024));
+        hipLaunchKernelGGL((k_track_sph_fast<L, K, TRACK_TT, true>), grid, block, shm, m->ctx->stream, m->sph, Q, lat, lon, alt,
+                           rec, w, R, Cp, hull, F, out);
+    } else {
+        VI_HIP(hipFuncSetAttribute((const void*)k_track_sph_fast<L, K, TRACK_TT, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   64 * 1024));
+        hipLaunchKernelGGL((k_track_sph_fast<L, K, TRACK_TT, false>), grid, block, shm, m->ctx->stream, m->sph, Q, lat, lon, alt,
+                           rec, w, R, Cp, hull, F, out);
+    }
+    VI_HIP(hipGetLastError());
+    return VI_OK;
+}
+
+template <int LCAP, int KCAP>
+int launch_track_sph(vi_model* m, int64_t Q, const double* lat, const double* lon, const double* alt, const int* rec,
+                     const double* w, int R, const double* Cp, const unsigned char* hull, int F, double* out)
+{
+    const dim3 grid(nblocks(Q, BLOCK)), block(BLOCK);
+    if (w)
+        hipLaunchKernelGGL((k_track_sph<LCAP, KCAP, true>), grid, block, 0, m->ctx->stream, m->sph, Q, lat, lon, alt, rec, w, R, Cp,
+                           hull, F, out);
+    else
+        hipLaunchKernelGGL((k_track_sph<LCAP, KCAP, false>), grid, block, 0, m->ctx->stream, m->sph, Q, lat, lon, alt, rec, w, R, Cp,
+                           hull, F, out);
+    VI_HIP(hipGetLastError());
     return VI_OK;
 }
 
@@ -1660,4 +1914,74 @@ extern "C" int vi_eval_f64(vi_model* m, int64_t Q, const double* d_lat, const do
         t += tc;
     }
     return VI_OK;
+}
+
+// Densities along a trajectory (include/vinterp.h): K2t.  The hull pass and the coefficient preparation of vi_eval_f64 (all R
+// rows prepared once into m->d_coef), then one launch: k_track_sph_fast for the orders of vi_eval_f64's fast list, the per-lane
+// kernels for every other order, VINTERP_EVAL=generic and the RBF model.  fp64 chains whatever vi_model_set_eval_precision set.
+extern "C" int vi_eval_track_f64(vi_model* m, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt,
+                                 const int32_t* d_rec, const double* d_w, int64_t R, const double* d_C, const double* d_hull_eq,
+                                 int32_t F, double hull_tol, double* d_out)
+{
+    VI_REQUIRE(m && d_lat && d_lon && d_alt && d_rec && d_out, "null argument");
+    VI_REQUIRE(Q >= 0 && R >= 0 && F >= 0, "negative size");
+    VI_REQUIRE(R == 0 || d_C, "record count given without coefficients");
+    VI_REQUIRE(R <= 0x7fffffffLL, "more records than a 32-bit record index");
+    VI_REQUIRE(Q <= (int64_t)TRACK_BLOCK * 0x7fffffffLL, "more points than one launch takes");
+    VI_REQUIRE(F == 0 || d_hull_eq, "hull facet count given without facet equations");
+    if (Q == 0) return VI_OK;
+    VI_HIP(hipSetDevice(m->ctx->device));
+    const int N = m->N;
+    const bool sph = m->kind == VI_MODEL_SPHHARMLAG;
+    if (F > 0) {
+        const int rc = hull_pass(m, Q, d_lat, d_lon, d_alt, d_hull_eq, F, hull_tol);
+        if (rc != VI_OK) return rc;
+    }
+    const unsigned char* d_mask = F > 0 ? m->d_mask : nullptr;
+    const int Ri = (int)R;
+    if (!sph) {
+        EvalTimer timer(m->ctx);
+        const dim3 grid(nblocks(Q, BLOCK)), block(BLOCK);
+        if (d_w)
+            hipLaunchKernelGGL(k_track_rbf<true>, grid, block, 0, m->ctx->stream, m->rbf, Q, d_lat, d_lon, d_alt, d_rec, d_w, Ri, d_C,
+                               d_mask, (int)F, d_out);
+        else
+            hipLaunchKernelGGL(k_track_rbf<false>, grid, block, 0, m->ctx->stream, m->rbf, Q, d_lat, d_lon, d_alt, d_rec, d_w, Ri, d_C,
+                               d_mask, (int)F, d_out);
+        VI_HIP(hipGetLastError());
+        return VI_OK;
+    }
+    const int L = m->sph.maxl, K = m->sph.maxk;
+    if (R > 0) {                // (no record: every point is NaN, no kernel reads a row)
+        const size_t need = (size_t)R * N * sizeof(double);
+        if (need > m->coef_bytes) {
+            if (m->d_coef) VI_HIP(hipFree(m->d_coef));
+            m->d_coef = nullptr;
+            m->coef_bytes = 0;
+            VI_HIP(hipMalloc((void**)&m->d_coef, need));
+            m->coef_bytes = need;
+        }
+        hipLaunchKernelGGL(k_prep_coef, dim3(nblocks(R * N, 256)), dim3(256), 0, m->ctx->stream, Ri, K, L * L, d_C, m->sph.scale,
+                           m->d_coef);
+        VI_HIP(hipGetLastError());
+    }
+    const double* coef = m->d_coef;
+    EvalTimer timer(m->ctx);
+    if (use_fast_eval() && m->sph.ngroups == 1 && (size_t)(m->nvmax0 + 1) * L * 8 + (size_t)TRACK_TT * N * 8 < 60 * 1024) {
+#define VI_TRACK_FAST(LL, KK) \
+    if (L == LL && K == KK) return launch_track_sph_fast<LL, KK>(m, Q, d_lat, d_lon, d_alt, d_rec, d_w, Ri, coef, d_mask, F, d_out)
+        VI_TRACK_FAST(6, 4);
+        VI_TRACK_FAST(2, 8);
+        VI_TRACK_FAST(3, 4);
+        VI_TRACK_FAST(4, 3);
+        VI_TRACK_FAST(3, 2);
+        VI_TRACK_FAST(12, 2);
+        VI_TRACK_FAST(12, 8);
+#undef VI_TRACK_FAST
+    }
+    if (L <= 6 && K <= 4) return launch_track_sph<6, 4>(m, Q, d_lat, d_lon, d_alt, d_rec, d_w, Ri, coef, d_mask, F, d_out);
+    if (L <= 12 && K <= 8) return launch_track_sph<12, 8>(m, Q, d_lat, d_lon, d_alt, d_rec, d_w, Ri, coef, d_mask, F, d_out);
+    if (L <= 24 && K <= 16) return launch_track_sph<24, 16>(m, Q, d_lat, d_lon, d_alt, d_rec, d_w, Ri, coef, d_mask, F, d_out);
+    vi_set_error("vi_eval_track_f64: order MAXL=%d MAXK=%d beyond the compiled limits (24, 16)", L, K);
+    return VI_ERR_UNSUPPORTED;
 }

@@ -65,6 +65,90 @@ def ravel_points(gdlat, gdlon, gdalt):
     return lat, lon, alt
 
 
+OUT_OF_RANGE = 'Requested time out of range of data file.'        # estimate.py:219
+
+
+def unix_seconds(times):
+    """float64 unix seconds of naive-UTC datetimes (the expression of get_C, estimate.py:196) or of numbers, shape kept."""
+    a = np.asarray(times)
+    if a.dtype != object:
+        return a.astype(np.float64)
+    epoch = dt.datetime(1970, 1, 1)
+    flat = [(t - epoch).total_seconds() for t in a.ravel()]
+    return np.array(flat, dtype=np.float64).reshape(a.shape)
+
+
+def _select_literal(mt, t0, timetol, timeinterp, rec, ok, idx):
+    """select_records for the elements idx of the raveled t0 by the literal rule of get_C, a slab of elements at a time."""
+    slab = max(1, (1 << 20) // max(1, mt.size))
+    for s in range(0, idx.size, slab):
+        k = idx[s:s + slab]
+        t = t0[k][:, None]
+        if timeinterp:
+            hit = (t >= mt[None, :-1]) & (t < mt[None, 1:])             # estimate.py:204
+            rec[k] = np.argmax(hit, axis=1) if hit.shape[1] else 0      # the first i
+            ok[k] = hit.any(axis=1)
+        else:
+            d = np.abs(mt[None, :] - t)                                 # estimate.py:212
+            i = np.argmin(d, axis=1)                                    # the first minimum
+            rec[k] = i
+            ok[k] = ~(d[np.arange(k.size), i] > timetol)                # estimate.py:213
+
+
+def select_records(time, t0, timetol=60., timeinterp=False, outside='raise'):
+    """The record Estimate.get_C (estimate.py:180-221) selects, for every element of t0 at once.
+
+    time: the (R, 2) /UnixTime array; t0: float64 unix seconds of any shape.  Returns (rec, w): rec int32 of the shape of t0 and
+    w float64 of that shape, or None without timeinterp.  Nearest mode: rec = argmin |mt - t0| over the record mid-times mt
+    (the first minimum), out of range where that distance exceeds timetol.  With timeinterp: rec = the first i with
+    mt[i] <= t0 < mt[i+1] and w = (t0 - mt[i]) / (mt[i+1] - mt[i]), so that (1 - w) * Coeffs[rec] + w * Coeffs[rec + 1] is
+    get_C's row bit for bit; out of range where no such i exists (t0 == mt[-1] included, as in the reference).  Any `time`
+    array: mid-times that repeat or do not increase take the literal rule, strictly increasing ones a binary search.
+    outside='raise': ValueError with the reference's message if any element is out of range; 'nan': rec = -1 (and w = 0) there."""
+    if outside not in ('raise', 'nan'):
+        raise ValueError("outside must be 'raise' or 'nan', not %r" % (outside,))
+    mt = np.mean(np.asarray(time), axis=1)
+    t0 = np.asarray(t0, dtype=np.float64)
+    shape = t0.shape
+    t0 = t0.ravel()
+    R = mt.size
+    rec = np.zeros(t0.size, dtype=np.int64)
+    ok = np.zeros(t0.size, dtype=bool)
+    if R == 0:
+        pass                                            # no record: every time is out of range
+    elif R > 1 and np.all(mt[1:] > mt[:-1]):
+        hi = np.searchsorted(mt, t0, side='right')      # mt[hi - 1] <= t0 < mt[hi]; NaN sorts past the end
+        if timeinterp:
+            rec[:] = hi - 1
+            ok[:] = (hi >= 1) & (hi <= R - 1)
+            rec[~ok] = 0
+        else:
+            # the nearest of the two neighbours, the lower one on a tie; the distances |mt - t0| as get_C forms them do not
+            # decrease away from t0, so that one is the first minimum unless the record below it ties with it in floating
+            # point (or t0 is NaN): those elements take the literal rule
+            a, b = np.clip(hi - 1, 0, R - 1), np.clip(hi, 0, R - 1)
+            da, db = np.abs(mt[a] - t0), np.abs(mt[b] - t0)
+            rec[:] = np.where(da <= db, a, b)
+            d = np.abs(mt[rec] - t0)
+            ok[:] = ~(d > timetol)
+            below = np.abs(mt[np.maximum(rec - 1, 0)] - t0)
+            sure = (d == d) & ((rec == 0) | (below > d))
+            _select_literal(mt, t0, timetol, timeinterp, rec, ok, np.flatnonzero(~sure))
+    else:
+        _select_literal(mt, t0, timetol, timeinterp, rec, ok, np.arange(t0.size))
+    if not ok.all():
+        if outside == 'raise':
+            raise ValueError(OUT_OF_RANGE)
+        rec[~ok] = -1
+    w = None
+    if timeinterp:
+        w = np.zeros(t0.size)
+        i = rec[ok]
+        w[ok] = (t0[ok] - mt[i]) / (mt[i + 1] - mt[i])                # estimate.py:206
+        w = w.reshape(shape)
+    return rec.astype(np.int32).reshape(shape), w
+
+
 GRADIENT_FRAMES = {'model': _lib.VI_FRAME_MODEL, 'enu': _lib.VI_FRAME_ENU}
 PEAK_KINDS = {'max': 0, 'min': 1}                 # vi_eval_resident_peak_f64's kind
 REDUCED_BASES = 8                                  # reduced bases a ResidentGrid keeps (evaluate_integrals), oldest out
@@ -207,6 +291,63 @@ class Estimate(object):
             if check_hull:
                 out[~self.check_hull(lat, lon, alt)] = np.nan
         return out, lat, lon, alt
+
+    def select_records(self, times, outside='raise'):
+        """(rec, w) of select_records for `times` - naive-UTC datetimes or float unix seconds, any shape - with this
+        Estimate's records, timetol and timeinterp: what get_C selects for each of them."""
+        return select_records(self.time, unix_seconds(times), self.timetol, self.timeinterp, outside)
+
+    def track(self, times, gdlat, gdlon, gdalt, check_hull=True, outside='raise', out=None):
+        """Densities along a trajectory: element q is what self(times[q], gdlat[q], gdlon[q], gdalt[q], check_hull=check_hull)
+        returns - the record of get_C per point (nearest within timetol, or with timeinterp the blend of the two neighbours),
+        NaN outside the hull and where a record the point needs holds a NaN - in ONE library call for all points
+        (vi_eval_track_f64) instead of one __call__ per record of a satellite pass, another radar's gates or a series of
+        profiles.  times: naive-UTC datetimes or float unix seconds, of the shape of gdlat or one value for all points.
+        outside='raise': a time out of range of the file raises as get_C does; 'nan': those points are NaN.  Same shape as
+        gdlat; `out`: optional C-contiguous float64 array of that shape to write into."""
+        lat, lon, alt = ravel_points(gdlat, gdlon, gdalt)
+        shape, Q = np.shape(gdlat), lat.size
+        t0 = unix_seconds(times)
+        if t0.ndim and t0.shape != shape:
+            raise ValueError('times must be one value or have the shape of gdlat')
+        if out is None:
+            out = np.empty(shape, dtype=np.float64)
+        elif not isinstance(out, np.ndarray) or out.shape != shape or out.dtype != np.float64 or not out.flags.c_contiguous:
+            raise ValueError('out must be a C-contiguous float64 array of shape (%s)' % ', '.join('%d' % n for n in shape))
+        if Q == 0:
+            return out
+        rec, w = self.select_records(np.broadcast_to(t0, shape).ravel(), outside)
+        order = np.argsort(rec, kind='stable')          # the kernel's cost grows with the span of records in 64 points
+        if check_hull:
+            eq, tol = self._hull()
+        else:
+            eq, tol = None, 0.
+        ctx = self.model.ctx
+        bufs = []                                       # freed whatever happens
+        try:
+            for a in (lat[order], lon[order], alt[order]):
+                bufs.append(ctx.to_device(a))
+            bufs.append(ctx.to_device(rec[order], np.int32))
+            dw = dh = None
+            if w is not None:
+                dw = ctx.to_device(w[order])
+                bufs.append(dw)
+            dC = ctx.to_device(np.ascontiguousarray(self.Coeffs, dtype=np.float64))
+            bufs.append(dC)
+            if eq is not None:
+                dh = ctx.to_device(eq)
+                bufs.append(dh)
+            dO = ctx.empty(Q)
+            bufs.append(dO)
+            _lib.check(_lib.lib.vi_eval_track_f64(self.model.handle(), Q, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, bufs[3].ptr,
+                                                  dw.ptr if dw is not None else None, self.Coeffs.shape[0], dC.ptr,
+                                                  dh.ptr if dh is not None else None, 0 if eq is None else eq.shape[0], tol,
+                                                  dO.ptr), 'vi_eval_track_f64')
+            out.reshape(-1)[order] = dO.download()
+        finally:
+            for a in bufs:
+                a.free()
+        return out
 
     # estimate.py:153-178 (boolean mask, same shape as the inputs)
     def check_hull(self, lat0, lon0, alt0):
