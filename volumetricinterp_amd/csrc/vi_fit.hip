@@ -460,6 +460,7 @@ namespace {
 // record's numbers is therefore issued in groups of exactly GEMM_GROUP matrices through the pointer-array interface;
 // the last group is padded with repeats of its last entry whose results go to a scratch area.
 constexpr int GEMM_GROUP = 32;
+constexpr int64_t GRID_YZ_MAX = 65535;          // largest gridDim.y / gridDim.z of a launch
 
 // out[i] = base + min(i, count - 1) * stride   (i < countp; inputs)          or, with scratch != nullptr (outputs),
 // out[i] = i < count ? base + i * stride : scratch + (i - count) * sstride
@@ -552,7 +553,11 @@ extern "C" int vi_normal_eq_f64(vi_ctx* c, int64_t T, int64_t P, int32_t N, cons
     VI_HIP(hipSetDevice(c->device));
     const size_t per_t = (size_t)N * P * sizeof(double);
     const int NN = N * N;
-    const int64_t Tc = chunk_size((size_t)1 << 30, per_t, T);      // <= 1 GiB of scaled copies at a time
+    // <= 1 GiB of scaled copies at a time, and no more records than k_scale_rows' gridDim.z holds (whole product groups): small
+    // records (N P <= 2048) reached 65 536 within the byte budget and the launch was refused.  A record's numbers do not depend
+    // on the chunk it falls in.
+    int64_t Tc = chunk_size((size_t)1 << 30, per_t, T);
+    if (Tc > GRID_YZ_MAX / GEMM_GROUP * GEMM_GROUP) Tc = GRID_YZ_MAX / GEMM_GROUP * GEMM_GROUP;
     double *Bs, *scratch;
     const double **pA, **pB, **pC;
     int rc = ws_carve(c, [&](ws_carver& w) {
@@ -573,9 +578,13 @@ extern "C" int vi_normal_eq_f64(vi_ctx* c, int64_t T, int64_t P, int32_t N, cons
         return gemm_groups(c, rocblas_operation_transpose, rocblas_operation_none, N, N, (int)P, pA, (int)P, pB, (int)P, pC, N, tc);
     });
     if (rc != VI_OK) return rc;
-    hipLaunchKernelGGL(k_atwb<256>, dim3(N, nblk(T, 8)), dim3(256), 0, c->stream, P, N, T, d_At, d_W, d_b, d_y);
-    VI_HIP(hipGetLastError());
-    return VI_OK;
+    // k_atwb takes 8 records per block of gridDim.y: slices of 8 x 65 535 records
+    return for_chunks(T, 8 * GRID_YZ_MAX, [&](int64_t t0, int64_t tc) -> int {
+        hipLaunchKernelGGL(k_atwb<256>, dim3(N, nblk(tc, 8)), dim3(256), 0, c->stream, P, N, tc, d_At, d_W + t0 * P, d_b + t0 * P,
+                           d_y + t0 * N);
+        VI_HIP(hipGetLastError());
+        return VI_OK;
+    });
 }
 
 extern "C" int vi_form_system_f64(vi_ctx* c, int64_t B, int32_t N, const double* d_AWA, const int32_t* d_rec,
