@@ -239,6 +239,63 @@ def test_raw_abi_point_order_and_rows_outside(tag, timeinterp):
     assert np.isfinite(srt[hit]).any()                  # (some of them were numbers before)
 
 
+def _raw_eval(es, lat, lon, alt, C, eq, tol):
+    """vi_eval_f64 of the rows C at the points, masked by the facet equations eq (None: no hull test): (T, Q) host array."""
+    from volumetricinterp_amd import _lib
+    ctx = es.model.ctx
+    bufs = [ctx.to_device(a) for a in (lat, lon, alt, C)] + [ctx.empty((C.shape[0], lat.size))]
+    try:
+        dh = None
+        if eq is not None:
+            dh = ctx.to_device(eq)
+            bufs.append(dh)
+        _lib.check(_lib.lib.vi_eval_f64(es.model.handle(), lat.size, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, C.shape[0], bufs[3].ptr,
+                                        dh.ptr if dh is not None else None, 0 if eq is None else eq.shape[0], tol, bufs[4].ptr),
+                   'vi_eval_f64')
+        return bufs[4].download()
+    finally:
+        for a in bufs:
+            a.free()
+
+
+@pytest.mark.parametrize('tag', ['default', 'k8l2'])
+def test_raw_abi_buffers_regrow_on_one_handle(tag):
+    """The model's grow-only buffers (hull, mask, prepared coefficients) through grow, shrink, grow on ONE handle: vi_eval_f64 at
+    (Q, T, F) = (300, 3, all facets), (5000, 53, all facets) - the dispatch walks 53 as 32 + 16 + 4 + 1, every tile width on the
+    freshly grown coefficient buffer; 300 is no multiple of 256 -, (300, 3, the first half of the facets: fewer facets bound a
+    larger convex region), vi_eval_track_f64 with 257 points, 40 records, blending and the full hull, and vi_eval_f64 at
+    (300, 3, no hull).  Every result has the NaNs and the bits of the same call on a fresh model."""
+    eq, tol = _estimate(tag, True)._hull()
+    F = eq.shape[0]
+    C53 = _records(tag, 53)[1]
+    one = _estimate(tag, True)
+    mt = _mid(one.time)
+
+    def evaluate(Q, T, eqs):
+        lat, lon, alt = _box(np.random.default_rng(Q + T), Q)
+        return lambda es: _raw_eval(es, lat, lon, alt, C53[:T], eqs, tol if eqs is not None else 0.)
+
+    def track(Q):
+        lat, lon, alt = _box(np.random.default_rng(Q), Q)
+        rec, w = one.select_records(np.random.default_rng(Q + 1).uniform(mt[0], mt[-1], Q))
+        assert w is not None and one.Coeffs.shape[0] == R
+        return lambda es: _raw(es, lat, lon, alt, rec, w)
+
+    steps = [('eval 300 x 3, all facets', evaluate(300, 3, eq)), ('eval 5000 x 53, all facets', evaluate(5000, 53, eq)),
+             ('eval 300 x 3, half the facets', evaluate(300, 3, np.ascontiguousarray(eq[:F // 2]))),
+             ('track 257, blending, all facets', track(257)), ('eval 300 x 3, no hull', evaluate(300, 3, None))]
+    got = {}
+    for what, call in steps:
+        out, fresh = call(one), call(_estimate(tag, True))
+        assert np.array_equal(np.isnan(out), np.isnan(fresh)), what
+        ok = ~np.isnan(fresh)
+        assert ok.any() and _same_bits(out[ok], fresh[ok]), what
+        got[what] = ok
+    full, half = got['eval 300 x 3, all facets'], got['eval 300 x 3, half the facets']
+    assert 0 < full.sum() < full.size and np.all(half[full]) and got['eval 300 x 3, no hull'].all()
+    assert 0 < got['eval 5000 x 53, all facets'].sum() < 5000 * 53
+
+
 @pytest.mark.parametrize('timeinterp', [False, True])
 def test_track_failed_fit(timeinterp):
     """Record 17 all NaN (a failed fit).  Nearest mode: exactly its points are NaN, and the points of records 16 and 18, which

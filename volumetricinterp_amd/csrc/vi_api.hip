@@ -402,19 +402,6 @@ extern "C" int vi_model_create(vi_ctx* c, const vi_model_desc* d, vi_model** out
 // per call).  The grid is processed in chunks: the coordinates of chunk c+1 go up on the context's stream while the
 // densities of chunk c come down on a second stream, so the two directions of the link overlap - fully when the caller's
 // arrays are page-locked (vi_host_alloc), as far as the runtime's own staging allows when they are pageable.
-namespace {
-int grow(double** p, size_t* have, size_t need)
-{
-    if (need <= *have) return VI_OK;
-    if (*p) VI_HIP(hipFree(*p));
-    *p = nullptr;
-    *have = 0;
-    VI_HIP(hipMalloc((void**)p, need));
-    *have = need;
-    return VI_OK;
-}
-}  // namespace
-
 extern "C" int vi_eval_f64_host(vi_model* m, int64_t Q, const double* h_lat, const double* h_lon, const double* h_alt,
                                 int64_t T, const double* h_C, const double* h_hull_eq, int32_t F, double hull_tol,
                                 double* h_out)
@@ -432,10 +419,10 @@ extern "C" int vi_eval_f64_host(vi_model* m, int64_t Q, const double* h_lat, con
     const int64_t nchunk = (Q + chunk - 1) / chunk;
     VI_HIP(hipStreamSynchronize(c->stream));          // nothing of an earlier call may still use the staging buffers
     int rc = VI_OK;
-    if ((rc = grow(&m->h_din, &m->h_din_bytes, (size_t)2 * 3 * chunk * sizeof(double))) != VI_OK) return rc;
-    if ((rc = grow(&m->h_dC, &m->h_dC_bytes, (size_t)T * m->N * sizeof(double))) != VI_OK) return rc;
-    if ((rc = grow(&m->h_dout, &m->h_dout_bytes, (size_t)2 * T * chunk * sizeof(double))) != VI_OK) return rc;
-    if (F > 0 && (rc = grow(&m->h_dhull, &m->h_dhull_bytes, (size_t)F * 4 * sizeof(double))) != VI_OK) return rc;
+    if ((rc = vi_grow(c, &m->h_din, &m->h_din_bytes, (size_t)2 * 3 * chunk * sizeof(double))) != VI_OK) return rc;
+    if ((rc = vi_grow(c, &m->h_dC, &m->h_dC_bytes, (size_t)T * m->N * sizeof(double))) != VI_OK) return rc;
+    if ((rc = vi_grow(c, &m->h_dout, &m->h_dout_bytes, (size_t)2 * T * chunk * sizeof(double))) != VI_OK) return rc;
+    if (F > 0 && (rc = vi_grow(c, &m->h_dhull, &m->h_dhull_bytes, (size_t)F * 4 * sizeof(double))) != VI_OK) return rc;
     if (!m->h_stream2) {
         VI_HIP(hipStreamCreateWithFlags(&m->h_stream2, hipStreamNonBlocking));
         for (int i = 0; i < 2; ++i) VI_HIP(hipEventCreateWithFlags(&m->h_ev[i], hipEventDisableTiming));

@@ -1269,9 +1269,6 @@ __global__ void k_transform_rbf(int64_t P, const double* __restrict__ lat, const
     geodetic2ecef(lat[p], lon[p], alt[p], X[p], Y[p], Z[p]);
 }
 
-inline unsigned nblocks(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
-
-// (LCAP, KCAP) instantiations: default order; C5 order; larger orders
 template <int LCAP, int KCAP>
 int launch_basis_sph(vi_model* m, int64_t P, const double* lat, const double* lon, const double* alt, double* A,
                      int64_t ld_p, int64_t ld_n)
@@ -1287,31 +1284,18 @@ int launch_eval_sph(vi_model* m, int64_t Q, const double* lat, const double* lon
                     const double* Cp, const unsigned char* hull, int F, double tol, double* out)
 {
     const int N = m->N;
-    int64_t t = 0;
-    while (t < T) {
-        const int64_t left = T - t;
-        if (left >= 4) {
-            hipLaunchKernelGGL((k_eval_sph<LCAP, KCAP, 4>), dim3(nblocks(Q, BLOCK)), dim3(BLOCK), 0, m->ctx->stream,
-                               m->sph, Q, lat, lon, alt, 4, Cp + t * N, hull, F, tol, out + t * Q);
-            t += 4;
-        } else {
-            hipLaunchKernelGGL((k_eval_sph<LCAP, KCAP, 1>), dim3(nblocks(Q, BLOCK)), dim3(BLOCK), 0, m->ctx->stream,
-                               m->sph, Q, lat, lon, alt, 1, Cp + t * N, hull, F, tol, out + t * Q);
-            t += 1;
-        }
-        VI_HIP(hipGetLastError());
-    }
-    return VI_OK;
+    return for_tiles<4, 1>(T, [&](auto w, int64_t t) {
+        hipLaunchKernelGGL((k_eval_sph<LCAP, KCAP, w>), dim3(nblocks(Q, BLOCK)), dim3(BLOCK), 0, m->ctx->stream, m->sph, Q, lat,
+                           lon, alt, (int)w, Cp + t * N, hull, F, tol, out + t * Q);
+    });
 }
-
 
 template <int L, int K, typename CT>
 int launch_eval_sph_fast(vi_model* m, int64_t Q, const double* lat, const double* lon, const double* alt, int64_t T,
                          const double* Cp, const unsigned char* hull, int F, double tol, double* out)
 {
     const int N = m->N;
-    const int nj = m->nvmax0 + 1;
-    auto shm = [&](int TT) { return (size_t)(((nj * L + 1) & ~1) + TT * N) * sizeof(double) + L * sizeof(int) + 16; };
+    auto shm = [&](int TT) { return chain_lds_bytes(m->nvmax0 + 1, L, (size_t)TT * N); };
     // per call, not cached: the attribute is per device and several device contexts may live in one process
     VI_HIP(hipFuncSetAttribute((const void*)k_eval_sph_fast<L, K, 16, CT>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
     VI_HIP(hipFuncSetAttribute((const void*)k_eval_sph_fast<L, K, 4, CT>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
@@ -1321,24 +1305,10 @@ int launch_eval_sph_fast(vi_model* m, int64_t Q, const double* lat, const double
     // point-timesteps/s for tiles of 1 / 4 / 16 (a tile of 8 is slower than 16).  Whole tiles of 16 timesteps normally
     // never get here: vi_eval_mfma.hip contracts them on the matrix cores (1.2e11).
     const bool wide_ok = shm(16) <= 60 * 1024;
-    int64_t t = 0;
-    while (t < T) {
-        if (wide_ok && T - t >= 16) {
-            hipLaunchKernelGGL((k_eval_sph_fast<L, K, 16, CT>), dim3(nblocks(Q, BLOCK)), dim3(BLOCK), shm(16), m->ctx->stream,
-                               m->sph, Q, lat, lon, alt, 16, Cp + t * N, hull, F, tol, out + t * Q);
-            t += 16;
-        } else if (T - t >= 4) {
-            hipLaunchKernelGGL((k_eval_sph_fast<L, K, 4, CT>), dim3(nblocks(Q, BLOCK)), dim3(BLOCK), shm(4), m->ctx->stream,
-                               m->sph, Q, lat, lon, alt, 4, Cp + t * N, hull, F, tol, out + t * Q);
-            t += 4;
-        } else {
-            hipLaunchKernelGGL((k_eval_sph_fast<L, K, 1, CT>), dim3(nblocks(Q, BLOCK)), dim3(BLOCK), shm(1), m->ctx->stream,
-                               m->sph, Q, lat, lon, alt, 1, Cp + t * N, hull, F, tol, out + t * Q);
-            t += 1;
-        }
-        VI_HIP(hipGetLastError());
-    }
-    return VI_OK;
+    return for_tiles<16, 4, 1>(T, [&](int w) { return w < 16 || wide_ok; }, [&](auto w, int64_t t) {
+        hipLaunchKernelGGL((k_eval_sph_fast<L, K, w, CT>), dim3(nblocks(Q, BLOCK)), dim3(BLOCK), shm(w), m->ctx->stream, m->sph,
+                           Q, lat, lon, alt, (int)w, Cp + t * N, hull, F, tol, out + t * Q);
+    });
 }
 
 // K2t launches (vi_eval_track_f64): w == nullptr is nearest mode.  Cp: the R prepared rows.
@@ -1346,37 +1316,27 @@ template <int L, int K>
 int launch_track_sph_fast(vi_model* m, int64_t Q, const double* lat, const double* lon, const double* alt, const int* rec,
                           const double* w, int R, const double* Cp, const unsigned char* hull, int F, double* out)
 {
-    const int nj = m->nvmax0 + 1;
-    const size_t shm = (size_t)(((nj * L + 1) & ~1) + TRACK_TT * m->N) * sizeof(double) + L * sizeof(int) + 16;
-    const dim3 grid(nblocks(Q, TRACK_BLOCK)), block(TRACK_BLOCK);
-    if (w) {
-        VI_HIP(hipFuncSetAttribute((const void*)k_track_sph_fast<L, K, TRACK_TT, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    const size_t shm = chain_lds_bytes(m->nvmax0 + 1, L, (size_t)TRACK_TT * m->N);
+    return with_flag(w != nullptr, [&](auto interp) -> int {
+        VI_HIP(hipFuncSetAttribute((const void*)k_track_sph_fast<L, K, TRACK_TT, interp>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                    64 * 1024));
-        hipLaunchKernelGGL((k_track_sph_fast<L, K, TRACK_TT, true>), grid, block, shm, m->ctx->stream, m->sph, Q, lat, lon, alt,
-                           rec, w, R, Cp, hull, F, out);
-    } else {
-        VI_HIP(hipFuncSetAttribute((const void*)k_track_sph_fast<L, K, TRACK_TT, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   64 * 1024));
-        hipLaunchKernelGGL((k_track_sph_fast<L, K, TRACK_TT, false>), grid, block, shm, m->ctx->stream, m->sph, Q, lat, lon, alt,
-                           rec, w, R, Cp, hull, F, out);
-    }
-    VI_HIP(hipGetLastError());
-    return VI_OK;
+        hipLaunchKernelGGL((k_track_sph_fast<L, K, TRACK_TT, interp>), dim3(nblocks(Q, TRACK_BLOCK)), dim3(TRACK_BLOCK), shm,
+                           m->ctx->stream, m->sph, Q, lat, lon, alt, rec, w, R, Cp, hull, F, out);
+        VI_HIP(hipGetLastError());
+        return VI_OK;
+    });
 }
 
 template <int LCAP, int KCAP>
 int launch_track_sph(vi_model* m, int64_t Q, const double* lat, const double* lon, const double* alt, const int* rec,
                      const double* w, int R, const double* Cp, const unsigned char* hull, int F, double* out)
 {
-    const dim3 grid(nblocks(Q, BLOCK)), block(BLOCK);
-    if (w)
-        hipLaunchKernelGGL((k_track_sph<LCAP, KCAP, true>), grid, block, 0, m->ctx->stream, m->sph, Q, lat, lon, alt, rec, w, R, Cp,
-                           hull, F, out);
-    else
-        hipLaunchKernelGGL((k_track_sph<LCAP, KCAP, false>), grid, block, 0, m->ctx->stream, m->sph, Q, lat, lon, alt, rec, w, R, Cp,
-                           hull, F, out);
-    VI_HIP(hipGetLastError());
-    return VI_OK;
+    return with_flag(w != nullptr, [&](auto interp) -> int {
+        hipLaunchKernelGGL((k_track_sph<LCAP, KCAP, interp>), dim3(nblocks(Q, BLOCK)), dim3(BLOCK), 0, m->ctx->stream, m->sph, Q,
+                           lat, lon, alt, rec, w, R, Cp, hull, F, out);
+        VI_HIP(hipGetLastError());
+        return VI_OK;
+    });
 }
 
 // records HIP events around the evaluation kernel launches of one vi_eval_f64 call (see vi_eval_kernel_ms)
@@ -1392,13 +1352,39 @@ struct EvalTimer {
     }
 };
 
-}  // namespace
-namespace {
-
 bool use_fast_eval()
 {
     static const bool generic = vi_env_is("VINTERP_EVAL", "generic");
     return !generic;
+}
+
+// The orders (MAXL, MAXK) the tiled kernels k_eval_sph_fast and k_track_sph_fast are compiled at: X(L, K) for each.  The first
+// two are the orders of the fp32-chain tolerance sweep (vi_model_set_eval_precision), the only ones compiled with float chains.
+#define VI_FAST_ORDERS_F32(X) X(6, 4) X(2, 8)
+#define VI_FAST_ORDERS(X) VI_FAST_ORDERS_F32(X) X(3, 4) X(4, 3) X(3, 2) X(12, 2) X(12, 8)
+
+// Whether a model of one of those orders runs the tiled kernels at a tile of TT timesteps: one degree group, and table plus
+// tile within 60 KB of LDS.  The test is coarser than chain_lds_bytes - it counts neither the padding, the L ints nor the spare
+// 16 bytes - and is not replaced by it, because it decides the route: at (2, 8), (3, 4) and (3, 2) with nvmax0 = 3774, 2510 and
+// 2534 it admits a model whose exact size is 61 448 / 61 452 bytes (the launchers allow 64 KB), which the exact size turns away.
+bool fast_eval_fits(const vi_model* m, int TT)
+{
+    return use_fast_eval() && m->sph.ngroups == 1 &&
+           (size_t)(m->nvmax0 + 1) * m->sph.maxl * 8 + (size_t)TT * m->N * 8 < 60 * 1024;
+}
+
+// The per-lane kernels (k_basis_sph, k_eval_sph, k_track_sph) are compiled at three caps (LCAP, KCAP): the default order, the
+// C5 order, larger orders.  f(integral_constant LCAP, KCAP) at the first cap that holds the model's order.
+template <class F>
+int at_order_cap(const vi_model* m, const char* who, F&& f)
+{
+    const int L = m->sph.maxl, K = m->sph.maxk;
+#define VI_CAP(LC, KC) \
+    if (L <= LC && K <= KC) return f(std::integral_constant<int, LC>{}, std::integral_constant<int, KC>{});
+    VI_CAP(6, 4) VI_CAP(12, 8) VI_CAP(24, 16)
+#undef VI_CAP
+    vi_set_error("%s: order MAXL=%d MAXK=%d beyond the compiled limits (24, 16)", who, L, K);
+    return VI_ERR_UNSUPPORTED;
 }
 
 }  // namespace
@@ -1411,14 +1397,10 @@ extern "C" int vi_basis_f64(vi_model* m, int64_t P, const double* d_lat, const d
     VI_REQUIRE(P >= 0, "negative point count");
     if (P == 0) return VI_OK;
     VI_HIP(hipSetDevice(m->ctx->device));
-    if (m->kind == VI_MODEL_SPHHARMLAG) {
-        const int L = m->sph.maxl, K = m->sph.maxk;
-        if (L <= 6 && K <= 4) return launch_basis_sph<6, 4>(m, P, d_lat, d_lon, d_alt, d_A, ld_p, ld_n);
-        if (L <= 12 && K <= 8) return launch_basis_sph<12, 8>(m, P, d_lat, d_lon, d_alt, d_A, ld_p, ld_n);
-        if (L <= 24 && K <= 16) return launch_basis_sph<24, 16>(m, P, d_lat, d_lon, d_alt, d_A, ld_p, ld_n);
-        vi_set_error("vi_basis_f64: order MAXL=%d MAXK=%d beyond the compiled limits (24, 16)", L, K);
-        return VI_ERR_UNSUPPORTED;
-    }
+    if (m->kind == VI_MODEL_SPHHARMLAG)
+        return at_order_cap(m, "vi_basis_f64", [&](auto lc, auto kc) {
+            return launch_basis_sph<lc, kc>(m, P, d_lat, d_lon, d_alt, d_A, ld_p, ld_n);
+        });
     hipLaunchKernelGGL(k_basis_rbf, dim3(nblocks(P, BLOCK)), dim3(BLOCK), 0, m->ctx->stream, m->rbf, P, d_lat, d_lon,
                        d_alt, d_A, ld_p, ld_n);
     VI_HIP(hipGetLastError());
@@ -1583,31 +1565,33 @@ void launch_hull_mask(vi_model* m, int64_t Q, const double* d_lat, const double*
 }  // namespace
 
 namespace {
-// m->d_mask[q] <- 1 where point q passes the hull test of the F facet equations, else 0 (grows the model's hull buffer and mask)
-int hull_pass(vi_model* m, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt, const double* d_hull_eq,
-              int32_t F, double hull_tol)
+// Gets a call ready, the one routine that does: grows the model's hull, mask and coefficient buffers; builds the hull buffer from
+// the F facet equations and m->d_coef from the `rows` coefficient rows of d_C (sphharmlag only: the RBF kernels read d_C as
+// it is, their callers pass rows = 0) - in one launch where the call has both -; then, with F > 0, m->d_mask[q] <- 1 where point
+// q passes the hull test, else 0.
+int prepare_call(vi_model* m, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt, const double* d_hull_eq,
+                 int32_t F, double hull_tol, int64_t rows, const double* d_C)
 {
-    const size_t need = hull_buf_bytes((size_t)F);
-    if (need > m->hull_bytes) {
-        VI_HIP(hipStreamSynchronize(m->ctx->stream));
-        if (m->d_hull) VI_HIP(hipFree(m->d_hull));
-        m->d_hull = nullptr;
-        m->hull_bytes = 0;
-        VI_HIP(hipMalloc((void**)&m->d_hull, need));
-        m->hull_bytes = need;
-    }
-    hipLaunchKernelGGL(k_prep_hull, dim3(HULL_PREP_BLOCKS), dim3(256), 0, m->ctx->stream, (int)F, d_hull_eq, m->d_hull);
+    vi_ctx* c = m->ctx;
+    const int N = m->N, K = m->sph.maxk, L2 = m->sph.maxl * m->sph.maxl;
+    int rc = VI_OK;
+    if (F > 0 && (rc = vi_grow(c, &m->d_hull, &m->hull_bytes, hull_buf_bytes((size_t)F))) != VI_OK) return rc;
+    if (F > 0 && (rc = vi_grow(c, &m->d_mask, &m->mask_bytes, (size_t)Q)) != VI_OK) return rc;
+    if (rows > 0 && (rc = vi_grow(c, &m->d_coef, &m->coef_bytes, (size_t)rows * N * sizeof(double))) != VI_OK) return rc;
+    const unsigned coef_blocks = nblocks(rows * N, 256);
+    if (F == 0 && rows == 0) return VI_OK;             // nothing to prepare, nothing launched
+    if (F > 0 && rows > 0)
+        hipLaunchKernelGGL(k_prep_hull_coef, dim3(HULL_PREP_BLOCKS + coef_blocks), dim3(256), 0, c->stream, (int)F, d_hull_eq,
+                           m->d_hull, (int)rows, K, L2, d_C, m->sph.scale, m->d_coef);
+    else if (F > 0)
+        hipLaunchKernelGGL(k_prep_hull, dim3(HULL_PREP_BLOCKS), dim3(256), 0, c->stream, (int)F, d_hull_eq, m->d_hull);
+    else if (rows > 0)
+        hipLaunchKernelGGL(k_prep_coef, dim3(coef_blocks), dim3(256), 0, c->stream, (int)rows, K, L2, d_C, m->sph.scale, m->d_coef);
     VI_HIP(hipGetLastError());
-    if ((size_t)Q > m->mask_bytes) {
-        VI_HIP(hipStreamSynchronize(m->ctx->stream));
-        if (m->d_mask) VI_HIP(hipFree(m->d_mask));
-        m->d_mask = nullptr;
-        m->mask_bytes = 0;
-        VI_HIP(hipMalloc((void**)&m->d_mask, (size_t)Q));
-        m->mask_bytes = (size_t)Q;
+    if (F > 0) {
+        launch_hull_mask(m, Q, d_lat, d_lon, d_alt, (int)F, hull_tol);
+        VI_HIP(hipGetLastError());
     }
-    launch_hull_mask(m, Q, d_lat, d_lon, d_alt, (int)F, hull_tol);
-    VI_HIP(hipGetLastError());
     return VI_OK;
 }
 }  // namespace
@@ -1621,7 +1605,7 @@ extern "C" int vi_eval_basis_f64(vi_model* m, int64_t Q, const double* d_lat, co
     if (Q == 0) return VI_OK;
     int rc = vi_basis_f64(m, Q, d_lat, d_lon, d_alt, d_Y, 1, Q);
     if (rc != VI_OK || F == 0) return rc;
-    rc = hull_pass(m, Q, d_lat, d_lon, d_alt, d_hull_eq, F, hull_tol);
+    rc = prepare_call(m, Q, d_lat, d_lon, d_alt, d_hull_eq, F, hull_tol, 0, nullptr);
     if (rc != VI_OK) return rc;
     hipLaunchKernelGGL(k_mask_basis, dim3(nblocks(Q, 256)), dim3(256), 0, m->ctx->stream, Q, m->N, m->d_mask, d_Y);
     VI_HIP(hipGetLastError());
@@ -1641,7 +1625,7 @@ extern "C" int vi_eval_grad_basis_f64(vi_model* m, int64_t Q, const double* d_la
     VI_REQUIRE(frame == VI_FRAME_MODEL || frame == VI_FRAME_ENU, "frame must be VI_FRAME_MODEL or VI_FRAME_ENU");
     if (Q > 0 && F > 0 && m->kind == VI_MODEL_SPHHARMLAG) {          // (the launcher refuses the other model)
         VI_HIP(hipSetDevice(m->ctx->device));
-        const int rc = hull_pass(m, Q, d_lat, d_lon, d_alt, d_hull_eq, F, hull_tol);
+        const int rc = prepare_call(m, Q, d_lat, d_lon, d_alt, d_hull_eq, F, hull_tol, 0, nullptr);
         if (rc != VI_OK) return rc;
     }
     const unsigned char* d_mask = F > 0 ? m->d_mask : nullptr;
@@ -1806,57 +1790,16 @@ extern "C" int vi_eval_f64(vi_model* m, int64_t Q, const double* d_lat, const do
     VI_HIP(hipSetDevice(m->ctx->device));
     const int N = m->N;
     const bool sph = m->kind == VI_MODEL_SPHHARMLAG;
-    if (sph) {
-        const size_t need = (size_t)T * N * sizeof(double);
-        if (need > m->coef_bytes) {
-            if (m->d_coef) VI_HIP(hipFree(m->d_coef));
-            m->d_coef = nullptr;
-            m->coef_bytes = 0;
-            VI_HIP(hipMalloc((void**)&m->d_coef, need));
-            m->coef_bytes = need;
-        }
-    }
-    const int L2 = sph ? m->sph.maxl * m->sph.maxl : 0;
-    if (F > 0) {
-        const size_t need = hull_buf_bytes((size_t)F);
-        if (need > m->hull_bytes) {
-            VI_HIP(hipStreamSynchronize(m->ctx->stream));
-            if (m->d_hull) VI_HIP(hipFree(m->d_hull));
-            m->d_hull = nullptr;
-            m->hull_bytes = 0;
-            VI_HIP(hipMalloc((void**)&m->d_hull, need));
-            m->hull_bytes = need;
-        }
-        if (sph)            // the hull buffer and the coefficients of the call in one launch
-            hipLaunchKernelGGL(k_prep_hull_coef, dim3(HULL_PREP_BLOCKS + nblocks((int64_t)T * N, 256)), dim3(256), 0, m->ctx->stream,
-                               (int)F, d_hull_eq, m->d_hull, (int)T, m->sph.maxk, L2, d_C, m->sph.scale, m->d_coef);
-        else
-            hipLaunchKernelGGL(k_prep_hull, dim3(HULL_PREP_BLOCKS), dim3(256), 0, m->ctx->stream, (int)F, d_hull_eq, m->d_hull);
-        VI_HIP(hipGetLastError());
-        if ((size_t)Q > m->mask_bytes) {
-            VI_HIP(hipStreamSynchronize(m->ctx->stream));
-            if (m->d_mask) VI_HIP(hipFree(m->d_mask));
-            m->d_mask = nullptr;
-            m->mask_bytes = 0;
-            VI_HIP(hipMalloc((void**)&m->d_mask, (size_t)Q));
-            m->mask_bytes = (size_t)Q;
-        }
-        launch_hull_mask(m, Q, d_lat, d_lon, d_alt, (int)F, hull_tol);
-        VI_HIP(hipGetLastError());
-    }
+    int rc = prepare_call(m, Q, d_lat, d_lon, d_alt, d_hull_eq, F, hull_tol, sph ? T : 0, d_C);
+    if (rc != VI_OK) return rc;
     const unsigned char* d_mask = F > 0 ? m->d_mask : nullptr;
+    EvalTimer timer(m->ctx);
     if (sph) {
-        if (F == 0) {
-            hipLaunchKernelGGL(k_prep_coef, dim3(nblocks((int64_t)T * N, 256)), dim3(256), 0, m->ctx->stream, (int)T,
-                               m->sph.maxk, L2, d_C, m->sph.scale, m->d_coef);
-            VI_HIP(hipGetLastError());
-        }
         const int L = m->sph.maxl, K = m->sph.maxk;
-        EvalTimer timer(m->ctx);
         // whole tiles of 16 timesteps go to the matrix-core kernel (vi_eval_mfma.hip); the rest to the VALU kernels
         int64_t done = 0;
         if (use_fast_eval() && !m->chain_f32) {
-            const int rc = vi_eval_sph_mfma(m, Q, d_lat, d_lon, d_alt, T, m->d_coef, d_mask, (int)F, d_out, &done);
+            rc = vi_eval_sph_mfma(m, Q, d_lat, d_lon, d_alt, T, m->d_coef, d_mask, (int)F, d_out, &done);
             if (rc != VI_OK) return rc;
             if (done == T) return VI_OK;
         }
@@ -1865,55 +1808,35 @@ extern "C" int vi_eval_f64(vi_model* m, int64_t Q, const double* d_lat, const do
         double* outp = d_out + done * Q;
         if (use_fast_eval()) {                  // high orders: the chains in groups (vi_eval_split.hip)
             int handled = 0;
-            const int rc = vi_eval_sph_split(m, Q, d_lat, d_lon, d_alt, Tr, coef, d_mask, (int)F, outp, &handled);
+            rc = vi_eval_sph_split(m, Q, d_lat, d_lon, d_alt, Tr, coef, d_mask, (int)F, outp, &handled);
             if (rc != VI_OK || handled) return rc;
         }
-        if (use_fast_eval() && m->sph.ngroups == 1 && (size_t)(m->nvmax0 + 1) * L * 8 + (size_t)4 * N * 8 < 60 * 1024) {
+        if (fast_eval_fits(m, 4)) {
+#define VI_FAST(CT, LL, KK) \
+    if (L == LL && K == KK) return launch_eval_sph_fast<LL, KK, CT>(m, Q, d_lat, d_lon, d_alt, Tr, coef, d_mask, F, hull_tol, outp);
+#define VI_FAST_F32(LL, KK) VI_FAST(float, LL, KK)
+#define VI_FAST_F64(LL, KK) VI_FAST(double, LL, KK)
             if (m->chain_f32) {     // fp32 Legendre chains (vi_model_set_eval_precision): the orders of the tolerance sweep
-                if (L == 6 && K == 4) return launch_eval_sph_fast<6, 4, float>(m, Q, d_lat, d_lon, d_alt, Tr, coef, d_mask, F, hull_tol, outp);
-                if (L == 2 && K == 8) return launch_eval_sph_fast<2, 8, float>(m, Q, d_lat, d_lon, d_alt, Tr, coef, d_mask, F, hull_tol, outp);
+                VI_FAST_ORDERS_F32(VI_FAST_F32)
                 vi_set_error("vi_eval_f64: no fp32-chain kernel for MAXL=%d MAXK=%d", L, K);
                 return VI_ERR_UNSUPPORTED;
             }
-#define VI_FAST(LL, KK) \
-    if (L == LL && K == KK) return launch_eval_sph_fast<LL, KK, double>(m, Q, d_lat, d_lon, d_alt, Tr, coef, d_mask, F, hull_tol, outp)
-            VI_FAST(6, 4);
-            VI_FAST(2, 8);
-            VI_FAST(3, 4);
-            VI_FAST(4, 3);
-            VI_FAST(3, 2);
-            VI_FAST(12, 2);
-            VI_FAST(12, 8);
+            VI_FAST_ORDERS(VI_FAST_F64)
+#undef VI_FAST_F64
+#undef VI_FAST_F32
 #undef VI_FAST
         }
-        if (L <= 6 && K <= 4)
-            return launch_eval_sph<6, 4>(m, Q, d_lat, d_lon, d_alt, Tr, coef, d_mask, F, hull_tol, outp);
-        if (L <= 12 && K <= 8)
-            return launch_eval_sph<12, 8>(m, Q, d_lat, d_lon, d_alt, Tr, coef, d_mask, F, hull_tol, outp);
-        if (L <= 24 && K <= 16)
-            return launch_eval_sph<24, 16>(m, Q, d_lat, d_lon, d_alt, Tr, coef, d_mask, F, hull_tol, outp);
-        vi_set_error("vi_eval_f64: order MAXL=%d MAXK=%d beyond the compiled limits (24, 16)", L, K);
-        return VI_ERR_UNSUPPORTED;
+        return at_order_cap(m, "vi_eval_f64", [&](auto lc, auto kc) {
+            return launch_eval_sph<lc, kc>(m, Q, d_lat, d_lon, d_alt, Tr, coef, d_mask, F, hull_tol, outp);
+        });
     }
-    EvalTimer timer(m->ctx);
-    int64_t t = 0;
     // the exponential of a (point, centre) pair is the cost (~20 of the ~28 fp64 operations per pair): it is computed once per
     // tile of timesteps, so the tile is as wide as the registers allow (16 accumulators; a tile of 4 recomputed every
     // exponential four times for 16 timesteps: 10.7 ms instead of 3.4 at 1000 centres x 128^3 points)
-    while (t < T) {
-        const int64_t left = T - t;
-        const int tc = left >= 16 ? 16 : left >= 4 ? 4 : 1;
-#define VI_RBF(TT)                                                                                                        \
-    hipLaunchKernelGGL(k_eval_rbf<TT>, dim3(nblocks(Q, BLOCK)), dim3(BLOCK), 0, m->ctx->stream, m->rbf, Q, d_lat, d_lon, \
-                       d_alt, TT, d_C + t * N, d_mask, F, hull_tol, d_out + t * Q)
-        if (tc == 16) VI_RBF(16);
-        else if (tc == 4) VI_RBF(4);
-        else VI_RBF(1);
-#undef VI_RBF
-        VI_HIP(hipGetLastError());
-        t += tc;
-    }
-    return VI_OK;
+    return for_tiles<16, 4, 1>(T, [&](auto w, int64_t t) {
+        hipLaunchKernelGGL(k_eval_rbf<w>, dim3(nblocks(Q, BLOCK)), dim3(BLOCK), 0, m->ctx->stream, m->rbf, Q, d_lat, d_lon, d_alt,
+                           (int)w, d_C + t * N, d_mask, F, hull_tol, d_out + t * Q);
+    });
 }
 
 // Densities along a trajectory (include/vinterp.h): K2t.  The hull pass and the coefficient preparation of vi_eval_f64 (all R
@@ -1931,57 +1854,29 @@ extern "C" int vi_eval_track_f64(vi_model* m, int64_t Q, const double* d_lat, co
     VI_REQUIRE(F == 0 || d_hull_eq, "hull facet count given without facet equations");
     if (Q == 0) return VI_OK;
     VI_HIP(hipSetDevice(m->ctx->device));
-    const int N = m->N;
     const bool sph = m->kind == VI_MODEL_SPHHARMLAG;
-    if (F > 0) {
-        const int rc = hull_pass(m, Q, d_lat, d_lon, d_alt, d_hull_eq, F, hull_tol);
-        if (rc != VI_OK) return rc;
-    }
+    // (R = 0 prepares no coefficients: every point is NaN, no kernel reads a row)
+    const int rc = prepare_call(m, Q, d_lat, d_lon, d_alt, d_hull_eq, F, hull_tol, sph ? R : 0, d_C);
+    if (rc != VI_OK) return rc;
     const unsigned char* d_mask = F > 0 ? m->d_mask : nullptr;
     const int Ri = (int)R;
-    if (!sph) {
-        EvalTimer timer(m->ctx);
-        const dim3 grid(nblocks(Q, BLOCK)), block(BLOCK);
-        if (d_w)
-            hipLaunchKernelGGL(k_track_rbf<true>, grid, block, 0, m->ctx->stream, m->rbf, Q, d_lat, d_lon, d_alt, d_rec, d_w, Ri, d_C,
-                               d_mask, (int)F, d_out);
-        else
-            hipLaunchKernelGGL(k_track_rbf<false>, grid, block, 0, m->ctx->stream, m->rbf, Q, d_lat, d_lon, d_alt, d_rec, d_w, Ri, d_C,
-                               d_mask, (int)F, d_out);
-        VI_HIP(hipGetLastError());
-        return VI_OK;
-    }
-    const int L = m->sph.maxl, K = m->sph.maxk;
-    if (R > 0) {                // (no record: every point is NaN, no kernel reads a row)
-        const size_t need = (size_t)R * N * sizeof(double);
-        if (need > m->coef_bytes) {
-            if (m->d_coef) VI_HIP(hipFree(m->d_coef));
-            m->d_coef = nullptr;
-            m->coef_bytes = 0;
-            VI_HIP(hipMalloc((void**)&m->d_coef, need));
-            m->coef_bytes = need;
-        }
-        hipLaunchKernelGGL(k_prep_coef, dim3(nblocks(R * N, 256)), dim3(256), 0, m->ctx->stream, Ri, K, L * L, d_C, m->sph.scale,
-                           m->d_coef);
-        VI_HIP(hipGetLastError());
-    }
-    const double* coef = m->d_coef;
     EvalTimer timer(m->ctx);
-    if (use_fast_eval() && m->sph.ngroups == 1 && (size_t)(m->nvmax0 + 1) * L * 8 + (size_t)TRACK_TT * N * 8 < 60 * 1024) {
+    if (!sph)
+        return with_flag(d_w != nullptr, [&](auto interp) -> int {
+            hipLaunchKernelGGL(k_track_rbf<interp>, dim3(nblocks(Q, BLOCK)), dim3(BLOCK), 0, m->ctx->stream, m->rbf, Q, d_lat, d_lon,
+                               d_alt, d_rec, d_w, Ri, d_C, d_mask, (int)F, d_out);
+            VI_HIP(hipGetLastError());
+            return VI_OK;
+        });
+    const int L = m->sph.maxl, K = m->sph.maxk;
+    const double* coef = m->d_coef;
+    if (fast_eval_fits(m, TRACK_TT)) {
 #define VI_TRACK_FAST(LL, KK) \
-    if (L == LL && K == KK) return launch_track_sph_fast<LL, KK>(m, Q, d_lat, d_lon, d_alt, d_rec, d_w, Ri, coef, d_mask, F, d_out)
-        VI_TRACK_FAST(6, 4);
-        VI_TRACK_FAST(2, 8);
-        VI_TRACK_FAST(3, 4);
-        VI_TRACK_FAST(4, 3);
-        VI_TRACK_FAST(3, 2);
-        VI_TRACK_FAST(12, 2);
-        VI_TRACK_FAST(12, 8);
+    if (L == LL && K == KK) return launch_track_sph_fast<LL, KK>(m, Q, d_lat, d_lon, d_alt, d_rec, d_w, Ri, coef, d_mask, F, d_out);
+        VI_FAST_ORDERS(VI_TRACK_FAST)
 #undef VI_TRACK_FAST
     }
-    if (L <= 6 && K <= 4) return launch_track_sph<6, 4>(m, Q, d_lat, d_lon, d_alt, d_rec, d_w, Ri, coef, d_mask, F, d_out);
-    if (L <= 12 && K <= 8) return launch_track_sph<12, 8>(m, Q, d_lat, d_lon, d_alt, d_rec, d_w, Ri, coef, d_mask, F, d_out);
-    if (L <= 24 && K <= 16) return launch_track_sph<24, 16>(m, Q, d_lat, d_lon, d_alt, d_rec, d_w, Ri, coef, d_mask, F, d_out);
-    vi_set_error("vi_eval_track_f64: order MAXL=%d MAXK=%d beyond the compiled limits (24, 16)", L, K);
-    return VI_ERR_UNSUPPORTED;
+    return at_order_cap(m, "vi_eval_track_f64", [&](auto lc, auto kc) {
+        return launch_track_sph<lc, kc>(m, Q, d_lat, d_lon, d_alt, d_rec, d_w, Ri, coef, d_mask, F, d_out);
+    });
 }

@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/vinterp.h"
@@ -75,6 +76,21 @@ struct vi_ctx {
 
 int vi_ctx_workspace(vi_ctx* ctx, size_t bytes, void** out);
 
+// A grow-only device buffer (p, *have bytes) made to hold `need` bytes.  Growing drains the context's stream before the old
+// block is freed: a kernel of an earlier call may still be reading it.
+template <class T>
+int vi_grow(vi_ctx* ctx, T** p, size_t* have, size_t need)
+{
+    if (need <= *have) return VI_OK;
+    VI_HIP(hipStreamSynchronize(ctx->stream));
+    if (*p) VI_HIP(hipFree(*p));
+    *p = nullptr;
+    *have = 0;
+    VI_HIP(hipMalloc((void**)p, need));
+    *have = need;
+    return VI_OK;
+}
+
 // Carves consecutive arrays out of one allocation.  On a null base it only counts: ws_carve below runs a layout on both.
 struct ws_carver {
     char* base;
@@ -120,6 +136,35 @@ int for_chunks(int64_t B, int64_t Bc, F&& f)
         if (rc != VI_OK) return rc;
     }
     return VI_OK;
+}
+
+inline unsigned nblocks(int64_t n, int64_t b) { return (unsigned)((n + b - 1) / b); }
+
+// T timesteps in tiles of the widths W..., given widest first and ending in 1: launch(integral_constant<int, w>, t0) for the
+// first width w that what is left fills and that ok(w) admits (ok(1) must hold), then the launch check, until all are done
+template <int... W, class OK, class F>
+int for_tiles(int64_t T, OK&& ok, F&& launch)
+{
+    for (int64_t t = 0; t < T;) {
+        const int64_t t0 = t;
+        // one term per width, in the order given: a term that launches also advances t and yields true, which ends the fold
+        (void)((T - t0 >= W && ok(W) ? (launch(std::integral_constant<int, W>{}, t0), t += W, true) : false) || ...);
+        VI_REQUIRE(t > t0, "no admissible tile width");
+        VI_HIP(hipGetLastError());
+    }
+    return VI_OK;
+}
+template <int... W, class F>
+int for_tiles(int64_t T, F&& launch)
+{
+    return for_tiles<W...>(T, [](int) { return true; }, launch);
+}
+
+// f(std::true_type) or f(std::false_type): a run-time flag as the template argument of a kernel
+template <class F>
+int with_flag(bool b, F&& f)
+{
+    return b ? f(std::true_type{}) : f(std::false_type{});
 }
 
 // The VINTERP_* switches.  A switch is read once per process into a function-local `static const` where it is used: the
@@ -190,3 +235,11 @@ struct vi_model {
     hipEvent_t h_ev[2] = {nullptr, nullptr};
     hipEvent_t h_evdown[2] = {nullptr, nullptr};   // "the download out of staging slot s has finished" (h_stream2)
 };
+
+// Dynamic LDS of the kernels that run the Legendre chains out of LDS (k_eval_sph_fast, k_track_sph_fast, k_eval_sph_split,
+// k_eval_sph_mfma), which all lay it out as [nj x L recurrence table, padded to an even count of doubles | coefficient tile of
+// tile_doubles | L ints: the degree each chain segment ends at | 16 bytes spare], nj = nvmax0 + 1
+inline size_t chain_lds_bytes(int nj, int L, size_t tile_doubles)
+{
+    return ((size_t)((nj * L + 1) & ~1) + tile_doubles) * sizeof(double) + L * sizeof(int) + 16;
+}

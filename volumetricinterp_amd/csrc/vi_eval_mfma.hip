@@ -283,20 +283,24 @@ __global__ __launch_bounds__(MBLOCK, (NT >= 2 ? 2 : 1)) void k_eval_sph_mfma(Sph
     }
 }
 
-inline unsigned nblocks64(int64_t n, int64_t b) { return (unsigned)((n + b - 1) / b); }
+// the LDS of k_eval_sph_mfma<L, KQ, NT>: the coefficient image is NT x L^2 x KQ x 64 doubles
+template <int L, int KQ>
+size_t mfma_lds_bytes(const vi_model* m, int NT)
+{
+    return chain_lds_bytes(m->nvmax0 + 1, L, (size_t)NT * L * L * KQ * 64);
+}
 
 template <int L, int KQ, int NT>
 int launch_tile(vi_model* m, int64_t Q, const double* lat, const double* lon, const double* alt, int tcount,
                 const double* Cp, const unsigned char* hull, int F, double* out)
 {
-    const int nj = m->nvmax0 + 1;
-    const size_t shm = (size_t)(((nj * L + 1) & ~1) + NT * L * L * KQ * 64) * sizeof(double) + L * sizeof(int) + 16;
+    const size_t shm = mfma_lds_bytes<L, KQ>(m, NT);
     // per call, not cached: the attribute is per device and several device contexts may live in one process
     VI_HIP(hipFuncSetAttribute((const void*)k_eval_sph_mfma<L, KQ, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
     // points per workgroup: enough groups of 256 to amortise the coefficient image, yet >= ~8 workgroups per CU
     int ngrp = 8;
     while (ngrp > 1 && (Q + MBLOCK * ngrp - 1) / (MBLOCK * ngrp) < (int64_t)8 * m->ctx->n_cu) ngrp >>= 1;
-    hipLaunchKernelGGL((k_eval_sph_mfma<L, KQ, NT>), dim3(nblocks64(Q, (int64_t)MBLOCK * ngrp)), dim3(MBLOCK), shm,
+    hipLaunchKernelGGL((k_eval_sph_mfma<L, KQ, NT>), dim3(nblocks(Q, (int64_t)MBLOCK * ngrp)), dim3(MBLOCK), shm,
                        m->ctx->stream, m->sph, Q, lat, lon, alt, tcount, Cp, hull, F, ngrp, out);
     VI_HIP(hipGetLastError());
     return VI_OK;
@@ -307,10 +311,7 @@ int launch_mfma(vi_model* m, int64_t Q, const double* lat, const double* lon, co
                 const double* Cp, const unsigned char* hull, int F, double* out, int64_t* done)
 {
     const int N = m->N;
-    const int nj = m->nvmax0 + 1;
-    auto fits = [&](int NT) {
-        return (size_t)(((nj * L + 1) & ~1) + NT * L * L * KQ * 64) * sizeof(double) + L * sizeof(int) + 16 <= 80 * 1024;
-    };
+    auto fits = [&](int NT) { return mfma_lds_bytes<L, KQ>(m, NT) <= 80 * 1024; };
     int64_t t = 0;
     static const int ntmax = vi_env_int("VINTERP_MFMA_NT", 2);          // experiment switch: widest timestep tile (in units of 16)
     while (T - t >= 16) {

@@ -217,34 +217,21 @@ __global__ __launch_bounds__(BLOCK) void k_eval_sph_split(SphDev M, int64_t Q, c
     }
 }
 
-inline unsigned nblocks_s(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
-
 template <int L, int K, int NH, typename CT>
 int launch_split(vi_model* m, int64_t Q, const double* lat, const double* lon, const double* alt, int64_t T,
                  const double* Cp, const unsigned char* hull, int F, double* out)
 {
     const int N = m->N;
-    const int nj = m->nvmax0 + 1;
-    auto shm = [&](int TT) { return (size_t)(((nj * L + 1) & ~1) + TT * N) * sizeof(double) + L * sizeof(int) + 16; };
+    auto shm = [&](int TT) { return chain_lds_bytes(m->nvmax0 + 1, L, (size_t)TT * N); };
     // per call, not cached: the attribute is per device and several device contexts may live in one process
     VI_HIP(hipFuncSetAttribute((const void*)k_eval_sph_split<L, K, 4, NH, CT>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                64 * 1024));
     VI_HIP(hipFuncSetAttribute((const void*)k_eval_sph_split<L, K, 1, NH, CT>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                64 * 1024));
-    int64_t t = 0;
-    while (t < T) {
-        if (T - t >= 4 && shm(4) <= 60 * 1024) {
-            hipLaunchKernelGGL((k_eval_sph_split<L, K, 4, NH, CT>), dim3(nblocks_s(Q, BLOCK)), dim3(BLOCK), shm(4), m->ctx->stream,
-                               m->sph, Q, lat, lon, alt, 4, Cp + t * N, hull, F, out + t * Q);
-            t += 4;
-        } else {
-            hipLaunchKernelGGL((k_eval_sph_split<L, K, 1, NH, CT>), dim3(nblocks_s(Q, BLOCK)), dim3(BLOCK), shm(1), m->ctx->stream,
-                               m->sph, Q, lat, lon, alt, 1, Cp + t * N, hull, F, out + t * Q);
-            t += 1;
-        }
-        VI_HIP(hipGetLastError());
-    }
-    return VI_OK;
+    return for_tiles<4, 1>(T, [&](int w) { return w == 1 || shm(w) <= 60 * 1024; }, [&](auto w, int64_t t) {
+        hipLaunchKernelGGL((k_eval_sph_split<L, K, w, NH, CT>), dim3(nblocks(Q, BLOCK)), dim3(BLOCK), shm(w), m->ctx->stream, m->sph,
+                           Q, lat, lon, alt, (int)w, Cp + t * N, hull, F, out + t * Q);
+    });
 }
 
 }  // namespace
@@ -258,8 +245,7 @@ int vi_eval_sph_split(vi_model* m, int64_t Q, const double* lat, const double* l
     static const bool off = vi_env_is("VINTERP_EVAL_SPLIT", "0");
     if (off || m->sph.ngroups != 1) return VI_OK;
     const int L = m->sph.maxl, K = m->sph.maxk;
-    const int nj = m->nvmax0 + 1;
-    if ((size_t)(((nj * L + 1) & ~1) + m->N) * sizeof(double) + 64 > 60 * 1024) return VI_OK;
+    if (chain_lds_bytes(m->nvmax0 + 1, L, m->N) > 60 * 1024) return VI_OK;
     int rc = VI_OK;
     static const int nh = vi_env_int("VINTERP_SPLIT_NH", 3);
     // measured at MAXK 8 x MAXL 12, 128^3 points: 1.93 ms with all twelve chains at once (k_eval_sph_fast), 1.13 ms in two
