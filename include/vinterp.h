@@ -167,6 +167,26 @@ int  vi_eval_f64(vi_model* model, int64_t Q, const double* d_lat, const double* 
 int  vi_eval_track_f64(vi_model* model, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt,
                        const int32_t* d_rec, const double* d_w, int64_t R, const double* d_C,
                        const double* d_hull_eq, int32_t F, double hull_tol, double* d_out);
+/* Line integrals of the fitted parameter along straight rays that each carry their OWN time (slant TEC between a receiver and a
+ * satellite, an occultation link, an optical column): one call for all rays.  d_a, d_b: start and end of the P rays in ECEF
+ * metres, planar (3 x P: X of all rays, then Y, then Z); d_rec, d_w, R, d_C select and blend the coefficient rows as in
+ * vi_eval_track_f64 (d_w == NULL: nearest mode; the blend is formed on the rows, as get_C does, as written: a NaN in either
+ * row of the pair gives NaN at any d_w).  (d_x, d_wq): a quadrature rule of n >= 1 nodes on [-1, 1].
+ *   d_out[p] = (s1 - s0) / 2 * |b - a| * sum_i d_wq[i] * f(a + s_i (b - a)),   s_i = s0 + (s1 - s0) (1 + d_x[i]) / 2
+ * in the parameter's unit times metres, with [s0, s1] the part of [0, 1] where the segment is inside the hull - ONE interval,
+ * the hull being convex: the segment clipped against the F half-spaces hull_eq[f][0..2] . x + hull_eq[f][3] <= hull_tol in
+ * fp64, straight from hull_eq (a segment whose two ends are inside keeps [0, 1] exactly) - or [0, 1] with F = 0.
+ * d_chord (or NULL): 2 x P doubles, s0 of all rays, then s1; geometry only, written for a ray without a record too.
+ * NaN - d_out, and the chord - where the segment does not enter the hull (not s0 < s1) and where an end point is not finite;
+ * NaN d_out where d_rec[p] < 0 or a row the ray needs is >= R (R = 0: every ray), and where such a row holds a NaN.  A segment
+ * of length zero inside the hull gives 0.  A wave integrates a ray, 64 nodes per pass, and adds the nodes in a fixed order: a
+ * ray's bits depend on the ray, its row(s) and the rule, not on the other rays or their order - no sorting is needed.
+ * Models and orders as vi_eval_track_f64; the orders of vi_eval_f64's fast kernels run K2l's tiled form (csrc/vi_basis.hip),
+ * other orders, VINTERP_EVAL=generic and the RBF model the per-lane forms (correct, not tuned).  fp64 chains.  Asynchronous
+ * on the context's stream; timed for vi_eval_kernel_ms like its siblings (tests/test_gpu_slant.py). */
+int  vi_eval_slant_f64(vi_model* model, int64_t P, const double* d_a, const double* d_b, const int32_t* d_rec, const double* d_w,
+                       int64_t R, const double* d_C, const double* d_hull_eq, int32_t F, double hull_tol, int32_t n,
+                       const double* d_x, const double* d_wq, double* d_out, double* d_chord);
 /* Many timesteps on ONE grid (BASELINE configs[3]: a GPU's share of 10 000 timesteps, all on the same 256^3 grid - Estimate.__call__
  * (estimate.py:110-123) once per timestep in the reference, which rebuilds the basis of the grid every time): the basis matrix
  * of the grid is assembled once and kept in HBM, and every batch of timesteps is one matrix product.
@@ -236,7 +256,7 @@ int    vi_reduce_basis_f64(vi_model* model, int64_t outer, int64_t L, int64_t in
  * BASELINE configs[4] sweeps against the 1e-6 tolerance.  Orders with an fp32 kernel: (MAXL, MAXK) = (6,4), (2,8), (12,8);
  * others return VI_ERR_UNSUPPORTED from vi_eval_f64 while the flag is set. */
 int  vi_model_set_eval_precision(vi_model* model, int32_t chain_f32);
-/* device time (ms) of the evaluation kernel launches of the last vi_eval_f64 / vi_eval_track_f64 / vi_eval_resident_f64 /
+/* device time (ms) of the evaluation kernel launches of the last vi_eval_f64 / vi_eval_track_f64 / vi_eval_slant_f64 / vi_eval_resident_f64 /
  * vi_eval_resident_err_f64 / vi_eval_resident_peak_f64 call on this context, from HIP events recorded on the context's stream around them (the preparation kernels are excluded).
  * The events are recorded only while vi_ctx_set_eval_timing(ctx, 1) is in force (default: off - the pair costs a 0.2 ms call about 7 us);
  * vi_eval_kernel_ms fails with VI_ERR_ARG while it is off or before a call has been timed. */

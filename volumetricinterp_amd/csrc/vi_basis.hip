@@ -1132,6 +1132,245 @@ __global__ __launch_bounds__(BLOCK) void k_track_sph(SphDev M, int64_t Q, const 
     if (q < Q) out[q] = live ? val : __builtin_nan("");
 }
 
+// ---------------------------------------------------------------------------------------------
+// K2l: line integrals along straight rays, every ray at its own time (vi_eval_slant_f64).  Ray p runs from a_p to b_p (ECEF);
+// the part of it inside the hull is ONE interval [s0, s1] of the segment parameter (the hull is convex, its facets half-spaces),
+// and the integral is the caller's rule on [-1, 1] mapped onto that interval:
+//   out[p] = (s1 - s0) / 2 * |b - a| * sum_i wq[i] * f(a + s_i (b - a)),   s_i = s0 + (s1 - s0) (1 + x[i]) / 2.
+// The unit is a WAVE per ray.  The model coordinates are functions of ECEF only (sph_geom_ecef), so the nodes need no geodetic
+// step, and every node of a ray shares the ray's time: the wave needs one coefficient row - in interpolation mode the blend
+// (1 - w) Cp[r] + w Cp[r + 1] of two prepared rows, the preparation being linear - and no window.
+
+// sph_geom (vi_sph_device.h) from its second line on: the model coordinates of an ECEF point.  A function of its own - sph_geom
+// is inlined into the benchmarked kernels and stays as it is.
+__device__ __forceinline__ Geom sph_geom_ecef(const SphDev& M, double X, double Y, double Z)
+{
+    Geom g;
+    g.X = X;
+    g.Y = Y;
+    g.Z = Z;
+    const double kd = M.kx * X + M.ky * Y;
+    const double omc = 1.0 - M.rc;
+    const double Rx = X * M.rc + (M.ky * Z) * M.rs + M.kx * kd * omc;
+    const double Ry = Y * M.rc + (-M.kx * Z) * M.rs + M.ky * kd * omc;
+    const double Rz = Z * M.rc + (M.kx * Y - M.ky * X) * M.rs;
+    const double rho2 = Rx * Rx + Ry * Ry;
+    const double r = sqrt(rho2 + Rz * Rz);
+    g.x = Rz / r;
+    g.s = sqrt(1.0 - g.x * g.x);
+    const double rho = sqrt(rho2);
+    const bool pole = !(rho > 0.0);
+    g.cphi = pole ? 1.0 : Rx / rho;
+    g.sphi = pole ? 0.0 : Ry / rho;
+    g.z = 100.0 * (r / M.RE - 1.0);
+    g.Rx = Rx;
+    g.Ry = Ry;
+    return g;
+}
+
+constexpr int SLANT_WAVES = 4;      // rays (waves) of a workgroup at most; they share the recurrence table of the fast kernel
+
+// a value that is the same in every lane of the wave, moved to scalar registers
+__device__ __forceinline__ double wave_uniform(double v)
+{
+    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+
+// the wave of the workgroup this thread belongs to, as a scalar: what is indexed with it is loaded and kept on the scalar path
+__device__ __forceinline__ int wave_index() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
+
+// What a wave knows about its ray after the prologue: every field is the same in all 64 lanes.
+struct SlantRay {
+    double ax, ay, az, dx, dy, dz;  // a and b - a
+    double s0, s1;                  // the part of the segment inside the hull
+    double len;                     // |b - a|
+    int r;                          // the ray's row
+    bool live;                      // to be integrated: a ray of the launch that enters the hull and whose row(s) exist
+};
+
+// The prologue of every K2l kernel.  Clips the segment against the F half-spaces n_f . x + d_f <= tol straight from the caller's
+// list in fp64, the lanes striding over the facets: with the plane distances ga, gb of the two ends, a facet that has both ends
+// inside does not bound the segment, one with both ends outside (a segment parallel to it and outside among them) is missed by
+// the whole segment, the others bound s from below at (ga - tol) / (ga - gb) or from above at (tol - ga) / (gb - ga); max / min
+// butterflies make [s0, s1] of the lanes' bounds.  A segment with both ends inside the hull keeps [0, 1] exactly.  A miss
+// (not s0 < s1) and non-finite end points give a NaN chord.  Writes the chord - geometry only: a ray without a record has one.
+__device__ __forceinline__ SlantRay slant_ray(int64_t p, int64_t P, const double* __restrict__ a, const double* __restrict__ b,
+                                              const int* __restrict__ rec, int R, int pair, const double* __restrict__ eq, int F,
+                                              double tol, double* __restrict__ chord)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t pc = p < P ? p : P - 1;
+    SlantRay y;
+    y.ax = a[pc];
+    y.ay = a[P + pc];
+    y.az = a[2 * P + pc];
+    const double bx = b[pc], by = b[P + pc], bz = b[2 * P + pc];
+    y.dx = bx - y.ax;
+    y.dy = by - y.ay;
+    y.dz = bz - y.az;
+    y.len = sqrt(y.dx * y.dx + y.dy * y.dy + y.dz * y.dz);
+    double lo = 0.0, hi = 1.0;
+    bool miss = !(fabs(y.ax) + fabs(y.ay) + fabs(y.az) + fabs(bx) + fabs(by) + fabs(bz) < __builtin_inf());
+    for (int f = lane; f < F; f += 64) {
+        const double nx = eq[4 * f], ny = eq[4 * f + 1], nz = eq[4 * f + 2], off = eq[4 * f + 3];
+        const double ga = fma(nx, y.ax, fma(ny, y.ay, fma(nz, y.az, off)));
+        const double gb = fma(nx, bx, fma(ny, by, fma(nz, bz, off)));
+        const bool ina = ga <= tol, inb = gb <= tol;
+        if (!ina && !inb) miss = true;
+        else if (!ina) lo = fmax(lo, (ga - tol) / (ga - gb));
+        else if (!inb) hi = fmin(hi, (tol - ga) / (gb - ga));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        lo = fmax(lo, __shfl_xor(lo, o, 64));
+        hi = fmin(hi, __shfl_xor(hi, o, 64));
+    }
+    lo = wave_uniform(lo);
+    hi = wave_uniform(hi);
+    miss = __any(miss) || !(lo < hi);
+    y.s0 = miss ? __builtin_nan("") : lo;
+    y.s1 = miss ? __builtin_nan("") : hi;
+    if (chord && p < P && lane == 0) {
+        chord[p] = y.s0;
+        chord[P + p] = y.s1;
+    }
+    y.r = rec[pc];
+    y.live = p < P && !miss && y.r >= 0 && y.r <= R - 1 - pair;
+    return y;
+}
+
+// node i of the rule on the ray: the ECEF point, and the weight of the node in metres
+__device__ __forceinline__ void slant_node(const SlantRay& y, double xi, double& X, double& Y, double& Z)
+{
+    const double s = y.s0 + (y.s1 - y.s0) * (0.5 * (1.0 + xi));
+    X = fma(s, y.dx, y.ax);
+    Y = fma(s, y.dy, y.ay);
+    Z = fma(s, y.dz, y.az);
+}
+
+// the epilogue: the lanes' sums added in one fixed order (a butterfly: every lane ends with the same bits), scaled to metres
+__device__ __forceinline__ double slant_sum(const SlantRay& y, double acc)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    return 0.5 * (y.s1 - y.s0) * y.len * acc;
+}
+
+// The orders of the fast list.  A workgroup is `blockDim.x / 64` rays (SLANT_WAVES unless the LDS holds fewer rows beside the
+// table): the recurrence table is staged once for all of them, as k_eval_sph_fast stages it for 256 points, and each wave stages
+// its own row - blended while staging, as written: never a product that would drop a NaN.  ONE barrier, which every wave meets:
+// a dead ray's wave (no record, a miss, rows past R - 1, past the end of the launch) stages zeros instead of a row it must not
+// read, and leaves after the barrier without chain work.  Then ceil(n / 64) passes: lane i of pass k takes node 64 k + i and
+// runs the chains of k_eval_sph_fast at TT = 1 on it; the lanes past n run node 0 again and add nothing.  No atomics: a ray's
+// bits depend on the ray, its row(s) and the rule alone.
+template <int L, int K, bool INTERP>
+__global__ __launch_bounds__(SLANT_WAVES * 64) void k_slant_sph_fast(SphDev M, int64_t P, const double* __restrict__ a,
+                                                                     const double* __restrict__ b, const int* __restrict__ rec,
+                                                                     const double* __restrict__ wgt, int R,
+                                                                     const double* __restrict__ Cp, const double* __restrict__ eq,
+                                                                     int F, double tol, int n, const double* __restrict__ xq,
+                                                                     const double* __restrict__ wq, double* __restrict__ out,
+                                                                     double* __restrict__ chord)
+{
+    constexpr int NB = L * L * K;
+    extern __shared__ __align__(16) double sh[];
+    const int lane = threadIdx.x & 63, wave = wave_index(), waves = blockDim.x >> 6;
+    const int64_t p = (int64_t)blockIdx.x * waves + wave;
+    const SlantRay y = slant_ray(p, P, a, b, rec, R, INTERP ? 1 : 0, eq, F, tol, chord);
+    const SphGroupDev G = M.groups[0];
+    const int nj = G.nvmax + 1;
+    double* shc = sh;                                           // [nj][L] recurrence table
+    double* shC = sh + ((nj * L + 1) & ~1) + wave * NB;         // [waves][NB]: the wave's row
+    int* nvl = reinterpret_cast<int*>(sh + ((nj * L + 1) & ~1) + waves * NB);      // [L]
+    for (int i = threadIdx.x; i < nj * L; i += blockDim.x) shc[i] = G.c[i];
+    for (int j = threadIdx.x; j < nj; j += blockDim.x) {
+        const int l = G.pick[j];
+        if (l >= 0) nvl[l] = j;
+    }
+    if (y.live) {
+        const double* __restrict__ row = Cp + (int64_t)y.r * NB;
+        if (INTERP) {
+            const double w = wgt[p];
+            for (int i = lane; i < NB; i += 64) shC[i] = (1.0 - w) * row[i] + w * row[NB + i];
+        } else {
+            for (int i = lane; i < NB; i += 64) shC[i] = row[i];
+        }
+    } else {
+        for (int i = lane; i < NB; i += 64) shC[i] = 0.0;
+    }
+    __syncthreads();                                            // the only barrier: every wave of the workgroup is here
+    if (!y.live) {
+        if (p < P && lane == 0) out[p] = __builtin_nan("");
+        return;
+    }
+    double acc = 0.0;
+#pragma unroll 1
+    for (int i0 = 0; i0 < n; i0 += 64) {
+        // a pass reads the table and the row as the one-pass kernel does: nothing is carried in registers from pass to pass
+        // (left to hoist the loop-invariant LDS and table reads, the compiler spends 50 VGPRs - a wave per SIMD or two - on them)
+        asm volatile("" ::: "memory");
+        const int i = i0 + lane;
+        const bool on = i < n;
+        double X, Y, Z;
+        slant_node(y, xq[on ? i : 0], X, Y, Z);
+        const Geom g = sph_geom_ecef(M, X, Y, Z);
+        FastEval<L, K, 1> E;
+        E.shC = shC;
+        fast_chains<L, K, 1, double>(E, G, g, shc, nvl, nj);
+        const double term = wq[on ? i : 0] * (exp(-0.5 * g.z) * E.acc[0]);
+        acc += on ? term : 0.0;
+    }
+    const double val = slant_sum(y, acc);
+    if (lane == 0) out[p] = val;
+}
+
+// The per-lane form for the orders without a fast kernel (and VINTERP_EVAL=generic): the same wave per ray, the generic sink
+// reading the ray's prepared row, or its two rows, from global memory (wave-uniform); in interpolation mode the two densities
+// of a node are blended.  No LDS, no barrier: a dead ray's wave leaves at once.  Correct, not tuned.
+template <int LCAP, int KCAP, bool INTERP>
+__global__ __launch_bounds__(BLOCK) void k_slant_sph(SphDev M, int64_t P, const double* __restrict__ a, const double* __restrict__ b,
+                                                     const int* __restrict__ rec, const double* __restrict__ wgt, int R,
+                                                     const double* __restrict__ Cp, const double* __restrict__ eq, int F, double tol,
+                                                     int n, const double* __restrict__ xq, const double* __restrict__ wq,
+                                                     double* __restrict__ out, double* __restrict__ chord)
+{
+    constexpr int TT = INTERP ? 2 : 1;
+    const int lane = threadIdx.x & 63;
+    const int64_t p = (int64_t)blockIdx.x * (BLOCK / 64) + wave_index();
+    const SlantRay y = slant_ray(p, P, a, b, rec, R, TT - 1, eq, F, tol, chord);
+    if (!y.live) {
+        if (p < P && lane == 0) out[p] = __builtin_nan("");
+        return;
+    }
+    const double w = INTERP ? wgt[p] : 0.0;
+    double acc = 0.0;
+#pragma unroll 1
+    for (int i0 = 0; i0 < n; i0 += 64) {
+        const int i = i0 + lane;
+        const bool on = i < n;
+        double X, Y, Z;
+        slant_node(y, xq[on ? i : 0], X, Y, Z);
+        const Geom g = sph_geom_ecef(M, X, Y, Z);
+        EvalSink<KCAP, TT> sink;
+        sink.Cp = Cp + (int64_t)y.r * M.N;
+        sink.maxk = M.maxk;
+        sink.NB = M.N;
+        laguerre<KCAP>(M.maxk, g.z, sink.Lk);
+#pragma unroll
+        for (int t = 0; t < TT; ++t) sink.acc[t] = 0.0;
+        sph_point<LCAP, KCAP>(M, g, sink);
+        const double E = exp(-0.5 * g.z);
+        double val = E * sink.acc[0];
+        if (INTERP) val = (1.0 - w) * val + w * (E * sink.acc[TT - 1]);
+        const double term = wq[on ? i : 0] * val;
+        acc += on ? term : 0.0;
+    }
+    const double val = slant_sum(y, acc);
+    if (lane == 0) out[p] = val;
+}
+
 // Cp[t][r*maxk + k] = C[t][k*L2 + r] * scale[r]
 __device__ __forceinline__ void prep_coef_body(int T, int maxk, int L2, const double* __restrict__ C,
                                                const double* __restrict__ scale, double* __restrict__ Cp, int64_t bid)
@@ -1261,6 +1500,46 @@ __global__ __launch_bounds__(BLOCK) void k_track_rbf(RbfDev M, int64_t Q, const 
     if (q < Q) out[q] = live ? val : __builtin_nan("");
 }
 
+// K2l for the RBF model: a wave per ray, a lane per node, the ray's coefficient row(s) from global memory (see k_slant_sph)
+template <bool INTERP>
+__global__ __launch_bounds__(BLOCK) void k_slant_rbf(RbfDev M, int64_t P, const double* __restrict__ a, const double* __restrict__ b,
+                                                     const int* __restrict__ rec, const double* __restrict__ wgt, int R,
+                                                     const double* __restrict__ C, const double* __restrict__ eq, int F, double tol,
+                                                     int n, const double* __restrict__ xq, const double* __restrict__ wq,
+                                                     double* __restrict__ out, double* __restrict__ chord)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t p = (int64_t)blockIdx.x * (BLOCK / 64) + wave_index();
+    const SlantRay y = slant_ray(p, P, a, b, rec, R, INTERP ? 1 : 0, eq, F, tol, chord);
+    if (!y.live) {
+        if (p < P && lane == 0) out[p] = __builtin_nan("");
+        return;
+    }
+    const double w = INTERP ? wgt[p] : 0.0;
+    const double* __restrict__ c = M.centers;
+    const double* __restrict__ Cr = C + (int64_t)y.r * M.N;
+    double acc = 0.0;
+#pragma unroll 1
+    for (int i0 = 0; i0 < n; i0 += 64) {
+        const int i = i0 + lane;
+        const bool on = i < n;
+        double X, Y, Z;
+        slant_node(y, xq[on ? i : 0], X, Y, Z);
+        double va = 0.0, vb = 0.0;
+        for (int k = 0; k < M.N; ++k) {
+            const double dx = X - c[3 * k], dy = Y - c[3 * k + 1], dz = Z - c[3 * k + 2];
+            const double e = exp(-(dx * dx + dy * dy + dz * dz) * M.inv_eps2);
+            va = fma(e, Cr[k], va);
+            if (INTERP) vb = fma(e, Cr[M.N + k], vb);
+        }
+        const double val = INTERP ? (1.0 - w) * va + w * vb : va;
+        const double term = wq[on ? i : 0] * val;
+        acc += on ? term : 0.0;
+    }
+    const double val = slant_sum(y, acc);
+    if (lane == 0) out[p] = val;
+}
+
 __global__ void k_transform_rbf(int64_t P, const double* __restrict__ lat, const double* __restrict__ lon,
                                 const double* __restrict__ alt, double* X, double* Y, double* Z)
 {
@@ -1334,6 +1613,50 @@ int launch_track_sph(vi_model* m, int64_t Q, const double* lat, const double* lo
     return with_flag(w != nullptr, [&](auto interp) -> int {
         hipLaunchKernelGGL((k_track_sph<LCAP, KCAP, interp>), dim3(nblocks(Q, BLOCK)), dim3(BLOCK), 0, m->ctx->stream, m->sph, Q,
                            lat, lon, alt, rec, w, R, Cp, hull, F, out);
+        VI_HIP(hipGetLastError());
+        return VI_OK;
+    });
+}
+
+// K2l launches (vi_eval_slant_f64): w == nullptr is nearest mode.  Cp: the R prepared rows.
+struct SlantArgs {
+    int64_t P;
+    const double *a, *b;
+    const int* rec;
+    const double* w;
+    int R;
+    const double* eq;
+    int F;
+    double tol;
+    int n;
+    const double *xq, *wq;
+    double *out, *chord;
+};
+
+template <int L, int K>
+int launch_slant_sph_fast(vi_model* m, const SlantArgs& s, const double* Cp)
+{
+    // as many rays in a workgroup as the LDS holds rows beside the table: SLANT_WAVES, fewer at the orders whose table and row
+    // fill most of it (one always fits: fast_eval_fits(m, 1))
+    int waves = SLANT_WAVES;
+    while (waves > 1 && chain_lds_bytes(m->nvmax0 + 1, L, (size_t)waves * m->N) > 64 * 1024) waves >>= 1;
+    const size_t shm = chain_lds_bytes(m->nvmax0 + 1, L, (size_t)waves * m->N);
+    return with_flag(s.w != nullptr, [&](auto interp) -> int {
+        VI_HIP(hipFuncSetAttribute((const void*)k_slant_sph_fast<L, K, interp>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   64 * 1024));
+        hipLaunchKernelGGL((k_slant_sph_fast<L, K, interp>), dim3(nblocks(s.P, waves)), dim3(waves * 64), shm, m->ctx->stream,
+                           m->sph, s.P, s.a, s.b, s.rec, s.w, s.R, Cp, s.eq, s.F, s.tol, s.n, s.xq, s.wq, s.out, s.chord);
+        VI_HIP(hipGetLastError());
+        return VI_OK;
+    });
+}
+
+template <int LCAP, int KCAP>
+int launch_slant_sph(vi_model* m, const SlantArgs& s, const double* Cp)
+{
+    return with_flag(s.w != nullptr, [&](auto interp) -> int {
+        hipLaunchKernelGGL((k_slant_sph<LCAP, KCAP, interp>), dim3(nblocks(s.P, BLOCK / 64)), dim3(BLOCK), 0, m->ctx->stream, m->sph,
+                           s.P, s.a, s.b, s.rec, s.w, s.R, Cp, s.eq, s.F, s.tol, s.n, s.xq, s.wq, s.out, s.chord);
         VI_HIP(hipGetLastError());
         return VI_OK;
     });
@@ -1879,4 +2202,44 @@ extern "C" int vi_eval_track_f64(vi_model* m, int64_t Q, const double* d_lat, co
     return at_order_cap(m, "vi_eval_track_f64", [&](auto lc, auto kc) {
         return launch_track_sph<lc, kc>(m, Q, d_lat, d_lon, d_alt, d_rec, d_w, Ri, coef, d_mask, F, d_out);
     });
+}
+
+// Line integrals along straight rays (include/vinterp.h): K2l.  The coefficient preparation of vi_eval_track_f64 (all R rows
+// prepared once into m->d_coef) and no hull pass - the kernel clips each ray against the caller's facet list itself -, then one
+// launch: k_slant_sph_fast for the orders of vi_eval_f64's fast list, the per-lane kernels for every other order,
+// VINTERP_EVAL=generic and the RBF model.  fp64 chains whatever vi_model_set_eval_precision set.
+extern "C" int vi_eval_slant_f64(vi_model* m, int64_t P, const double* d_a, const double* d_b, const int32_t* d_rec,
+                                 const double* d_w, int64_t R, const double* d_C, const double* d_hull_eq, int32_t F,
+                                 double hull_tol, int32_t n, const double* d_x, const double* d_wq, double* d_out, double* d_chord)
+{
+    VI_REQUIRE(m && d_a && d_b && d_rec && d_x && d_wq && d_out, "null argument");
+    VI_REQUIRE(P >= 0 && R >= 0 && F >= 0, "negative size");
+    VI_REQUIRE(n >= 1, "a rule has at least one node");
+    VI_REQUIRE(R == 0 || d_C, "record count given without coefficients");
+    VI_REQUIRE(R <= 0x7fffffffLL, "more records than a 32-bit record index");
+    VI_REQUIRE(P <= 0x7fffffffLL, "more rays than one launch takes");
+    VI_REQUIRE(F == 0 || d_hull_eq, "hull facet count given without facet equations");
+    if (P == 0) return VI_OK;
+    VI_HIP(hipSetDevice(m->ctx->device));
+    const bool sph = m->kind == VI_MODEL_SPHHARMLAG;
+    // (R = 0 prepares no coefficients: every ray is NaN, no kernel reads a row)
+    const int rc = prepare_call(m, 0, nullptr, nullptr, nullptr, nullptr, 0, 0., sph ? R : 0, d_C);
+    if (rc != VI_OK) return rc;
+    const SlantArgs s{P, d_a, d_b, d_rec, d_w, (int)R, d_hull_eq, (int)F, hull_tol, (int)n, d_x, d_wq, d_out, d_chord};
+    EvalTimer timer(m->ctx);
+    if (!sph)
+        return with_flag(d_w != nullptr, [&](auto interp) -> int {
+            hipLaunchKernelGGL(k_slant_rbf<interp>, dim3(nblocks(P, BLOCK / 64)), dim3(BLOCK), 0, m->ctx->stream, m->rbf, s.P, s.a,
+                               s.b, s.rec, s.w, s.R, d_C, s.eq, s.F, s.tol, s.n, s.xq, s.wq, s.out, s.chord);
+            VI_HIP(hipGetLastError());
+            return VI_OK;
+        });
+    const int L = m->sph.maxl, K = m->sph.maxk;
+    if (fast_eval_fits(m, 1)) {
+#define VI_SLANT_FAST(LL, KK) \
+    if (L == LL && K == KK) return launch_slant_sph_fast<LL, KK>(m, s, m->d_coef);
+        VI_FAST_ORDERS(VI_SLANT_FAST)
+#undef VI_SLANT_FAST
+    }
+    return at_order_cap(m, "vi_eval_slant_f64", [&](auto lc, auto kc) { return launch_slant_sph<lc, kc>(m, s, m->d_coef); });
 }

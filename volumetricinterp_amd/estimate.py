@@ -18,6 +18,7 @@ import numpy as np
 from scipy.spatial import ConvexHull
 
 from . import _lib
+from . import geodesy
 
 
 def hull_equations(hull_vert):
@@ -147,6 +148,63 @@ def select_records(time, t0, timetol=60., timeinterp=False, outside='raise'):
         w[ok] = (t0[ok] - mt[i]) / (mt[i + 1] - mt[i])                # estimate.py:206
         w = w.reshape(shape)
     return rec.astype(np.int32).reshape(shape), w
+
+
+def hull_chords(eq, tol, a, b):
+    """(s0, s1), each (P,): the part [s0, s1] of [0, 1] on which the segment a + s (b - a) lies inside the hull of
+    hull_equations - inside <=> eq[:, :3] @ x + eq[:, 3] <= tol - for (P, 3) end points in ECEF metres.  The hull is convex, so
+    that part is one interval: with the plane distances ga, gb of the two ends, a facet with both ends inside does not bound
+    the segment, one with both ends outside is missed by the whole segment, every other facet bounds s from below at
+    (ga - tol) / (ga - gb) or from above at (tol - ga) / (gb - ga).  Two end points inside give (0, 1) exactly.  (NaN, NaN)
+    for a miss (not s0 < s1) and for non-finite end points.  The host statement of the clip in K2l (vi_eval_slant_f64)."""
+    eq = np.asarray(eq, dtype=np.float64).reshape(-1, 4)
+    a = np.asarray(a, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64)
+    if a.ndim != 2 or a.shape[1] != 3 or a.shape != b.shape:
+        raise ValueError('a and b must both have shape (P, 3)')
+    P = a.shape[0]
+    s0, s1 = np.zeros(P), np.ones(P)
+    miss = ~(np.isfinite(a).all(axis=1) & np.isfinite(b).all(axis=1))
+    slab = max(1, (1 << 20) // max(1, eq.shape[0]))
+    with np.errstate(invalid='ignore', divide='ignore'):
+        for i in range(0, P if eq.shape[0] else 0, slab):
+            k = slice(i, i + slab)
+            ga = a[k] @ eq[:, :3].T + eq[:, 3]
+            gb = b[k] @ eq[:, :3].T + eq[:, 3]
+            ina, inb = ga <= tol, gb <= tol
+            miss[k] |= (~ina & ~inb).any(axis=1)
+            enter, leave = ~ina & inb, ina & ~inb
+            s0[k] = np.maximum(s0[k], np.where(enter, (ga - tol) / (ga - gb), 0.).max(axis=1))
+            s1[k] = np.minimum(s1[k], np.where(leave, (tol - ga) / (gb - ga), 1.).min(axis=1))
+    miss |= ~(s0 < s1)
+    s0[miss] = np.nan
+    s1[miss] = np.nan
+    return s0, s1
+
+
+SLANT_COORDS = ('geodetic', 'ecef')
+SLANT_MAX_NODES = 256                              # Gauss-Legendre nodes Estimate.slant makes itself
+SLANT_MAX_RULE = 65536                             # nodes of a caller's rule
+
+
+def slant_rule(nodes=64, rule=None):
+    """(x, w), contiguous float64: the quadrature rule of Estimate.slant on [-1, 1] - the caller's `rule`, else Gauss-Legendre
+    of `nodes` nodes."""
+    if rule is None:
+        if isinstance(nodes, bool) or not isinstance(nodes, (int, np.integer)) or not 1 <= nodes <= SLANT_MAX_NODES:
+            raise ValueError('nodes must be an integer from 1 to %d, not %r' % (SLANT_MAX_NODES, nodes))
+        x, w = np.polynomial.legendre.leggauss(int(nodes))
+    else:
+        try:
+            x, w = rule
+            x, w = np.ascontiguousarray(x, dtype=np.float64), np.ascontiguousarray(w, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError('rule must be a pair (x, w) of 1-D arrays of numbers')
+        if x.ndim != 1 or w.ndim != 1 or x.size != w.size or not 1 <= x.size <= SLANT_MAX_RULE:
+            raise ValueError('rule must be a pair (x, w) of 1-D arrays of one length from 1 to %d' % SLANT_MAX_RULE)
+        if not (np.isfinite(x).all() and np.isfinite(w).all()):
+            raise ValueError('rule must be finite')
+    return np.ascontiguousarray(x, dtype=np.float64), np.ascontiguousarray(w, dtype=np.float64)
 
 
 GRADIENT_FRAMES = {'model': _lib.VI_FRAME_MODEL, 'enu': _lib.VI_FRAME_ENU}
@@ -347,6 +405,92 @@ class Estimate(object):
         finally:
             for a in bufs:
                 a.free()
+        return out
+
+    def slant(self, times, start, end, nodes=64, rule=None, coords='geodetic', check_hull=True, outside='raise', chord=False,
+              out=None):
+        """Line integrals of the fitted parameter along straight rays, every ray at its own time (slant TEC between a receiver
+        and a satellite, an occultation link, an optical column), in ONE library call (vi_eval_slant_f64, kernel K2l).
+
+        start, end: triples of arrays - (gdlat, gdlon, gdalt) in degrees, degrees, metres with coords='geodetic', (X, Y, Z) in
+        metres with coords='ecef'.  The six arrays broadcast against each other (one receiver, many satellites); the ray shape
+        is the broadcast shape.  times: one value or an array of the ray shape, naive-UTC datetimes or float unix seconds; the
+        record (or the pair, with timeinterp) of each ray is what select_records gives, `outside` as in track.
+        nodes: Gauss-Legendre nodes per ray, 1 to 256.  rule=(x, w): the caller's own rule on [-1, 1] instead (finite 1-D
+        arrays of one length up to 65 536; a composite or trapezoid rule is one of these); `nodes` is then ignored.  The default
+        is converged: 64 and 128 nodes differ by 1.4e-14 of the ray's absolute sum at most on receiver-to-GNSS rays through the
+        hull of the default fixture (profiles/r10_perf_eval_slant.txt).
+
+        With a, b the ECEF end points, ray p gives  sum_i w_i (s1 - s0) / 2 |b - a| f(a + s_i (b - a)),
+        s_i = s0 + (s1 - s0) (1 + x_i) / 2, f the fitted parameter at the ray's time: the parameter's unit times metres.
+        [s0, s1] is the part of the segment inside the data hull (hull_chords) with check_hull, else [0, 1]; the rule sits on
+        exactly that interval, on which the model is analytic.  NaN where the segment does not enter the hull, where the ray
+        has no record (outside='nan'), where a record it needs holds a NaN (with timeinterp: at w == 0 too, as get_C's blend)
+        and where an end point is not finite; 0 for a segment of length zero inside the hull.
+
+        chord=True: returns (value, d0, d1), d0 = s0 |b - a| and d1 = s1 |b - a| the distances from `start` in metres between
+        which the ray is inside the hull - geometry only, given for a ray without a record too; NaN for a miss.
+        `out`: optional C-contiguous float64 array of the ray shape to write the values into."""
+        if coords not in SLANT_COORDS:
+            raise ValueError("coords must be 'geodetic' or 'ecef', not %r" % (coords,))
+        x, wq = slant_rule(nodes, rule)
+        try:
+            if len(start) != 3 or len(end) != 3:
+                raise TypeError
+            ends = np.broadcast_arrays(*(np.asarray(v, dtype=np.float64) for v in tuple(start) + tuple(end)))
+        except TypeError:
+            raise ValueError('start and end must each be a triple of arrays')
+        except ValueError:
+            raise ValueError('the arrays of start and end do not broadcast against each other')
+        shape = ends[0].shape
+        t0 = unix_seconds(times)
+        if t0.ndim and t0.shape != shape:
+            raise ValueError('times must be one value or have the shape of the rays')
+        if out is None:
+            out = np.empty(shape, dtype=np.float64)
+        elif not isinstance(out, np.ndarray) or out.shape != shape or out.dtype != np.float64 or not out.flags.c_contiguous:
+            raise ValueError('out must be a C-contiguous float64 array of shape (%s)' % ', '.join('%d' % n for n in shape))
+        P = ends[0].size
+        if P == 0:
+            return (out, np.empty(shape), np.empty(shape)) if chord else out
+        ends = [np.ascontiguousarray(v).ravel() for v in ends]
+        if coords == 'geodetic':
+            ends = geodesy.geodetic2ecef(*ends[:3]) + geodesy.geodetic2ecef(*ends[3:])
+        a, b = np.array(ends[:3]), np.array(ends[3:])   # planar (3, P)
+        rec, w = self.select_records(np.broadcast_to(t0, shape).ravel(), outside)
+        if check_hull:
+            eq, tol = self._hull()
+        else:
+            eq, tol = None, 0.
+        ctx = self.model.ctx
+        bufs = []                                       # freed whatever happens
+        try:
+            def up(host, dtype=None):
+                bufs.append(ctx.to_device(host, dtype))
+                return bufs[-1]
+            da, db, dr = up(a), up(b), up(rec, np.int32)
+            dw = up(w) if w is not None else None
+            dC = up(np.ascontiguousarray(self.Coeffs, dtype=np.float64))
+            dh = up(eq) if eq is not None else None
+            dx, dq = up(x), up(wq)
+            bufs.append(ctx.empty(P))
+            dO = bufs[-1]
+            dS = None
+            if chord:
+                bufs.append(ctx.empty((2, P)))
+                dS = bufs[-1]
+            _lib.check(_lib.lib.vi_eval_slant_f64(self.model.handle(), P, da.ptr, db.ptr, dr.ptr, dw.ptr if dw is not None else None,
+                                                  self.Coeffs.shape[0], dC.ptr, dh.ptr if dh is not None else None,
+                                                  0 if eq is None else eq.shape[0], tol, x.size, dx.ptr, dq.ptr, dO.ptr,
+                                                  dS.ptr if dS is not None else None), 'vi_eval_slant_f64')
+            out.reshape(-1)[:] = dO.download()
+            if chord:
+                length = np.linalg.norm(b - a, axis=0)
+                s = dS.download()
+                return out, (s[0] * length).reshape(shape), (s[1] * length).reshape(shape)
+        finally:
+            for v in bufs:
+                v.free()
         return out
 
     # estimate.py:153-178 (boolean mask, same shape as the inputs)
