@@ -187,6 +187,24 @@ int  vi_eval_track_f64(vi_model* model, int64_t Q, const double* d_lat, const do
 int  vi_eval_slant_f64(vi_model* model, int64_t P, const double* d_a, const double* d_b, const int32_t* d_rec, const double* d_w,
                        int64_t R, const double* d_C, const double* d_hull_eq, int32_t F, double hull_tol, int32_t n,
                        const double* d_x, const double* d_wq, double* d_out, double* d_chord);
+/* The ray-integrated basis of P rays that stay where they are (an imager's lines of sight, links to geostationary satellites, a
+ * fixed optical column) while the records change: the integral of vi_eval_slant_f64 is linear in the coefficients, so
+ *   d_Y[n*P + p] = (s1 - s0) / 2 * |b - a| * sum_i d_wq[i] * basis_n(a + s_i (b - a))
+ * is built once - N x P doubles, basis_n in the PUBLIC order and scaling of vi_basis_f64 / vi_eval_basis_f64 (not the prepared
+ * order of the evaluation kernels), in metres.  d_Y is a matrix of the kind vi_eval_basis_f64 makes for a grid:
+ * vi_eval_resident_f64 with the coefficients as stored gives the line integrals of T timesteps as one product,
+ * vi_eval_resident_err_f64 with the covariances as stored their standard errors sqrt(b^T dC b), vi_eval_resident_peak_f64 and
+ * vi_reduce_basis_f64 maxima and weighted sums over an axis of the rays; d_Y itself is the linear forward operator of the links.
+ * d_a, d_b, d_hull_eq, F, hull_tol, (n, d_x, d_wq) and d_chord (or NULL) exactly as in vi_eval_slant_f64: the same clip, in fp64,
+ * straight from the facet list; F = 0 keeps [0, 1].  A ray that does not enter the hull (not s0 < s1) or has a non-finite end
+ * point gets the NaN of vi_eval_basis_f64 in ALL N rows (and a NaN chord); a segment of length zero inside the hull a column
+ * of zeros.  Kernel K1l (csrc/vi_basis.hip): a wave per ray, 64 nodes per pass, every basis function summed over the lanes
+ * through an LDS tile in one fixed order, the passes in pass order, no atomics - a column's bits depend on the ray and the rule,
+ * not on P, the other rays or their order.  Models and orders as vi_basis_f64 while the N accumulators of a ray fit a
+ * workgroup's LDS (N <= 7000; beyond: VI_ERR_UNSUPPORTED).  Asynchronous on the context's stream; timed for vi_eval_kernel_ms
+ * like its siblings (tests/test_gpu_resident_rays.py). */
+int  vi_eval_slant_basis_f64(vi_model* model, int64_t P, const double* d_a, const double* d_b, const double* d_hull_eq, int32_t F,
+                             double hull_tol, int32_t n, const double* d_x, const double* d_wq, double* d_Y, double* d_chord);
 /* Many timesteps on ONE grid (BASELINE configs[3]: a GPU's share of 10 000 timesteps, all on the same 256^3 grid - Estimate.__call__
  * (estimate.py:110-123) once per timestep in the reference, which rebuilds the basis of the grid every time): the basis matrix
  * of the grid is assembled once and kept in HBM, and every batch of timesteps is one matrix product.
@@ -256,7 +274,7 @@ int    vi_reduce_basis_f64(vi_model* model, int64_t outer, int64_t L, int64_t in
  * BASELINE configs[4] sweeps against the 1e-6 tolerance.  Orders with an fp32 kernel: (MAXL, MAXK) = (6,4), (2,8), (12,8);
  * others return VI_ERR_UNSUPPORTED from vi_eval_f64 while the flag is set. */
 int  vi_model_set_eval_precision(vi_model* model, int32_t chain_f32);
-/* device time (ms) of the evaluation kernel launches of the last vi_eval_f64 / vi_eval_track_f64 / vi_eval_slant_f64 / vi_eval_resident_f64 /
+/* device time (ms) of the evaluation kernel launches of the last vi_eval_f64 / vi_eval_track_f64 / vi_eval_slant_f64 / vi_eval_slant_basis_f64 / vi_eval_resident_f64 /
  * vi_eval_resident_err_f64 / vi_eval_resident_peak_f64 call on this context, from HIP events recorded on the context's stream around them (the preparation kernels are excluded).
  * The events are recorded only while vi_ctx_set_eval_timing(ctx, 1) is in force (default: off - the pair costs a 0.2 ms call about 7 us);
  * vi_eval_kernel_ms fails with VI_ERR_ARG while it is off or before a call has been timed. */

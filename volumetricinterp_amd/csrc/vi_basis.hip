@@ -1196,9 +1196,9 @@ struct SlantRay {
 // the whole segment, the others bound s from below at (ga - tol) / (ga - gb) or from above at (tol - ga) / (gb - ga); max / min
 // butterflies make [s0, s1] of the lanes' bounds.  A segment with both ends inside the hull keeps [0, 1] exactly.  A miss
 // (not s0 < s1) and non-finite end points give a NaN chord.  Writes the chord - geometry only: a ray without a record has one.
-__device__ __forceinline__ SlantRay slant_ray(int64_t p, int64_t P, const double* __restrict__ a, const double* __restrict__ b,
-                                              const int* __restrict__ rec, int R, int pair, const double* __restrict__ eq, int F,
-                                              double tol, double* __restrict__ chord)
+// slant_clip is the geometry alone (K1l has no records): live = a ray of the launch that enters the hull, r = 0.
+__device__ __forceinline__ SlantRay slant_clip(int64_t p, int64_t P, const double* __restrict__ a, const double* __restrict__ b,
+                                               const double* __restrict__ eq, int F, double tol, double* __restrict__ chord)
 {
     const int lane = threadIdx.x & 63;
     const int64_t pc = p < P ? p : P - 1;
@@ -1236,8 +1236,18 @@ __device__ __forceinline__ SlantRay slant_ray(int64_t p, int64_t P, const double
         chord[p] = y.s0;
         chord[P + p] = y.s1;
     }
-    y.r = rec[pc];
-    y.live = p < P && !miss && y.r >= 0 && y.r <= R - 1 - pair;
+    y.r = 0;
+    y.live = p < P && !miss;
+    return y;
+}
+
+__device__ __forceinline__ SlantRay slant_ray(int64_t p, int64_t P, const double* __restrict__ a, const double* __restrict__ b,
+                                              const int* __restrict__ rec, int R, int pair, const double* __restrict__ eq, int F,
+                                              double tol, double* __restrict__ chord)
+{
+    SlantRay y = slant_clip(p, P, a, b, eq, F, tol, chord);
+    y.r = rec[p < P ? p : P - 1];
+    y.live = y.live && y.r >= 0 && y.r <= R - 1 - pair;
     return y;
 }
 
@@ -1369,6 +1379,163 @@ __global__ __launch_bounds__(BLOCK) void k_slant_sph(SphDev M, int64_t P, const 
     }
     const double val = slant_sum(y, acc);
     if (lane == 0) out[p] = val;
+}
+
+// ---------------------------------------------------------------------------------------------
+// K1l: the ray-integrated basis (vi_eval_slant_basis_f64).  The line integral is linear in the coefficients, so for rays that
+// stay where they are the integrated basis functions are built once,
+//   Y[n*P + p] = (s1 - s0) / 2 * |b - a| * sum_i wq[i] * basis_n(a + s_i (b - a)),
+// N x P doubles in the public order of vi_basis_f64 - a matrix of the kind vi_eval_basis_f64 makes for a grid, which K2r, K2e,
+// K2p and vi_reduce_basis_f64 take as it is.  K2l's structure: a wave per ray, slant_clip, a lane per node, ceil(n / 64) passes.
+// New is the sum across the lanes of EVERY basis function instead of one density.  N accumulators per lane would be 288 VGPRs
+// at N = 144, and a butterfly per value is 12 cross-lane moves for one number; the values go through an LDS tile instead:
+//   - the sink writes a group of TR values (TR = 8 or 16: both parities of one (l, m) at up to 8 k) as TR rows of the wave's tile
+//     [TR][64 + 1], lane i into column i: 64 consecutive doubles per row, no bank conflict;
+//   - rayb_sum adds the columns: lane (part, r) = (lane / TR, lane % TR) adds the TR columns part * TR ... of row r in ascending
+//     order (the row pitch of 65 doubles puts the 32 lanes of a half wave on 32 different bank pairs), 64 / TR - 1 butterfly
+//     steps add the parts, and lane (0, r) adds the row's sum to the ray's accumulator of that basis function.
+// All 64 lanes work in both halves, a value costs one LDS write and one LDS read, and the order of the additions is fixed: the
+// columns of a part ascending, the parts as a butterfly, the passes in pass order - no atomics; a column's bits depend on the ray
+// and the rule alone.  The accumulators are LDS too: [N][waves] doubles, ray-minor, so that after the one barrier the workgroup
+// stores N pieces of `waves` neighbouring columns (32 bytes at four rays) instead of N x waves single doubles at stride P.
+// A dead ray (a miss, a non-finite end point) runs no chain: its wave fills its accumulators with the NaN of vi_eval_basis_f64
+// and waits at the barrier.  The tile is touched by its own wave only: LDS operations of a wave complete in order, so a fence
+// at wavefront scope - which keeps the compiler from moving them - is all the reads after the writes need.
+constexpr int RAYB_LD = 65;         // doubles per tile row: the 64 lanes and one of padding
+
+__device__ __forceinline__ void wave_lds_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// the column sums of the wave's tile: acc[row(r) * ld] += sum_c tile[r][c] for the rows with row(r) >= 0
+template <int TR, class RowFn>
+__device__ __forceinline__ void rayb_sum(double* tile, double* acc, int ld, RowFn&& row)
+{
+    static_assert(TR == 8 || TR == 16 || TR == 32 || TR == 64, "a part is TR columns and 64 / TR parts make a row");
+    const int lane = threadIdx.x & 63, r = lane & (TR - 1), part = lane / TR;
+    wave_lds_sync();
+    const double* src = tile + r * RAYB_LD + part * TR;
+    double s = src[0];
+#pragma unroll
+    for (int c = 1; c < TR; ++c) s += src[c];
+#pragma unroll
+    for (int o = TR; o < 64; o <<= 1) s += __shfl_xor(s, o, 64);
+    const int n = row(r);
+    if (part == 0 && n >= 0) acc[(size_t)n * ld] += s;
+    wave_lds_sync();                // the tile is free again
+}
+
+// the sink of sph_point: BasisSink's values, weighted with the node's weight (0 in a lane past the rule), summed over the wave
+template <int KCAP>
+struct RayBasisSink {
+    static constexpr int KG = KCAP < 8 ? KCAP : 8, TR = 2 * KG;
+    double* tile;                   // the wave's [TR][RAYB_LD]
+    double* acc;                    // the ray's accumulators, acc[n * ld]
+    int ld, maxk, L2;
+    const double* __restrict__ scale;
+    double ELk[KCAP];               // exp(-z / 2) L_k(z), 0 from maxk on
+    double wgt;
+    template <int LCAP>
+    __device__ __forceinline__ void consume(int l, const double* cur, const double* cm, const double* sm)
+    {
+        const int lane = threadIdx.x & 63;
+        const int r0 = l * (l + 1);
+#pragma unroll
+        for (int m = 0; m < LCAP; ++m) {
+            if (m <= l) {
+                const double fp = scale[r0 + m] * cm[m] * cur[m];
+                const double fm = scale[r0 - m] * sm[m] * cur[m];
+#pragma unroll
+                for (int k0 = 0; k0 < KCAP; k0 += KG) {
+                    if (k0 < maxk) {
+#pragma unroll
+                        for (int k = 0; k < KG; ++k) {
+                            tile[(2 * k) * RAYB_LD + lane] = wgt * (ELk[k0 + k] * fp);
+                            tile[(2 * k + 1) * RAYB_LD + lane] = wgt * (ELk[k0 + k] * fm);
+                        }
+                        // row 2 k + 1 of m = 0 (sin 0) and the rows from maxk on are no basis function
+                        rayb_sum<TR>(tile, acc, ld, [&](int r) {
+                            const int k = k0 + (r >> 1);
+                            const bool minus = (r & 1) != 0;
+                            return (k < maxk && !(minus && m == 0)) ? k * L2 + r0 + (minus ? -m : m) : -1;
+                        });
+                    }
+                }
+            }
+        }
+    }
+};
+
+// LDS of a K1l workgroup: the accumulators and a tile per wave
+__host__ __device__ constexpr size_t rayb_lds_bytes(int N, int waves, int TR)
+{
+    return ((size_t)N * waves + (size_t)waves * TR * RAYB_LD) * sizeof(double);
+}
+
+// after the passes: the ray's accumulators scaled to metres, or NaN for a dead ray; then, every wave of the workgroup through
+// the one barrier, the stores - thread i takes accumulator i: `waves` neighbouring columns of a row are neighbouring threads
+__device__ __forceinline__ void rayb_finish(const SlantRay& y, double* sh, int N, int waves, int wave, int64_t P,
+                                            double* __restrict__ Yo)
+{
+    const int lane = threadIdx.x & 63;
+    double* acc = sh + wave;
+    if (y.live) {
+        const double c = 0.5 * (y.s1 - y.s0) * y.len;
+        wave_lds_sync();
+        for (int i = lane; i < N; i += 64) acc[(size_t)i * waves] = c * acc[(size_t)i * waves];
+    } else {
+        for (int i = lane; i < N; i += 64) acc[(size_t)i * waves] = __builtin_nan("");
+    }
+    __syncthreads();                // the only barrier: every wave of the workgroup is here
+    const int64_t p0 = (int64_t)blockIdx.x * waves;
+    for (int i = threadIdx.x; i < N * waves; i += blockDim.x) {
+        const int n = i / waves, w = i - n * waves;
+        if (p0 + w < P) Yo[(int64_t)n * P + p0 + w] = sh[i];
+    }
+}
+
+template <int LCAP, int KCAP>
+__global__ __launch_bounds__(SLANT_WAVES * 64) void k_slant_basis_sph(SphDev M, int64_t P, const double* __restrict__ a,
+                                                                      const double* __restrict__ b, const double* __restrict__ eq,
+                                                                      int F, double tol, int n, const double* __restrict__ xq,
+                                                                      const double* __restrict__ wq, double* __restrict__ Yo,
+                                                                      double* __restrict__ chord)
+{
+    using Sink = RayBasisSink<KCAP>;
+    extern __shared__ __align__(16) double sh[];
+    const int lane = threadIdx.x & 63, wave = wave_index(), waves = blockDim.x >> 6;
+    const int64_t p = (int64_t)blockIdx.x * waves + wave;
+    const SlantRay y = slant_clip(p, P, a, b, eq, F, tol, chord);
+    const int N = M.N;
+    if (y.live) {
+        Sink sink;
+        sink.tile = sh + (size_t)N * waves + (size_t)wave * Sink::TR * RAYB_LD;
+        sink.acc = sh + wave;
+        sink.ld = waves;
+        sink.maxk = M.maxk;
+        sink.L2 = M.maxl * M.maxl;
+        sink.scale = M.scale;
+        for (int i = lane; i < N; i += 64) sink.acc[(size_t)i * waves] = 0.0;
+#pragma unroll 1
+        for (int i0 = 0; i0 < n; i0 += 64) {
+            const int i = i0 + lane;
+            const bool on = i < n;
+            double X, Y, Z;
+            slant_node(y, xq[on ? i : 0], X, Y, Z);
+            const Geom g = sph_geom_ecef(M, X, Y, Z);
+            double Lk[KCAP];
+            laguerre<KCAP>(M.maxk, g.z, Lk);
+            const double E = exp(-0.5 * g.z);
+#pragma unroll
+            for (int k = 0; k < KCAP; ++k) sink.ELk[k] = k < M.maxk ? E * Lk[k] : 0.0;
+            const double w = wq[on ? i : 0];
+            sink.wgt = on ? w : 0.0;            // the lanes past n run node 0 again and add nothing
+            sph_point<LCAP, KCAP>(M, g, sink);
+        }
+    }
+    rayb_finish(y, sh, N, waves, wave, P, Yo);
 }
 
 // Cp[t][r*maxk + k] = C[t][k*L2 + r] * scale[r]
@@ -1538,6 +1705,49 @@ __global__ __launch_bounds__(BLOCK) void k_slant_rbf(RbfDev M, int64_t P, const 
     }
     const double val = slant_sum(y, acc);
     if (lane == 0) out[p] = val;
+}
+
+// K1l for the RBF model: the same wave per ray and lane per node; the centres in groups of RAYB_RBF_TR, a group's Gaussians
+// through the tile and rayb_sum
+constexpr int RAYB_RBF_TR = 16;
+
+__global__ __launch_bounds__(SLANT_WAVES * 64) void k_slant_basis_rbf(RbfDev M, int64_t P, const double* __restrict__ a,
+                                                                      const double* __restrict__ b, const double* __restrict__ eq,
+                                                                      int F, double tol, int n, const double* __restrict__ xq,
+                                                                      const double* __restrict__ wq, double* __restrict__ Yo,
+                                                                      double* __restrict__ chord)
+{
+    constexpr int TR = RAYB_RBF_TR;
+    extern __shared__ __align__(16) double sh[];
+    const int lane = threadIdx.x & 63, wave = wave_index(), waves = blockDim.x >> 6;
+    const int64_t p = (int64_t)blockIdx.x * waves + wave;
+    const SlantRay y = slant_clip(p, P, a, b, eq, F, tol, chord);
+    const int N = M.N;
+    if (y.live) {
+        double* tile = sh + (size_t)N * waves + (size_t)wave * TR * RAYB_LD;
+        double* acc = sh + wave;
+        const double* __restrict__ c = M.centers;
+        for (int i = lane; i < N; i += 64) acc[(size_t)i * waves] = 0.0;
+#pragma unroll 1
+        for (int i0 = 0; i0 < n; i0 += 64) {
+            const int i = i0 + lane;
+            const bool on = i < n;
+            double X, Y, Z;
+            slant_node(y, xq[on ? i : 0], X, Y, Z);
+            const double w = wq[on ? i : 0];
+            const double wgt = on ? w : 0.0;
+            for (int k0 = 0; k0 < N; k0 += TR) {
+#pragma unroll
+                for (int j = 0; j < TR; ++j) {
+                    const int k = k0 + j < N ? k0 + j : N - 1;
+                    const double dx = X - c[3 * k], dy = Y - c[3 * k + 1], dz = Z - c[3 * k + 2];
+                    tile[j * RAYB_LD + lane] = wgt * exp(-(dx * dx + dy * dy + dz * dz) * M.inv_eps2);
+                }
+                rayb_sum<TR>(tile, acc, waves, [&](int r) { return k0 + r < N ? k0 + r : -1; });
+            }
+        }
+    }
+    rayb_finish(y, sh, N, waves, wave, P, Yo);
 }
 
 __global__ void k_transform_rbf(int64_t P, const double* __restrict__ lat, const double* __restrict__ lon,
@@ -2242,4 +2452,45 @@ extern "C" int vi_eval_slant_f64(vi_model* m, int64_t P, const double* d_a, cons
 #undef VI_SLANT_FAST
     }
     return at_order_cap(m, "vi_eval_slant_f64", [&](auto lc, auto kc) { return launch_slant_sph<lc, kc>(m, s, m->d_coef); });
+}
+
+// The ray-integrated basis (include/vinterp.h): K1l.  No preparation - the kernel clips each ray against the caller's facet list
+// itself and reads no coefficients - and one launch: as many rays in a workgroup as the LDS holds accumulator columns beside
+// the tiles, SLANT_WAVES unless N is in the thousands.
+namespace {
+template <class K, class Dev>
+int launch_slant_basis(vi_model* m, K kernel, const Dev& dev, int TR, const SlantArgs& s)
+{
+    int waves = SLANT_WAVES;
+    while (waves > 1 && rayb_lds_bytes(m->N, waves, TR) > 64 * 1024) waves >>= 1;
+    const size_t shm = rayb_lds_bytes(m->N, waves, TR);
+    if (shm > 64 * 1024) {
+        vi_set_error("vi_eval_slant_basis_f64: the %d accumulators of a ray exceed the LDS of a workgroup", m->N);
+        return VI_ERR_UNSUPPORTED;
+    }
+    VI_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+    hipLaunchKernelGGL(kernel, dim3(nblocks(s.P, waves)), dim3(waves * 64), shm, m->ctx->stream, dev, s.P, s.a, s.b, s.eq, s.F,
+                       s.tol, s.n, s.xq, s.wq, s.out, s.chord);
+    VI_HIP(hipGetLastError());
+    return VI_OK;
+}
+}  // namespace
+
+extern "C" int vi_eval_slant_basis_f64(vi_model* m, int64_t P, const double* d_a, const double* d_b, const double* d_hull_eq,
+                                       int32_t F, double hull_tol, int32_t n, const double* d_x, const double* d_wq, double* d_Y,
+                                       double* d_chord)
+{
+    VI_REQUIRE(m && d_a && d_b && d_x && d_wq && d_Y, "null argument");
+    VI_REQUIRE(P >= 0 && F >= 0, "negative size");
+    VI_REQUIRE(n >= 1, "a rule has at least one node");
+    VI_REQUIRE(P <= 0x7fffffffLL, "more rays than one launch takes");
+    VI_REQUIRE(F == 0 || d_hull_eq, "hull facet count given without facet equations");
+    if (P == 0) return VI_OK;
+    VI_HIP(hipSetDevice(m->ctx->device));
+    const SlantArgs s{P, d_a, d_b, nullptr, nullptr, 0, d_hull_eq, (int)F, hull_tol, (int)n, d_x, d_wq, d_Y, d_chord};
+    EvalTimer timer(m->ctx);
+    if (m->kind != VI_MODEL_SPHHARMLAG) return launch_slant_basis(m, k_slant_basis_rbf, m->rbf, RAYB_RBF_TR, s);
+    return at_order_cap(m, "vi_eval_slant_basis_f64", [&](auto lc, auto kc) {
+        return launch_slant_basis(m, k_slant_basis_sph<lc, kc>, m->sph, RayBasisSink<kc>::TR, s);
+    });
 }

@@ -207,6 +207,29 @@ def slant_rule(nodes=64, rule=None):
     return np.ascontiguousarray(x, dtype=np.float64), np.ascontiguousarray(w, dtype=np.float64)
 
 
+def slant_rays(start, end, nodes=64, rule=None, coords='geodetic'):
+    """(x, w, shape, a, b): what Estimate.slant and Estimate.resident_rays make of their ray arguments - the rule of slant_rule,
+    the ray shape (the broadcast shape of the six arrays of `start` and `end`) and the end points in ECEF metres, planar
+    (3, P) each, P the number of rays."""
+    if coords not in SLANT_COORDS:
+        raise ValueError("coords must be 'geodetic' or 'ecef', not %r" % (coords,))
+    x, wq = slant_rule(nodes, rule)
+    try:
+        if len(start) != 3 or len(end) != 3:
+            raise TypeError
+        ends = np.broadcast_arrays(*(np.asarray(v, dtype=np.float64) for v in tuple(start) + tuple(end)))
+    except TypeError:
+        raise ValueError('start and end must each be a triple of arrays')
+    except ValueError:
+        raise ValueError('the arrays of start and end do not broadcast against each other')
+    shape = ends[0].shape
+    ends = [np.ascontiguousarray(v).ravel() for v in ends]
+    if coords == 'geodetic':
+        ends = geodesy.geodetic2ecef(*ends[:3]) + geodesy.geodetic2ecef(*ends[3:])
+    a, b = np.array(ends[:3]), np.array(ends[3:])       # planar (3, P)
+    return x, wq, shape, a, b
+
+
 GRADIENT_FRAMES = {'model': _lib.VI_FRAME_MODEL, 'enu': _lib.VI_FRAME_ENU}
 PEAK_KINDS = {'max': 0, 'min': 1}                 # vi_eval_resident_peak_f64's kind
 REDUCED_BASES = 8                                  # reduced bases a ResidentGrid keeps (evaluate_integrals), oldest out
@@ -305,6 +328,16 @@ class Estimate(object):
         ResidentGrid.gradient / evaluate_gradients give the gradient maps of many timesteps as one product, with components
         along the model coordinates (z, theta, phi, as Estimate.gradient) or along local east, north, up."""
         return ResidentGrid(self, gdlat, gdlon, gdalt, check_hull, gradient)
+
+    def resident_rays(self, start, end, nodes=64, rule=None, coords='geodetic', check_hull=True):
+        """The rays of a fixed geometry that MANY timesteps are going to be integrated along (an all-sky imager's lines of
+        sight, a receiver looking at geostationary satellites, a fixed optical column): Estimate.slant walks the chains of all
+        nodes of every ray at every call, but the integral is linear in the coefficients, so the ray-integrated basis
+        B[n, p] = (s1 - s0) / 2 |b - a| sum_i w_i basis_n(a_p + s_i (b_p - a_p)) is assembled once (vi_eval_slant_basis_f64,
+        kernel K1l) and stays in device memory - N x P doubles, 0.3 GB for 512 x 512 rays at the default order - and every
+        batch of timesteps is one matrix product.  start, end, nodes, rule, coords and check_hull as in slant: the same rays,
+        the same clip against the data hull, the same rule on the part inside.  Returns a ResidentRays."""
+        return ResidentRays(self, start, end, nodes, rule, coords, check_hull)
 
     def gradient(self, time, gdlat, gdlon, gdalt, check_hull=True, frame='model'):
         """Gradient of the fitted parameter at the points: array of shape gdlat.shape + (3,), components along the
@@ -431,18 +464,7 @@ class Estimate(object):
         chord=True: returns (value, d0, d1), d0 = s0 |b - a| and d1 = s1 |b - a| the distances from `start` in metres between
         which the ray is inside the hull - geometry only, given for a ray without a record too; NaN for a miss.
         `out`: optional C-contiguous float64 array of the ray shape to write the values into."""
-        if coords not in SLANT_COORDS:
-            raise ValueError("coords must be 'geodetic' or 'ecef', not %r" % (coords,))
-        x, wq = slant_rule(nodes, rule)
-        try:
-            if len(start) != 3 or len(end) != 3:
-                raise TypeError
-            ends = np.broadcast_arrays(*(np.asarray(v, dtype=np.float64) for v in tuple(start) + tuple(end)))
-        except TypeError:
-            raise ValueError('start and end must each be a triple of arrays')
-        except ValueError:
-            raise ValueError('the arrays of start and end do not broadcast against each other')
-        shape = ends[0].shape
+        x, wq, shape, a, b = slant_rays(start, end, nodes, rule, coords)
         t0 = unix_seconds(times)
         if t0.ndim and t0.shape != shape:
             raise ValueError('times must be one value or have the shape of the rays')
@@ -450,13 +472,9 @@ class Estimate(object):
             out = np.empty(shape, dtype=np.float64)
         elif not isinstance(out, np.ndarray) or out.shape != shape or out.dtype != np.float64 or not out.flags.c_contiguous:
             raise ValueError('out must be a C-contiguous float64 array of shape (%s)' % ', '.join('%d' % n for n in shape))
-        P = ends[0].size
+        P = a.shape[1]
         if P == 0:
             return (out, np.empty(shape), np.empty(shape)) if chord else out
-        ends = [np.ascontiguousarray(v).ravel() for v in ends]
-        if coords == 'geodetic':
-            ends = geodesy.geodetic2ecef(*ends[:3]) + geodesy.geodetic2ecef(*ends[3:])
-        a, b = np.array(ends[:3]), np.array(ends[3:])   # planar (3, P)
         rec, w = self.select_records(np.broadcast_to(t0, shape).ravel(), outside)
         if check_hull:
             eq, tol = self._hull()
@@ -527,11 +545,26 @@ class ResidentGrid(object):
     def __init__(self, est, gdlat, gdlon, gdalt, check_hull=True, gradient=None):
         if gradient is not None and gradient not in GRADIENT_FRAMES:
             raise ValueError("gradient must be None, 'model' or 'enu', not %r" % (gradient,))
+        shape = np.asarray(gdlat).shape
+        lat, lon, alt = ravel_points(gdlat, gdlon, gdalt)
+
+        def build(up, hp, F, tol):
+            h, Q = est.model.handle(), lat.size
+            dlat, dlon, dalt = up(lat), up(lon), up(alt)
+            if gradient is not None:    # first: the call that refuses a model or an order
+                _lib.check(_lib.lib.vi_eval_grad_basis_f64(h, Q, dlat.ptr, dlon.ptr, dalt.ptr, hp, F, tol,
+                                                           GRADIENT_FRAMES[gradient], self.dG.ptr), 'vi_eval_grad_basis_f64')
+            _lib.check(_lib.lib.vi_eval_basis_f64(h, Q, dlat.ptr, dlon.ptr, dalt.ptr, hp, F, tol, self.dY.ptr), 'vi_eval_basis_f64')
+        self._setup(est, shape, lat.size, check_hull, gradient, build)
+
+    def _setup(self, est, shape, Q, check_hull, gradient, build):
+        """What every resident matrix shares: the state, the free-memory check, the allocation of dY (N x Q) and - with a
+        gradient frame - dG, and build(up, hull pointer, F, tol) filling them: up(host array[, dtype]) gives a device copy that
+        is freed when the set-up ends, whatever happens.  A failed set-up closes the object."""
         self.est = est
         self.frame = gradient
-        self.shape = np.asarray(gdlat).shape
-        lat, lon, alt = ravel_points(gdlat, gdlon, gdalt)
-        self.Q = lat.size
+        self.shape = shape
+        self.Q = Q
         ctx = est.model.ctx
         N = est.model.nbasis
         free, _ = ctx.mem_info()
@@ -543,26 +576,22 @@ class ResidentGrid(object):
         self.dY = self.dG = None
         self._reduced = {}              # (axis, weight bytes) -> reduced basis on the device (evaluate_integrals)
         tmp = []                        # device temporaries of the set-up: freed whatever happens below
+
+        def up(host, dtype=None):
+            tmp.append(ctx.to_device(host, dtype))
+            return tmp[-1]
         try:
             self.dY = ctx.empty((N, self.Q))
             if gradient is not None:
                 self.dG = ctx.empty((N, 3, self.Q))
             if self.Q == 0:
                 return
-            for a in (lat, lon, alt):
-                tmp.append(ctx.to_device(a))
             if check_hull:
                 eq, tol = est._hull()
-                dh, F = ctx.to_device(eq), eq.shape[0]
-                tmp.append(dh)
+                hp, F = up(eq).ptr, eq.shape[0]
             else:
-                dh, F, tol = None, 0, 0.
-            hp = dh.ptr if dh is not None else None
-            if gradient is not None:    # first: the call that refuses a model or an order
-                _lib.check(_lib.lib.vi_eval_grad_basis_f64(est.model.handle(), self.Q, tmp[0].ptr, tmp[1].ptr, tmp[2].ptr, hp, F,
-                                                           tol, GRADIENT_FRAMES[gradient], self.dG.ptr), 'vi_eval_grad_basis_f64')
-            _lib.check(_lib.lib.vi_eval_basis_f64(est.model.handle(), self.Q, tmp[0].ptr, tmp[1].ptr, tmp[2].ptr, hp, F, tol,
-                                                  self.dY.ptr), 'vi_eval_basis_f64')
+                hp, F, tol = None, 0, 0.
+            build(up, hp, F, tol)
             ctx.sync()
         except BaseException:
             self.close()                # the matrices (19 + 57 GB at the default order on 256^3) must not outlive a failed set-up
@@ -859,3 +888,41 @@ class ResidentGrid(object):
             self.close()
         except Exception:               # interpreter shutdown: the library may already be gone
             pass
+
+
+class ResidentRays(ResidentGrid):
+    """Ray-integrated basis of a fixed set of rays, resident on the device (Estimate.resident_rays): a ResidentGrid whose
+    "points" are the rays and whose matrix dY is B[n, p] = (s1 - s0) / 2 |b - a| sum_i w_i basis_n(a_p + s_i (b_p - a_p)), in
+    metres.  Everything a ResidentGrid does with the basis of its points holds for the line integrals, in the parameter's unit
+    times metres:
+      r(times), evaluate_coeffs(C)    the integrals of slant at one time per image, (T,) + ray shape, as one product (K2r);
+      error(times), evaluate_errors   their standard errors sqrt(b^T dC b) (K2e) - the parameter's unit times metres too;
+      peak, evaluate_peaks            the largest (smallest) integral along an axis of the ray shape and where it sits;
+      integrate, evaluate_integrals   weighted sums of the integrals along an axis, over the rays that enter the hull.
+    NaN for a ray that does not enter the hull or has a non-finite end point, 0 for a segment of length zero inside it.
+    It holds no gradient basis: gradient and evaluate_gradients raise."""
+
+    def __init__(self, est, start, end, nodes=64, rule=None, coords='geodetic', check_hull=True):
+        x, wq, shape, a, b = slant_rays(start, end, nodes, rule, coords)
+        P = a.shape[1]
+        self._length = np.linalg.norm(b - a, axis=0)
+        self._s = np.empty((2, P))
+
+        def build(up, hp, F, tol):
+            da, db, dx, dq, dS = up(a), up(b), up(x), up(wq), up(self._s)
+            _lib.check(_lib.lib.vi_eval_slant_basis_f64(est.model.handle(), P, da.ptr, db.ptr, hp, F, tol, x.size, dx.ptr, dq.ptr,
+                                                        self.dY.ptr, dS.ptr), 'vi_eval_slant_basis_f64')
+            self._s = dS.download()
+        self._setup(est, shape, P, check_hull, None, build)
+
+    def basis(self):
+        """The matrix itself on the host, (N,) + ray shape, in the parameter-free unit metres: the linear forward operator of
+        the rays - np.tensordot(C, r.basis(), 1) is the line integral of the model with coefficients C along every ray - in the
+        public order of Model.basis.  NaN in all N entries of a ray that does not enter the hull."""
+        return self._open(self.dY).download().reshape((self.est.model.nbasis,) + tuple(self.shape))
+
+    @property
+    def chords(self):
+        """(d0, d1), each of the ray shape: the distances from `start` in metres between which the ray is inside the hull,
+        NaN for a miss - as Estimate.slant(chord=True) returns them."""
+        return (self._s[0] * self._length).reshape(self.shape), (self._s[1] * self._length).reshape(self.shape)
