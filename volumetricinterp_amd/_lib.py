@@ -202,6 +202,9 @@ class Context:
         a.upload(host)
         return a
 
+    def scope(self):
+        return DeviceScope(self)
+
     def close(self):
         if self.handle:
             lib.vi_ctx_destroy(self.handle)
@@ -212,6 +215,39 @@ class Context:
             self.close()
         except Exception:
             pass
+
+
+class DeviceScope:
+    """The device temporaries of one call: `with ctx.scope() as dev:` frees every array dev.up / dev.empty gave when the block
+    ends - returned, raised, or an allocation itself raised - but the ones dev.detach handed to the caller."""
+
+    def __init__(self, ctx):
+        self.ctx, self.arrays = ctx, []
+
+    def up(self, host, dtype=None):
+        self.arrays.append(self.ctx.to_device(host, dtype))
+        return self.arrays[-1]
+
+    def empty(self, shape, dtype=np.float64):
+        self.arrays.append(self.ctx.empty(shape, dtype))
+        return self.arrays[-1]
+
+    def detach(self, a):
+        self.arrays = [b for b in self.arrays if b is not a]
+        return a
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, etype, *_):
+        failed = None
+        while self.arrays:
+            try:
+                self.arrays.pop().free()
+            except Exception as e:      # the others are freed all the same
+                failed = failed or e
+        if failed is not None and etype is None:        # (the body's own exception is the one that propagates)
+            raise failed
 
 
 class DeviceArray:

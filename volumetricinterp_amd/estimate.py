@@ -230,6 +230,21 @@ def slant_rays(start, end, nodes=64, rule=None, coords='geodetic'):
     return x, wq, shape, a, b
 
 
+def _check_out(out, shape, dtype=np.float64):
+    """`out`, checked, or a new array: what every entry with an `out` argument writes into."""
+    if out is None:
+        return np.empty(shape, dtype=dtype)
+    if not isinstance(out, np.ndarray) or out.shape != tuple(shape) or out.dtype != dtype or not out.flags.c_contiguous:
+        raise ValueError('out must be a C-contiguous %s array of shape (%s)'
+                         % (np.dtype(dtype).name, ', '.join('%d' % n for n in shape)))
+    return out
+
+
+def _ptr(a):
+    """The device pointer of an optional argument of a library call."""
+    return None if a is None else a.ptr
+
+
 GRADIENT_FRAMES = {'model': _lib.VI_FRAME_MODEL, 'enu': _lib.VI_FRAME_ENU}
 PEAK_KINDS = {'max': 0, 'min': 1}                 # vi_eval_resident_peak_f64's kind
 REDUCED_BASES = 8                                  # reduced bases a ResidentGrid keeps (evaluate_integrals), oldest out
@@ -282,6 +297,14 @@ class Estimate(object):
             self._hull_eq = hull_equations(self.hull_vert)
         return self._hull_eq
 
+    def _hull_args(self, check_hull):
+        """(eq, F, tol): the hull arguments of a library call - the half-spaces, their number, the tolerance - and
+        (None, 0, 0.) without the hull test."""
+        if not check_hull:
+            return None, 0, 0.
+        eq, tol = self._hull()
+        return eq, eq.shape[0], tol
+
     # estimate.py:75-123
     def __call__(self, time, gdlat, gdlon, gdalt, calcgrad=False, calcerr=False, check_hull=True):
         # calcgrad / calcerr are accepted and ignored, exactly as in the reference (code after the
@@ -299,21 +322,15 @@ class Estimate(object):
         T, Q = C.shape[0], lat.size
         if C.shape[1] != self.model.nbasis:
             raise ValueError('coefficient vector length %d != nbasis %d' % (C.shape[1], self.model.nbasis))
-        if out is None:
-            out = np.empty((T, Q), dtype=np.float64)
-        elif out.shape != (T, Q) or out.dtype != np.float64 or not out.flags.c_contiguous:
-            raise ValueError('out must be a C-contiguous float64 array of shape (%d, %d)' % (T, Q))
+        out = _check_out(out, (T, Q))
         if Q == 0 or T == 0:
             return out
         h = self.model.handle()
         P = _lib.c_double_p
-        if check_hull:
-            eq, tol = self._hull()
-            F, eqp = eq.shape[0], eq.ctypes.data_as(P)
-        else:
-            tol, F, eqp = 0., 0, None
+        eq, F, tol = self._hull_args(check_hull)
         _lib.check(_lib.lib.vi_eval_f64_host(h, Q, lat.ctypes.data_as(P), lon.ctypes.data_as(P),
-                                             alt.ctypes.data_as(P), T, C.ctypes.data_as(P), eqp, F, tol,
+                                             alt.ctypes.data_as(P), T, C.ctypes.data_as(P),
+                                             None if eq is None else eq.ctypes.data_as(P), F, tol,
                                              out.ctypes.data_as(P)), 'vi_eval_f64_host')
         return out
 
@@ -368,17 +385,11 @@ class Estimate(object):
         Q = lat.size
         out = np.empty((Q,) + width)
         if Q:
-            ctx = self.model.ctx
-            bufs = []                               # freed whatever happens (a failed call must not keep device memory)
-            try:
-                for a in (lat, lon, alt, np.ascontiguousarray(mat, dtype=np.float64)):
-                    bufs.append(ctx.to_device(a))
-                bufs.append(ctx.empty((Q,) + width))
-                _lib.check(getattr(_lib.lib, entry)(self.model.handle(), Q, *(a.ptr for a in bufs)), entry)
-                out = bufs[4].download()
-            finally:
-                for a in bufs:
-                    a.free()
+            with self.model.ctx.scope() as dev:     # (a failed call must not keep device memory)
+                dlat, dlon, dalt, dM = dev.up(lat), dev.up(lon), dev.up(alt), dev.up(np.ascontiguousarray(mat, dtype=np.float64))
+                dO = dev.empty((Q,) + width)
+                _lib.check(getattr(_lib.lib, entry)(self.model.handle(), Q, dlat.ptr, dlon.ptr, dalt.ptr, dM.ptr, dO.ptr), entry)
+                out = dO.download()
             if check_hull:
                 out[~self.check_hull(lat, lon, alt)] = np.nan
         return out, lat, lon, alt
@@ -398,47 +409,37 @@ class Estimate(object):
         gdlat; `out`: optional C-contiguous float64 array of that shape to write into."""
         lat, lon, alt = ravel_points(gdlat, gdlon, gdalt)
         shape, Q = np.shape(gdlat), lat.size
-        t0 = unix_seconds(times)
-        if t0.ndim and t0.shape != shape:
-            raise ValueError('times must be one value or have the shape of gdlat')
-        if out is None:
-            out = np.empty(shape, dtype=np.float64)
-        elif not isinstance(out, np.ndarray) or out.shape != shape or out.dtype != np.float64 or not out.flags.c_contiguous:
-            raise ValueError('out must be a C-contiguous float64 array of shape (%s)' % ', '.join('%d' % n for n in shape))
+        t0 = self._times_for(times, shape, 'gdlat')
+        out = _check_out(out, shape)
         if Q == 0:
             return out
-        rec, w = self.select_records(np.broadcast_to(t0, shape).ravel(), outside)
+        rec, w = self.select_records(t0, outside)
         order = np.argsort(rec, kind='stable')          # the kernel's cost grows with the span of records in 64 points
-        if check_hull:
-            eq, tol = self._hull()
-        else:
-            eq, tol = None, 0.
-        ctx = self.model.ctx
-        bufs = []                                       # freed whatever happens
-        try:
-            for a in (lat[order], lon[order], alt[order]):
-                bufs.append(ctx.to_device(a))
-            bufs.append(ctx.to_device(rec[order], np.int32))
-            dw = dh = None
-            if w is not None:
-                dw = ctx.to_device(w[order])
-                bufs.append(dw)
-            dC = ctx.to_device(np.ascontiguousarray(self.Coeffs, dtype=np.float64))
-            bufs.append(dC)
-            if eq is not None:
-                dh = ctx.to_device(eq)
-                bufs.append(dh)
-            dO = ctx.empty(Q)
-            bufs.append(dO)
-            _lib.check(_lib.lib.vi_eval_track_f64(self.model.handle(), Q, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, bufs[3].ptr,
-                                                  dw.ptr if dw is not None else None, self.Coeffs.shape[0], dC.ptr,
-                                                  dh.ptr if dh is not None else None, 0 if eq is None else eq.shape[0], tol,
-                                                  dO.ptr), 'vi_eval_track_f64')
+        with self.model.ctx.scope() as dev:
+            dlat, dlon, dalt = dev.up(lat[order]), dev.up(lon[order]), dev.up(alt[order])
+            records = self._upload_records(dev, rec[order], None if w is None else w[order], check_hull)
+            dO = dev.empty(Q)
+            _lib.check(_lib.lib.vi_eval_track_f64(self.model.handle(), Q, dlat.ptr, dlon.ptr, dalt.ptr, *records, dO.ptr),
+                       'vi_eval_track_f64')
             out.reshape(-1)[order] = dO.download()
-        finally:
-            for a in bufs:
-                a.free()
         return out
+
+    def _times_for(self, times, shape, what):
+        """The host half of what track and slant share: float64 unix seconds of `times`, one per point or ray, raveled."""
+        t0 = unix_seconds(times)
+        if t0.ndim and t0.shape != shape:
+            raise ValueError('times must be one value or have the shape of ' + what)
+        return np.broadcast_to(t0, shape).ravel()
+
+    def _upload_records(self, dev, rec, w, check_hull):
+        """The device half: the run of arguments vi_eval_track_f64 and vi_eval_slant_f64 share - (rec, w or None, R, Coeffs,
+        hull or None, F, tol) - of the (rec, w) of select_records in the caller's order, the device copies in the scope `dev`."""
+        eq, F, tol = self._hull_args(check_hull)
+        dr = dev.up(rec, np.int32)
+        dw = None if w is None else dev.up(w)
+        dC = dev.up(np.ascontiguousarray(self.Coeffs, dtype=np.float64))
+        dh = None if eq is None else dev.up(eq)
+        return dr.ptr, _ptr(dw), self.Coeffs.shape[0], dC.ptr, _ptr(dh), F, tol
 
     def slant(self, times, start, end, nodes=64, rule=None, coords='geodetic', check_hull=True, outside='raise', chord=False,
               out=None):
@@ -465,50 +466,25 @@ class Estimate(object):
         which the ray is inside the hull - geometry only, given for a ray without a record too; NaN for a miss.
         `out`: optional C-contiguous float64 array of the ray shape to write the values into."""
         x, wq, shape, a, b = slant_rays(start, end, nodes, rule, coords)
-        t0 = unix_seconds(times)
-        if t0.ndim and t0.shape != shape:
-            raise ValueError('times must be one value or have the shape of the rays')
-        if out is None:
-            out = np.empty(shape, dtype=np.float64)
-        elif not isinstance(out, np.ndarray) or out.shape != shape or out.dtype != np.float64 or not out.flags.c_contiguous:
-            raise ValueError('out must be a C-contiguous float64 array of shape (%s)' % ', '.join('%d' % n for n in shape))
+        t0 = self._times_for(times, shape, 'the rays')
+        out = _check_out(out, shape)
         P = a.shape[1]
         if P == 0:
             return (out, np.empty(shape), np.empty(shape)) if chord else out
-        rec, w = self.select_records(np.broadcast_to(t0, shape).ravel(), outside)
-        if check_hull:
-            eq, tol = self._hull()
-        else:
-            eq, tol = None, 0.
-        ctx = self.model.ctx
-        bufs = []                                       # freed whatever happens
-        try:
-            def up(host, dtype=None):
-                bufs.append(ctx.to_device(host, dtype))
-                return bufs[-1]
-            da, db, dr = up(a), up(b), up(rec, np.int32)
-            dw = up(w) if w is not None else None
-            dC = up(np.ascontiguousarray(self.Coeffs, dtype=np.float64))
-            dh = up(eq) if eq is not None else None
-            dx, dq = up(x), up(wq)
-            bufs.append(ctx.empty(P))
-            dO = bufs[-1]
-            dS = None
-            if chord:
-                bufs.append(ctx.empty((2, P)))
-                dS = bufs[-1]
-            _lib.check(_lib.lib.vi_eval_slant_f64(self.model.handle(), P, da.ptr, db.ptr, dr.ptr, dw.ptr if dw is not None else None,
-                                                  self.Coeffs.shape[0], dC.ptr, dh.ptr if dh is not None else None,
-                                                  0 if eq is None else eq.shape[0], tol, x.size, dx.ptr, dq.ptr, dO.ptr,
-                                                  dS.ptr if dS is not None else None), 'vi_eval_slant_f64')
+        rec, w = self.select_records(t0, outside)
+        with self.model.ctx.scope() as dev:
+            da, db = dev.up(a), dev.up(b)
+            records = self._upload_records(dev, rec, w, check_hull)
+            dx, dq = dev.up(x), dev.up(wq)
+            dO = dev.empty(P)
+            dS = dev.empty((2, P)) if chord else None
+            _lib.check(_lib.lib.vi_eval_slant_f64(self.model.handle(), P, da.ptr, db.ptr, *records, x.size, dx.ptr, dq.ptr, dO.ptr,
+                                                  _ptr(dS)), 'vi_eval_slant_f64')
             out.reshape(-1)[:] = dO.download()
             if chord:
                 length = np.linalg.norm(b - a, axis=0)
                 s = dS.download()
                 return out, (s[0] * length).reshape(shape), (s[1] * length).reshape(shape)
-        finally:
-            for v in bufs:
-                v.free()
         return out
 
     # estimate.py:153-178 (boolean mask, same shape as the inputs)
@@ -559,8 +535,8 @@ class ResidentGrid(object):
 
     def _setup(self, est, shape, Q, check_hull, gradient, build):
         """What every resident matrix shares: the state, the free-memory check, the allocation of dY (N x Q) and - with a
-        gradient frame - dG, and build(up, hull pointer, F, tol) filling them: up(host array[, dtype]) gives a device copy that
-        is freed when the set-up ends, whatever happens.  A failed set-up closes the object."""
+        gradient frame - dG, and build(up, hull pointer, F, tol) filling them: up(host array[, dtype]) gives a device copy in
+        the scope of the set-up, freed when it ends whatever happens.  A failed set-up closes the object."""
         self.est = est
         self.frame = gradient
         self.shape = shape
@@ -575,30 +551,19 @@ class ResidentGrid(object):
                                  free / 1e9))
         self.dY = self.dG = None
         self._reduced = {}              # (axis, weight bytes) -> reduced basis on the device (evaluate_integrals)
-        tmp = []                        # device temporaries of the set-up: freed whatever happens below
-
-        def up(host, dtype=None):
-            tmp.append(ctx.to_device(host, dtype))
-            return tmp[-1]
-        try:
-            self.dY = ctx.empty((N, self.Q))
-            if gradient is not None:
-                self.dG = ctx.empty((N, 3, self.Q))
-            if self.Q == 0:
-                return
-            if check_hull:
-                eq, tol = est._hull()
-                hp, F = up(eq).ptr, eq.shape[0]
-            else:
-                hp, F, tol = None, 0, 0.
-            build(up, hp, F, tol)
-            ctx.sync()
-        except BaseException:
-            self.close()                # the matrices (19 + 57 GB at the default order on 256^3) must not outlive a failed set-up
-            raise
-        finally:
-            for a in tmp:
-                a.free()
+        with ctx.scope() as dev:        # the temporaries of the set-up; dY and dG are the object's
+            try:
+                self.dY = ctx.empty((N, self.Q))
+                if gradient is not None:
+                    self.dG = ctx.empty((N, 3, self.Q))
+                if self.Q == 0:
+                    return
+                eq, F, tol = est._hull_args(check_hull)
+                build(dev.up, None if eq is None else dev.up(eq).ptr, F, tol)
+                ctx.sync()
+            except BaseException:
+                self.close()            # the matrices (19 + 57 GB at the default order on 256^3) must not outlive a failed set-up
+                raise
 
     def _open(self, dM):
         """dM, a matrix of this grid on the device, unless close() has given it back."""
@@ -618,14 +583,6 @@ class ResidentGrid(object):
         C = [np.asarray(self.est.get_C(t)[0], dtype=np.float64) for t in times]
         return np.array(C).reshape(len(times), self.est.model.nbasis)
 
-    @staticmethod
-    def _out(out, shape):
-        if out is None:
-            return np.empty(shape, dtype=np.float64)
-        if out.shape != shape or out.dtype != np.float64 or not out.flags.c_contiguous:
-            raise ValueError('out must be a C-contiguous float64 array of shape (%s)' % ', '.join('%d' % n for n in shape))
-        return out
-
     def _slab(self, T, nbytes):
         """The timesteps per slab: what a timestep takes on the device (`nbytes`) fits a quarter of the free device memory."""
         free, _ = self.est.model.ctx.mem_info()
@@ -636,7 +593,7 @@ class ResidentGrid(object):
         the timesteps per slab of that output.  Returns (C, out, slab); slab 0: nothing to compute."""
         C = self._coeffs(C)
         T = C.shape[0]
-        out = self._out(out, (T,) + width)
+        out = _check_out(out, (T,) + width)
         if T == 0 or self.Q == 0:
             return C, out, 0
         return C, out, self._slab(T, int(np.prod(width)) * 8)
@@ -648,25 +605,18 @@ class ResidentGrid(object):
         buffer is freed whatever happens."""
         ctx = self.est.model.ctx
         T = X.shape[0]
-        bufs = []
-        try:
-            dX = ctx.to_device(X) if once else ctx.empty((slab,) + X.shape[1:])
-            bufs.append(dX)
-            for o in outs:
-                bufs.append(ctx.empty((slab,) + o.shape[1:], o.dtype))
-            if work is not None:
-                bufs.append(ctx.empty(work, np.uint8))
+        with ctx.scope() as dev:
+            dX = dev.up(X) if once else dev.empty((slab,) + X.shape[1:])
+            dOs = [dev.empty((slab,) + o.shape[1:], o.dtype) for o in outs]
+            dW = [] if work is None else [dev.empty(work, np.uint8)]
             for t0 in range(0, T, slab):
                 tc = min(slab, T - t0)
                 if not once:
                     dX.upload(X[t0:t0 + tc])
-                call(tc, dX.offset_ptr(t0 * X[0].size if once else 0), *bufs[1:])
-                for o, dO in zip(outs, bufs[1:]):
+                call(tc, dX.offset_ptr(t0 * X[0].size if once else 0), *dOs, *dW)
+                for o, dO in zip(outs, dOs):
                     part = o[t0:t0 + tc]
                     _lib.check(_lib.lib.vi_d2h(ctx.handle, part.ctypes.data_as(_lib.VOIDP), dO.ptr, part.nbytes), 'd2h')
-        finally:
-            for a in bufs:
-                a.free()
         return outs
 
     def _products(self, dM, cols, C, out, slab):
@@ -721,7 +671,7 @@ class ResidentGrid(object):
         if dC.ndim != 3 or dC.shape[1:] != (N, N):
             raise ValueError('covariances must have shape (T, %d, %d)' % (N, N))
         T = dC.shape[0]
-        out = self._out(out, (T, self.Q))
+        out = _check_out(out, (T, self.Q))
         if T == 0 or self.Q == 0:
             return out
         slab = self._slab(T, (self.Q + N * N) * 8)      # the covariances of a slab go up with it, not all T at once
@@ -754,6 +704,12 @@ class ResidentGrid(object):
         inner = int(np.prod(self.shape[axis + 1:], dtype=np.int64))
         return axis, outer, int(self.shape[axis]), inner
 
+    def _rest(self, times, axis):
+        """(axis, shape) of the column maps of peak and integrate: `axis` as _columns checks it, (len(times),) + the grid
+        shape without that axis."""
+        axis = self._columns(axis)[0]
+        return axis, (len(times),) + tuple(self.shape[:axis]) + tuple(self.shape[axis + 1:])
+
     def evaluate_peaks(self, C, axis=-1, kind='max', out=None):
         """(value, index) of the peak of the density of coefficient row C[t] along `axis` of the grid, column by column:
         value (T, M) float64 and index (T, M) int32, M = Q / L columns in C order of the remaining axes - np.nanmax
@@ -766,16 +722,13 @@ class ResidentGrid(object):
         M = outer * inner
         C = self._coeffs(C)
         T = C.shape[0]
-        if out is None:
-            val, idx = np.empty((T, M), dtype=np.float64), np.empty((T, M), dtype=np.int32)
-        else:
-            try:
-                val, idx = out
-            except (TypeError, ValueError):
-                raise ValueError('out must be a pair (value, index) of arrays')
-            for a, dtype in ((val, np.float64), (idx, np.int32)):
-                if not isinstance(a, np.ndarray) or a.shape != (T, M) or a.dtype != dtype or not a.flags.c_contiguous:
-                    raise ValueError('out must be C-contiguous arrays of shape (%d, %d): value float64, index int32' % (T, M))
+        try:
+            val, idx = (None, None) if out is None else out
+            if out is not None and (val is None or idx is None):
+                raise TypeError
+        except (TypeError, ValueError):
+            raise ValueError('out must be a pair (value, index) of arrays')
+        val, idx = _check_out(val, (T, M)), _check_out(idx, (T, M), np.int32)
         if T == 0 or self.Q == 0:
             val.fill(np.nan)                # (columns of length zero: nothing to select)
             idx.fill(-1)
@@ -793,9 +746,8 @@ class ResidentGrid(object):
         """Peak maps for a list of datetimes (coefficients of Estimate.get_C per time, as __call__ takes them): (value, index),
         each (len(times),) + the grid shape without `axis`.  On a (lat, lon, alt) grid with the default axis: the peak of the
         parameter along altitude and the altitude index where it sits."""
-        axis, _, _, _ = self._columns(axis)
+        axis, rest = self._rest(times, axis)
         val, idx = self.evaluate_peaks(self._coeffs_at(times), axis=axis, kind=kind)
-        rest = (len(times),) + tuple(self.shape[:axis]) + tuple(self.shape[axis + 1:])
         return val.reshape(rest), idx.reshape(rest)
 
     @staticmethod
@@ -815,7 +767,6 @@ class ResidentGrid(object):
         dYr = self._reduced.get(key)
         if dYr is None:
             ctx = self.est.model.ctx
-            dw = None
             while len(self._reduced) >= REDUCED_BASES:          # the oldest entry goes: weights that change with every call
                 self._reduced.pop(next(iter(self._reduced))).free()
             nbytes = self.est.model.nbasis * outer * inner * 8
@@ -823,19 +774,12 @@ class ResidentGrid(object):
             if nbytes > 0.9 * free:
                 raise MemoryError('reduced basis of %d columns x %d functions (%.1f GB) does not fit the device (%.1f GB free)'
                                   % (outer * inner, self.est.model.nbasis, nbytes / 1e9, free / 1e9))
-            dYr = ctx.empty((self.est.model.nbasis, outer * inner))
-            try:
-                dw = ctx.to_device(w)
+            with ctx.scope() as dev:
+                dYr, dw = dev.empty((self.est.model.nbasis, outer * inner)), dev.up(w)
                 _lib.check(_lib.lib.vi_reduce_basis_f64(self.est.model.handle(), outer, L, inner, self.dY.ptr, dw.ptr, dYr.ptr),
                            'vi_reduce_basis_f64')
                 ctx.sync()
-            except BaseException:
-                dYr.free()
-                raise
-            finally:
-                if dw is not None:
-                    dw.free()
-            self._reduced[key] = dYr
+                self._reduced[key] = dev.detach(dYr)        # the set-up succeeded: the grid's until close()
         return dYr
 
     def evaluate_integrals(self, C, weights=None, axis=-1, out=None):
@@ -858,8 +802,7 @@ class ResidentGrid(object):
     def integrate(self, times, weights=None, axis=-1):
         """Weighted column sums for a list of datetimes (coefficients of Estimate.get_C per time): (len(times),) + the grid
         shape without `axis`; see evaluate_integrals."""
-        axis, _, _, _ = self._columns(axis)
-        rest = (len(times),) + tuple(self.shape[:axis]) + tuple(self.shape[axis + 1:])
+        axis, rest = self._rest(times, axis)
         return self.evaluate_integrals(self._coeffs_at(times), weights=weights, axis=axis).reshape(rest)
 
     def close(self):

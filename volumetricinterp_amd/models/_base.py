@@ -45,28 +45,31 @@ class DeviceModel(object):
             pass
         self._handle = None
 
-    def _upload_coords(self, gdlat, gdlon, gdalt):
-        ctx = self.ctx
-        return tuple(ctx.to_device(np.asarray(a, dtype=np.float64).ravel()) for a in (gdlat, gdlon, gdalt))
+    @staticmethod
+    def _upload_coords(dev, gdlat, gdlon, gdalt):
+        """Device copies of the raveled coordinates in the scope `dev`."""
+        return tuple(dev.up(np.asarray(a, dtype=np.float64).ravel()) for a in (gdlat, gdlon, gdalt))
 
     def _transform(self, gdlat, gdlon, gdalt):
         """Three (P,) arrays: (z, theta, phi) for sphharmlag, ECEF (x, y, z) for radbasfun."""
         h = self.handle()
         P = np.asarray(gdlat).size
-        dlat, dlon, dalt = self._upload_coords(gdlat, gdlon, gdalt)
-        out = [self._ctx.empty(P) for _ in range(3)]
-        _lib.check(_lib.lib.vi_transform_f64(h, P, dlat.ptr, dlon.ptr, dalt.ptr, out[0].ptr, out[1].ptr, out[2].ptr),
-                   'vi_transform_f64')
-        return [o.download() for o in out]
+        with self._ctx.scope() as dev:
+            dlat, dlon, dalt = self._upload_coords(dev, gdlat, gdlon, gdalt)
+            out = [dev.empty(P) for _ in range(3)]
+            _lib.check(_lib.lib.vi_transform_f64(h, P, dlat.ptr, dlon.ptr, dalt.ptr, out[0].ptr, out[1].ptr, out[2].ptr),
+                       'vi_transform_f64')
+            return [o.download() for o in out]
 
     def basis_device(self, dlat, dlon, dalt, P, transposed=False):
         """A on the device: (P, N) row-major, or the N x P layout the fit kernels consume."""
         h = self.handle()
         N = self.nbasis
-        dA = self._ctx.empty((N, P) if transposed else (P, N))
         ld_p, ld_n = (1, P) if transposed else (N, 1)
-        _lib.check(_lib.lib.vi_basis_f64(h, P, dlat.ptr, dlon.ptr, dalt.ptr, dA.ptr, ld_p, ld_n), 'vi_basis_f64')
-        return dA
+        with self._ctx.scope() as dev:
+            dA = dev.empty((N, P) if transposed else (P, N))
+            _lib.check(_lib.lib.vi_basis_f64(h, P, dlat.ptr, dlon.ptr, dalt.ptr, dA.ptr, ld_p, ld_n), 'vi_basis_f64')
+            return dev.detach(dA)                           # the caller's from here
 
     def basis(self, gdlat, gdlon, gdalt):
         """Model.basis of the reference (sphharmlag.py:118-145, radbasfun.py:83-112): shape + (nbasis,)."""
@@ -74,6 +77,10 @@ class DeviceModel(object):
         P = gdlat.size
         if P == 0:
             return np.zeros(gdlat.shape + (self.nbasis,))
-        dlat, dlon, dalt = self._upload_coords(gdlat, gdlon, gdalt)
-        A = self.basis_device(dlat, dlon, dalt, P).download()
-        return A.reshape(gdlat.shape + (self.nbasis,))
+        with self.ctx.scope() as dev:
+            dlat, dlon, dalt = self._upload_coords(dev, gdlat, gdlon, gdalt)
+            dA = self.basis_device(dlat, dlon, dalt, P)     # ours to free
+            try:
+                return dA.download().reshape(gdlat.shape + (self.nbasis,))
+            finally:
+                dA.free()

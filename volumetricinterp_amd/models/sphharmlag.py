@@ -212,11 +212,12 @@ class Model(DeviceModel):
         if P == 0:
             return np.zeros((0, 3, N))
         h = self.handle()
-        dlat, dlon, dalt = self._upload_coords(gdlat, gdlon, gdalt)
-        dG = self._ctx.empty((P, 3, N))
-        _lib.check(_lib.lib.vi_grad_basis_f64(h, P, dlat.ptr, dlon.ptr, dalt.ptr, dG.ptr, 3 * N, N, 1),
-                   'vi_grad_basis_f64')
-        return dG.download()
+        with self._ctx.scope() as dev:
+            dlat, dlon, dalt = self._upload_coords(dev, gdlat, gdlon, gdalt)
+            dG = dev.empty((P, 3, N))
+            _lib.check(_lib.lib.vi_grad_basis_f64(h, P, dlat.ptr, dlon.ptr, dalt.ptr, dG.ptr, 3 * N, N, 1),
+                       'vi_grad_basis_f64')
+            return dG.download()
 
     def gradient_frame(self, gdlat, gdlon, gdalt):
         """(P, 3, 3) matrices M with g_enu = M @ g_model: the components of a gradient along the model coordinates
