@@ -278,8 +278,14 @@ __global__ __launch_bounds__(IT <= 1 ? 768 : 512) void k_brent_warm(
             __syncthreads();
             BR_STAMP(1);
             // ---- the truncated solve in the rotated system (the K3 kernel's body)
-            jacobi_system_call<IT>(lds_raw, N, Xs, 1.0 / f, yt + slot * N, rcond, abs_floor, cp, logp, max_sweeps, shi + 1, shi + 2,
-                                   round_acc);
+            // (three super-blocks per thread: inlined - through the out-of-line copy the solutions changed from one function
+            //  value of a record to the next, and the roots were wrong; tests/test_gpu_brent_geometry.py)
+            if constexpr (IT == 3)
+                jacobi_system<3>(lds_raw, N, Xs, 1.0 / f, yt + slot * N, rcond, abs_floor, cp, nullptr, logp, max_sweeps, shi + 1,
+                                 nullptr, 0, shi + 2, round_acc);
+            else
+                jacobi_system_call<IT>(lds_raw, N, Xs, 1.0 / f, yt + slot * N, rcond, abs_floor, cp, logp, max_sweeps, shi + 1,
+                                       shi + 2, round_acc);
             __syncthreads();
             BR_STAMP(2);
 #ifdef VI_STAMPS
@@ -411,8 +417,11 @@ void brent_geometry(int N, int& threads, int& it)
 }
 
 // LDS of a k_brent_warm workgroup: the Jacobi image (or the product scratch of a re-basing, whichever is larger), the
-// coefficients, the chi^2 reduction tree, one partial sum per block of 256 data points, the state.
+// coefficients, the chi^2 reduction tree, one partial sum per block of 256 data points, the state - and the static LDS the
+// compiler gives the kernel beside the dynamic allocation (the word the block-wide votes of the solver go through, padded):
+// left out, the largest records of N = 189 ... 192 passed vi_brent_warm_supported and the launch then refused its LDS size.
 constexpr size_t VI_LDS_BYTES_PER_CU = 160 * 1024;
+constexpr size_t BRENT_STATIC_LDS = 256;
 size_t brent_lds_bytes(int N, int64_t P, size_t* ldsj_eff, int* npart)
 {
     const size_t ldsj = (vi_jacobi_lds_bytes(N) + 15) & ~(size_t)15;
@@ -422,7 +431,7 @@ size_t brent_lds_bytes(int N, int64_t P, size_t* ldsj_eff, int* npart)
     const int64_t np = nb < 64 ? 64 : ((nb + 1) & ~(int64_t)1);
     if (ldsj_eff) *ldsj_eff = eff;
     if (npart) *npart = (int)(np > (1 << 20) ? (1 << 20) : np);
-    return eff + ((size_t)((N + 1) & ~1) + 768 + (size_t)np + 16) * sizeof(double) + sizeof(BrentState) + 64;
+    return BRENT_STATIC_LDS + eff + ((size_t)((N + 1) & ~1) + 768 + (size_t)np + 16) * sizeof(double) + sizeof(BrentState) + 64;
 }
 
 }  // namespace
@@ -580,10 +589,11 @@ extern "C" int vi_brent_warm_f64(vi_ctx* c, int64_t ntask, int32_t N, int64_t P,
         return VI_ERR_UNSUPPORTED;
     }
     int npart;
-    const size_t shm = brent_lds_bytes(N, P, &ldsj_eff, &npart);
-    if (shm > VI_LDS_BYTES_PER_CU) {
+    const size_t lds_all = brent_lds_bytes(N, P, &ldsj_eff, &npart);
+    const size_t shm = lds_all - BRENT_STATIC_LDS;                   // the dynamic part
+    if (lds_all > VI_LDS_BYTES_PER_CU) {
         vi_set_error("vi_brent_warm_f64: %lld data points per record need %zu bytes of LDS (the chi^2 partial sums of a record "
-                     "sit beside its rotated system); the host-driven iteration has no such limit", (long long)P, shm);
+                     "sit beside its rotated system); the host-driven iteration has no such limit", (long long)P, lds_all);
         return VI_ERR_UNSUPPORTED;
     }
     VI_HIP(hipSetDevice(c->device));
@@ -608,6 +618,13 @@ extern "C" int vi_brent_warm_f64(vi_ctx* c, int64_t ntask, int32_t N, int64_t P,
     VI_HIP(hipMemsetAsync(queue, 0, sizeof(int), c->stream));
 #define VI_B(ITV)                                                                                                             \
     do {                                                                                                                      \
+        hipFuncAttributes fattr;                                                                                              \
+        VI_HIP(hipFuncGetAttributes(&fattr, (const void*)k_brent_warm<ITV>));                                                 \
+        if (fattr.sharedSizeBytes > BRENT_STATIC_LDS) {                                                                       \
+            vi_set_error("vi_brent_warm_f64: the kernel has %zu bytes of static LDS, BRENT_STATIC_LDS says %zu",             \
+                         (size_t)fattr.sharedSizeBytes, BRENT_STATIC_LDS);                                                    \
+            return VI_ERR_UNSUPPORTED;                                                                                        \
+        }                                                                                                                     \
         VI_HIP(hipFuncSetAttribute((const void*)k_brent_warm<ITV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));    \
         hipLaunchKernelGGL(k_brent_warm<ITV>, dim3((unsigned)nwg), dim3(threads), shm, c->stream, N, P, (int)ntask, d_D1, d_D2, \
                            d_yt, d_V, d_AWA, d_R, d_y, rr, VwW, VnW, d_At, d_W, d_b, d_rec, d_slot, d_xa, d_xb, d_fa, d_fb, d_nu, rcond, abs_floor,          \

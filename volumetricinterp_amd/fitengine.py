@@ -285,7 +285,10 @@ class FitEngine(object):
     def warm_enabled(self):
         if os.environ.get('VINTERP_WARM', '1') == '0':
             return False
-        return 8 <= self.N <= 180
+        # up to the last order at which every kernel of the rotated-system search keeps its system in a CU's LDS: the in-LDS
+        # solver itself reaches 196, the device-side root finder (k_brent_warm: the system, the re-basing panels and the chi^2
+        # partial sums side by side) 192.  It used to end at 180, the solver's range before its three-super-block kernel.
+        return 8 <= self.N <= 192
 
     SHARED_WALK_MIN_RECORDS = 8
 
@@ -839,7 +842,7 @@ class FitEngine(object):
     def default_prefetch(self):
         # walk prefetch: the whole alpha = 0 .. -101 table in one launch for a single record (latency-bound), a few steps
         # ahead for large batches (the launch is already full; don't waste solves).  Also beyond the in-LDS solver
-        # (N > 180, rocSOLVER syevd): its batched form costs 10.6 ms per system in launches of 4 but 2.7 ms in launches of
+        # (N > 196, rocSOLVER syevd): its batched form costs 10.6 ms per system in launches of 4 but 2.7 ms in launches of
         # 64 or more - one syevd at N = 1152 is ~900 small dependent kernels, and only a batch fills the GPU - so a
         # single N = 1152 record takes 481 ms with the whole walk in one launch against 1164 ms four values at a time
         # (measured; running several syevd calls from concurrent host threads instead made it slower, 1460 ms).
@@ -864,7 +867,7 @@ class FitEngine(object):
         # refused round costs one launch (measured at N = 144, where the indefinite curvature matrix puts poles of
         # chi^2 inside most brackets and the guard refuses: T = 1  38.0 vs 39.4 ms, T = 2  84 vs 94, T = 8  121 vs
         # 117, T = 16  153 vs 145 - the refused round also sets up the rotated system Brent then uses).
-        # Only where the in-LDS solver serves the rounds: at orders beyond it (N > 180, rocSOLVER, ~0.15 s per solve
+        # Only where the in-LDS solver serves the rounds: at orders beyond it (N > 196, rocSOLVER, ~0.15 s per solve
         # at N = 1152) K extra solves per round are far dearer than Brent's dependent ones.
         # Not at the default order and beyond (N >= 100): there the guard refuses on most brackets and the attempt is pure
         # cost - one launch of 254 warm systems, 3.1 ms of a 28.6 ms single-record fit (bench.py, 25.5 ms without it; the
