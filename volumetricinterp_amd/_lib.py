@@ -270,9 +270,13 @@ class DeviceArray:
         check(lib.vi_h2d(self.ctx.handle, self.ptr, host.ctypes.data_as(VOIDP), host.nbytes), 'vi_h2d')
         return self
 
-    def download(self):
-        out = np.empty(self.shape, dtype=self.dtype)
-        check(lib.vi_d2h(self.ctx.handle, out.ctypes.data_as(VOIDP), self.ptr, self.nbytes), 'vi_d2h')
+    def download(self, n=None, offset=0, out=None):
+        """Host copy of the allocation; or of its first n elements (n: a count or a shape) from element `offset` on; or
+        of as many as fill `out`, a C-contiguous array of the buffer's dtype, written in place."""
+        if out is None:
+            out = np.empty(self.shape if n is None else n, dtype=self.dtype)
+        check(lib.vi_d2h(self.ctx.handle, out.ctypes.data_as(VOIDP), self.offset_ptr(offset) if offset else self.ptr, out.nbytes),
+              'vi_d2h')
         return out
 
     def offset_ptr(self, nelem):

@@ -441,13 +441,86 @@ def chi2_search_gen(npts, multisection=0, refine=False, prefetch=1, defer_brent=
                                                      iterations=iters, finder=finder, other_end=other_end)
 
 
+class BrentPhase(object):
+    """Brent's iteration of the records of a batch, for both drivers: the brackets the walks end on, the records handed
+    to a brent_solver and the BrentBatch that iterates the rest.  results: the driver's list, a finished record's entry is
+    written here; cache[i]: {log10 alpha: chi^2} of record i (run_batched shares the walk's, chi^2 being memoised per
+    record as in the coroutine; the table driver's is the phase's own); nevals counts what a solver evaluated."""
+
+    def __init__(self, T, results, solver=None, cache=None):
+        self.batch = BrentBatch(T)
+        self.brackets, self.deferred = {}, {}
+        self.nu_arr = np.zeros(T)
+        self.results, self.solver = results, solver
+        self.cache = [dict() for _ in range(T)] if cache is None else cache
+        self.nevals = 0
+
+    def busy(self):
+        return bool(self.deferred) or bool(self.batch.active.any())
+
+    def admit(self, i, b):
+        """Record i's walk ended on bracket b: to the solver's hand-off, or - no solver, or an end that is a zero - here."""
+        self.brackets[i] = b
+        self.nu_arr[i] = b['nu']
+        if self.solver is not None and b['val'] != 0 and b['val0'] != 0:
+            self.deferred[i] = b                # iterated with all the others once the walks are over
+        else:
+            self._add(i, b)
+
+    def _add(self, i, b):
+        self.batch.add(i, b['alpha'], b['alpha0'], b['val'], b['val0'], jump=jump_rule(b['nu']))
+        self._finish((i,))
+
+    def _finish(self, ids):
+        for i in ids:
+            if i in self.batch.results:
+                root, iters, _, other_end = self.batch.results.pop(i)
+                b = self.brackets.pop(i)
+                info = dict(sf=b['sf'], bracket=(b['alpha'], b['alpha0']), log10_alpha=root, iterations=iters,
+                            finder='brentq', other_end=other_end)
+                if b.get('walk_redone_exact'):
+                    info['walk_redone_exact'] = True
+                self.results[i] = ('root', float(np.power(10., root)), info)
+
+    def hand_off(self):
+        """The deferred records to the solver, in one call; a record it answers None for is iterated here."""
+        ids = sorted(self.deferred)
+        for i, r_ in zip(ids, self.solver(ids, [self.deferred[i] for i in ids])):
+            b = self.deferred.pop(i)
+            if r_ is None:
+                self._add(i, b)
+            else:
+                self.batch.results[i] = r_
+                self.nevals += int(r_[2])
+                self._finish((i,))
+
+    def requests(self):
+        """(records, abscissae) whose chi^2 is wanted, after the requests whose value is known already have been fed."""
+        while True:
+            idx, xs = self.batch.requests()
+            hit = [(int(i), x) for i, x in zip(idx.tolist(), xs.tolist()) if x in self.cache[int(i)]]
+            if not hit:
+                return idx, xs
+            ii = np.array([i for i, _ in hit])
+            self.batch.feed(ii, np.array([self.cache[i][x] - self.nu_arr[i] for i, x in hit]))
+            self._finish(i for i, _ in hit)
+
+    def feed(self, idx, xs, chi2):
+        """chi^2 at the abscissae requests() returned."""
+        chi2 = np.asarray(chi2, dtype=np.float64)
+        for i, x, c in zip(idx.tolist(), xs.tolist(), chi2.tolist()):
+            self.cache[i][x] = c
+        self.batch.feed(idx, chi2 - self.nu_arr[idx])
+        self._finish(idx.tolist())
+
+
 def run_batched(npts_list, chi2_batch, prefetch=8, multisection=0, refine=False, vector_brent=True, brent_solver=None):
     """Drive one search coroutine per record against a batched chi^2 evaluator.
 
     npts_list[i]: number of finite data points of record i (``len(b)``, interpolate.py:175), or None to
     skip the record (result NaN).  chi2_batch(rec_idx: int array, log10_alpha: float array) -> chi^2 array; with
     refine (see chi2_search_gen) it is also called as chi2_batch(rec, log10_alpha, exact: bool array).
-    vector_brent: Brent's iteration of all records on arrays (BrentBatch) instead of one coroutine step per record and
+    vector_brent: Brent's iteration of all records on arrays (BrentPhase) instead of one coroutine step per record and
     round; same iterates, same answers.
     brent_solver(records, brackets) -> list of (root, iterations, funcalls, other_end) or None per record: Brent's whole
     iteration for many records at once somewhere else (FitEngine: one kernel launch, a workgroup per record).  It is
@@ -455,14 +528,11 @@ def run_batched(npts_list, chi2_batch, prefetch=8, multisection=0, refine=False,
     Returns (alpha list, outcome list, info list, number of chi^2 evaluations).
     """
     T = len(npts_list)
-    brent = BrentBatch(T) if (vector_brent or brent_solver is not None) else None
-    brackets = {}
-    deferred = {}
-    nu_arr = np.zeros(T)
     gens, pending = {}, {}
     cache = [dict() for _ in range(T)]
     cache_x = [dict() for _ in range(T)]
     results = [(None, float('nan'), {})] * T
+    brent = BrentPhase(T, results, brent_solver, cache) if (vector_brent or brent_solver is not None) else None
     nevals = 0
     for i, n in enumerate(npts_list):
         if n is None:
@@ -472,29 +542,13 @@ def run_batched(npts_list, chi2_batch, prefetch=8, multisection=0, refine=False,
         gens[i] = g
         pending[i] = next(g)
 
-    def finish_brent(i):
-        root, iters, _, other_end = brent.results.pop(i)
-        b = brackets.pop(i)
-        info = dict(sf=b['sf'], bracket=(b['alpha'], b['alpha0']), log10_alpha=root, iterations=iters, finder='brentq',
-                    other_end=other_end)
-        if b.get('walk_redone_exact'):
-            info['walk_redone_exact'] = True
-        results[i] = ('root', float(np.power(10., root)), info)
-
     def advance(i, value):
         try:
             pending[i] = gens[i].send(value)
         except StopIteration as stop:
             del gens[i], pending[i]
             if stop.value[0] == 'bracket':          # the walk is done: Brent's iteration goes on in the batch
-                b = brackets[i] = stop.value[2]
-                nu_arr[i] = b['nu']
-                if brent_solver is not None and b['val'] != 0 and b['val0'] != 0:
-                    deferred[i] = b                 # iterated with all the others once the walks are over
-                    return
-                brent.add(i, b['alpha'], b['alpha0'], b['val'], b['val0'], jump=jump_rule(b['nu']))
-                if i in brent.results:
-                    finish_brent(i)
+                brent.admit(i, stop.value[2])
             else:
                 results[i] = stop.value
 
@@ -513,41 +567,20 @@ def run_batched(npts_list, chi2_batch, prefetch=8, multisection=0, refine=False,
             else:
                 return
 
-    def serve_brent():
-        # Brent requests whose value is already known (chi^2 is memoised per record, as in the coroutine)
-        while True:
-            idx, xs = brent.requests()
-            hit = [(int(i), x) for i, x in zip(idx.tolist(), xs.tolist()) if x in cache[int(i)]]
-            if not hit:
-                return idx, xs
-            ii = np.array([i for i, _ in hit])
-            brent.feed(ii, np.array([cache[i][x] - brackets[i]['nu'] for i, x in hit]))
-            for i, _ in hit:
-                if i in brent.results:
-                    finish_brent(i)
-
     for i in list(gens):
         serve(i)
-    while gens or deferred or (brent is not None and brent.active.any()):
-        if deferred and not gens:
-            ids = sorted(deferred)
-            for i, r_ in zip(ids, brent_solver(ids, [deferred[i] for i in ids])):
-                b = deferred.pop(i)
-                if r_ is None:
-                    brent.add(i, b['alpha'], b['alpha0'], b['val'], b['val0'], jump=jump_rule(b['nu']))
-                else:
-                    brent.results[i] = r_
-                    nevals += int(r_[2])
-                if i in brent.results:
-                    finish_brent(i)
+    while gens or (brent is not None and brent.busy()):
+        if brent is not None and brent.deferred and not gens:
+            brent.hand_off()
             continue
         rec, alp, exact = [], [], []
-        bidx = None
-        if brent is not None and brent.active.any():
-            bidx, bxs = serve_brent()
+        nb = 0
+        if brent is not None and brent.batch.active.any():
+            bidx, bxs = brent.requests()
+            nb = len(bidx)
             rec += bidx.tolist()
             alp += bxs.tolist()
-            exact += [False] * len(bidx)
+            exact += [False] * nb
             if not rec and not gens:
                 break
         for i, a in pending.items():
@@ -563,24 +596,17 @@ def run_batched(npts_list, chi2_batch, prefetch=8, multisection=0, refine=False,
             exact.append(False)
             rec.append(i)
             alp.append(a)
-        if any(exact):
-            vals = chi2_batch(np.asarray(rec, dtype=np.int32), np.asarray(alp, dtype=np.float64),
-                              np.asarray(exact, dtype=bool))
-        else:
-            vals = chi2_batch(np.asarray(rec, dtype=np.int32), np.asarray(alp, dtype=np.float64))
+        vals = np.asarray(chi2_batch(np.asarray(rec, dtype=np.int32), np.asarray(alp, dtype=np.float64),
+                                     *([np.asarray(exact, dtype=bool)] if any(exact) else [])), dtype=np.float64)
         nevals += len(rec)
-        for i, a, v, ex in zip(rec, alp, np.asarray(vals, dtype=np.float64).tolist(), exact):
+        for i, a, v, ex in zip(rec[nb:], alp[nb:], vals[nb:].tolist(), exact[nb:]):
             (cache_x[i] if ex else cache[i])[a] = v
-        if bidx is not None and len(bidx):
-            nb = len(bidx)
-            fv = np.asarray(vals[:nb], dtype=np.float64) - nu_arr[bidx]
-            brent.feed(bidx, fv)
-            for i in bidx.tolist():
-                if i in brent.results:
-                    finish_brent(i)
+        if nb:
+            brent.feed(bidx, bxs, vals[:nb])
         for i in list(pending):             # every pending record had a request in this batch
             serve(i)
-    return ([r[1] for r in results], [r[0] for r in results], [r[2] for r in results], nevals)
+    return ([r[1] for r in results], [r[0] for r in results], [r[2] for r in results],
+            nevals + (brent.nevals if brent is not None else 0))
 
 
 def run_table_batched(npts_list, chi2_batch, prefetch=8, refine=False, brent_solver=None):
@@ -758,59 +784,18 @@ def run_table_batched(npts_list, chi2_batch, prefetch=8, refine=False, brent_sol
                             walking[i] = todo[i] = False
         request(want_plain, want_exact)
 
-    # ---- Brent's iteration (as in run_batched)
-    brent = BrentBatch(T)
-    nu_arr = np.zeros(T)
-    deferred = {}
-    bcache = {}
-
-    def finish_brent(i):
-        root, iters, _, other_end = brent.results.pop(i)
-        b = brackets.pop(i)
-        info = dict(sf=b['sf'], bracket=(b['alpha'], b['alpha0']), log10_alpha=root, iterations=iters, finder='brentq',
-                    other_end=other_end)
-        if b.get('walk_redone_exact'):
-            info['walk_redone_exact'] = True
-        results[i] = ('root', float(np.power(10., root)), info)
-
+    # ---- Brent's iteration, after the walks; its cache is its own
+    brent = BrentPhase(T, results, brent_solver)
     for i in sorted(brackets):
-        b = brackets[i]
-        nu_arr[i] = b['nu']
-        if brent_solver is not None and b['val'] != 0 and b['val0'] != 0:
-            deferred[i] = b
-            continue
-        brent.add(i, b['alpha'], b['alpha0'], b['val'], b['val0'], jump=jump_rule(b['nu']))
-        if i in brent.results:
-            finish_brent(i)
-    if deferred:
-        ids = sorted(deferred)
-        for i, r_ in zip(ids, brent_solver(ids, [deferred[i] for i in ids])):
-            b = deferred.pop(i)
-            if r_ is None:
-                brent.add(i, b['alpha'], b['alpha0'], b['val'], b['val0'], jump=jump_rule(b['nu']))
-            else:
-                brent.results[i] = r_
-                nevals += int(r_[2])
-            if i in brent.results:
-                finish_brent(i)
-    while brent.active.any():
+        brent.admit(i, brackets[i])
+    if brent.deferred:
+        brent.hand_off()
+    while brent.batch.active.any():
         idx, xs = brent.requests()
-        hit = [(int(i), x) for i, x in zip(idx.tolist(), xs.tolist()) if x in bcache.get(int(i), ())]
-        if hit:
-            brent.feed(np.array([i for i, _ in hit]), np.array([bcache[i][x] - nu_arr[i] for i, x in hit]))
-            for i, _ in hit:
-                if i in brent.results:
-                    finish_brent(i)
-            continue
-        vals = np.asarray(chi2_batch(idx.astype(np.int32), np.asarray(xs, dtype=np.float64)), dtype=np.float64)
-        nevals += len(idx)
-        for i, x, c in zip(idx.tolist(), xs.tolist(), vals.tolist()):
-            bcache.setdefault(i, {})[x] = c
-        brent.feed(idx, vals - nu_arr[idx])
-        for i in idx.tolist():
-            if i in brent.results:
-                finish_brent(i)
-    return ([r[1] for r in results], [r[0] for r in results], [r[2] for r in results], nevals)
+        if len(idx):
+            brent.feed(idx, xs, chi2_batch(idx.astype(np.int32), np.asarray(xs, dtype=np.float64)))
+            nevals += len(idx)
+    return ([r[1] for r in results], [r[0] for r in results], [r[2] for r in results], nevals + brent.nevals)
 
 
 POLISH_XTOL = 1e-7            # decades: a sign change confined to less than this without |f| getting small is a jump

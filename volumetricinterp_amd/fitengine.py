@@ -20,8 +20,11 @@ Device-side engine behind ``Interpolate.calc_coeffs`` / ``eval_C`` /
   the same matrix are solved once; a record fitted alone decomposes the candidate
   bracket bases in the launch of its walk; a big batch runs as concurrent pipelines.
   None of this changes a record's numbers with the batch it is fitted in, bit for bit.
+  A round of search requests is served in named steps: _route sorts it into cold / shared / warm / rebase,
+  _ensure_rotated and _reference_bases set up the bases, _launch_* solve, _resolve_unconverged redoes what the sweep cap ended.
 """
 import ctypes as C
+import functools
 import math
 import os
 import threading
@@ -74,6 +77,13 @@ _lib._sig('vi_brent_host_one_f64', C.c_int, _lib.VOIDP, C.c_int32, C.c_int64, *(
           C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _lib.VOIDP, _lib.VOIDP)
 _lib._sig('vi_brent_warm_supported', C.c_int, C.c_int32, C.c_int64)
 _lib.EXPORTS += ['vi_brent_warm_supported', 'vi_brent_host_one_f64', 'vi_brent_warm_f64', 'vi_exp10_f64', 'vi_max_sweeps', 'vi_cold_max_sweeps', 'vi_qr_similarity_f64', 'vi_rotation_log_bytes', 'vi_decompose_f64', 'vi_warm_finish_f64', 'vi_warm_rebase_f64', 'vi_reg_floor_f64', 'vi_basis_solve_f64', 'vi_warm_chi2_one_f64', 'vi_gcv_terms_f64', 'vi_warm_prepare_f64', 'vi_warm_solve_f64', 'vi_eigvals_f64', 'vi_normal_eq_f64', 'vi_form_system_f64', 'vi_solve_trunc_f64', 'vi_chi2_f64', 'vi_cov_f64']
+
+
+
+def _flag(name, default='1'):
+    """The switch VINTERP_<name>: on unless it is '0'.  Read at every call (tests change the switches between fits)."""
+    return os.environ.get('VINTERP_' + name, default) != '0'
+
 
 MAX_BATCH = 8192          # systems per solver launch (N=144: 1.3 GB of X)
 
@@ -145,6 +155,9 @@ class FitEngine(object):
             cur = _lib.DeviceArray(self.ctx, (max(n, 1),), dtype)
             self._bufs[name] = cur
         return cur
+
+    def _count(self, key, n=1):
+        self.stats[key] = self.stats.get(key, 0) + n
 
     # ------------------------------------------------------------------------------------------
     def upload_records(self, W, b):
@@ -224,11 +237,7 @@ class FitEngine(object):
     def normal_equations(self):
         """Host copies of A^T W A (T,N,N) and A^T W b (T,N) (for stage-wise parity tests)."""
         T, N = self.T, self.N
-        AWA = np.empty((T, N, N))
-        y = np.empty((T, N))
-        _lib.check(_lib.lib.vi_d2h(self.ctx.handle, AWA.ctypes.data_as(_lib.VOIDP), self.dAWA.ptr, AWA.nbytes), 'd2h')
-        _lib.check(_lib.lib.vi_d2h(self.ctx.handle, y.ctypes.data_as(_lib.VOIDP), self.dy.ptr, y.nbytes), 'd2h')
-        return AWA, y
+        return self.dAWA.download((T, N, N)), self.dy.download((T, N))
 
     def _solve_chunk(self, rec, alphas, want_H, tag):
         """Form and solve B systems; returns device C (B,N) [and H (B,N,N)]."""
@@ -275,15 +284,13 @@ class FitEngine(object):
             dchi = self._buf('s_chi2', (B,))
             _lib.check(_lib.lib.vi_chi2_f64(self.ctx.handle, B, self.P, self.N, self.At.ptr, dC.ptr, drec.ptr,
                                             self.dW.ptr, self.db.ptr, dchi.ptr), 'vi_chi2_f64')
-            tmp = np.empty(B)
-            _lib.check(_lib.lib.vi_d2h(self.ctx.handle, tmp.ctypes.data_as(_lib.VOIDP), dchi.ptr, tmp.nbytes), 'd2h')
-            out[s:e] = tmp
+            dchi.download(out=out[s:e])
         return out
 
     # ------------------------------------------------------------------------------------------
     # ---- warm-started chi^2 evaluation for the Brent phase ------------------------------------------
     def warm_enabled(self):
-        if os.environ.get('VINTERP_WARM', '1') == '0':
+        if not _flag('WARM'):
             return False
         # up to the last order at which every kernel of the rotated-system search keeps its system in a CU's LDS: the in-LDS
         # solver itself reaches 196, the device-side root finder (k_brent_warm: the system, the re-basing panels and the chi^2
@@ -297,7 +304,7 @@ class FitEngine(object):
         # (mean weights of the batch) and then 1-4 sweeps per record instead of 8-24.  The reference costs as much as one
         # more record and an extra launch in front of the first walk round, so it needs a few records to pay.
         return (self.warm_enabled() and self.T >= self.SHARED_WALK_MIN_RECORDS and len(self.regularization_list) == 1
-                and os.environ.get('VINTERP_SHAREDWALK', '1') != '0')
+                and _flag('SHAREDWALK'))
 
     def _find_same_below(self, name):
         """Per record: the largest integer k with 10^k below the alpha at which alpha R drops out of AWA + alpha R to
@@ -308,8 +315,7 @@ class FitEngine(object):
         dfl = self._buf('regfloor', (T,))
         _lib.check(_lib.lib.vi_reg_floor_f64(self.ctx.handle, T, N, self.dAWA.ptr, self.R[name].ptr, dfl.ptr),
                    'vi_reg_floor_f64')
-        fl = np.empty(T)
-        _lib.check(_lib.lib.vi_d2h(self.ctx.handle, fl.ctypes.data_as(_lib.VOIDP), dfl.ptr, fl.nbytes), 'd2h')
+        fl = dfl.download(T)
         k = np.full(T, -1000.)
         ok = np.isfinite(fl) & (fl > 0) & (fl < 1e300)
         k[ok] = np.ceil(np.log10(fl[ok])) - 1.
@@ -334,7 +340,7 @@ class FitEngine(object):
         one) and the record's rotated system still sits at the middle of the bracket: move it here, once
         (vi_warm_rebase_f64).  The rule looks at the record's own requests only, so what a record sees does not depend on
         the batch it is in."""
-        if os.environ.get('VINTERP_REBASE', '1') == '0':
+        if not _flag('REBASE'):
             return False
         last = self._last_x.get(r)
         if last is None:
@@ -347,16 +353,16 @@ class FitEngine(object):
         # chi^2 (an eigenvalue of X(alpha) at the cut), Brent bisects down to 2e-12 in 40-60 steps there, and from a basis
         # 1e-3 decades away those solves take 13 sweeps each
         return (done == len(sched) and self._nreq.get(r, 0) >= self.REBASE_AGAIN_AFTER
-                and abs(x - last) < self.REBASE_AGAIN_WITHIN and os.environ.get('VINTERP_REBASE2', '1') != '0')
+                and abs(x - last) < self.REBASE_AGAIN_WITHIN and _flag('REBASE2'))
 
     def _brent_rule(self):
         """h_rebase of vi_brent_warm_f64 / vi_brent_host_one_f64 (10 doubles): the re-basing schedule of the rotated systems and
         the early end on a jump of chi^2 (alpha_search.jump_rule: width in decades, |chi^2 - nu| threshold as a fraction of nu;
         zeros = brentq's own end)."""
-        sched = list(self._rebase_schedule()) if os.environ.get('VINTERP_REBASE', '1') != '0' else []
+        sched = list(self._rebase_schedule()) if _flag('REBASE') else []
         jr = alpha_search.jump_rule(1.)
         return np.array([len(sched)] + (sched + [0.] * 4)[:4] + [self.REBASE_AGAIN_AFTER, self.REBASE_AGAIN_WITHIN,
-                        1. if (sched and os.environ.get('VINTERP_REBASE2', '1') != '0') else 0.,
+                        1. if (sched and _flag('REBASE2')) else 0.,
                         jr[0] if jr else 0., jr[1] if jr else 0.], dtype=np.float64)
 
     def _rebase_schedule(self):
@@ -388,11 +394,15 @@ class FitEngine(object):
                                                 dD1.offset_ptr(slot0 * N * N), dD2.offset_ptr(slot0 * N * N),
                                                 dyt.offset_ptr(slot0 * N)), 'vi_warm_prepare_f64')
 
+    def _slots(self, tag, recs, slots=None):
+        """The slots of the rotated systems of `recs`, as a device array (buffer `tag`)."""
+        sl = np.array([(self._warm_slot if slots is None else slots)[int(r)] for r in recs], dtype=np.int32)
+        return self._buf(tag, (len(sl),), np.int32).upload(sl)
+
     def _warm_solve(self, tag, slots, recs, dalpha_ptr, n, dC_out, drank_out, dsweeps_out=None):
         N, h = self.N, self.ctx.handle
         dV, dD1, dD2, dyt = self._warm_buffers(tag)
-        sl = np.array([slots[int(r)] for r in recs], dtype=np.int32)
-        dslot = self._buf(tag + 'slot', (n,), np.int32).upload(sl)
+        dslot = self._slots(tag + 'slot', recs, slots)
         _lib.check(_lib.lib.vi_warm_solve_f64(h, n, N, dD1.ptr, dD2.ptr, dyt.ptr, dV.ptr, dslot.ptr, dalpha_ptr, EPS,
                                               dC_out, drank_out, dsweeps_out), 'vi_warm_solve_f64')
 
@@ -405,7 +415,7 @@ class FitEngine(object):
         log10a = np.asarray(log10a, dtype=np.float64)
         B = len(rec)
         is_int = log10a == np.floor(log10a)
-        if not is_int.any() or os.environ.get('VINTERP_DEDUPE', '1') == '0':
+        if not is_int.any() or not _flag('DEDUPE'):
             return self._chi2_batch_search_raw(rec, log10a, name, exact)
         ex = np.zeros(B, dtype=bool) if exact is None else np.asarray(exact, dtype=bool)
         eff = log10a.copy()
@@ -432,7 +442,7 @@ class FitEngine(object):
         _, first, inverse = np.unique(key, return_index=True, return_inverse=True)
         reps = miss[first]
         todo = np.sort(np.concatenate([np.nonzero(~is_int)[0], reps]))
-        self.stats['walk_same_system'] = self.stats.get('walk_same_system', 0) + B - len(todo)
+        self._count('walk_same_system', B - len(todo))
         if len(todo):
             out[todo] = self._chi2_batch_search_raw(rec[todo], eff[todo], name, ex[todo] if exact is not None else None)
         out[miss] = out[reps][inverse]
@@ -463,13 +473,13 @@ class FitEngine(object):
             forced = forced | np.asarray(exact, dtype=bool)      # reference-grade requests of the search: cold solves
         if (B == 1 and not is_int[0] and not forced[0] and self.warm_enabled() and int(rec[0]) in self._warm_slot
                 and not self._wants_rebase(int(rec[0]), float(log10a[0]))):
-            self._last_x[int(rec[0])] = float(log10a[0])
-            self._nreq[int(rec[0])] = self._nreq.get(int(rec[0]), 0) + 1
             # a single root-finder iterate of a record whose rotated system exists: one library call, no uploads
+            r = int(rec[0])
+            self._last_x[r] = float(log10a[0])
+            self._nreq[r] = self._nreq.get(r, 0) + 1
             dV, dD1, dD2, dyt = self._warm_buffers('w_')
             scratch = self._buf('w_one', (N + 8,))
             back = np.zeros(3)                  # chi^2, an internal word, the sweep count (low 32 bits)
-            r = int(rec[0])
             _lib.check(_lib.lib.vi_warm_chi2_one_f64(self.ctx.handle, N, self.P, dD1.ptr, dD2.ptr, dyt.ptr, dV.ptr,
                                                      self._warm_slot[r], self._exp10(log10a[0]), EPS,
                                                      self.At.ptr, r, self.dW.ptr, self.db.ptr, scratch.ptr,
@@ -479,15 +489,14 @@ class FitEngine(object):
             self.stats['warm_solves'] = self.stats.get('warm_solves', 0) + 1
             if int(back[2:3].view(np.int32)[0]) > self.max_sweeps():
                 # the sweep cap ended the solve: its value decides nothing - the same system from X(alpha) itself
-                self.stats['unconverged_resolved'] = self.stats.get('unconverged_resolved', 0) + 1
+                self._count('unconverged_resolved')
                 return self._cold_chi2(rec, np.power(10., log10a), name)
             if trace:
                 print('[search round] B=1 warm (single call)  %.2f ms  log10a[0]=%.12f' %
                       ((time.perf_counter() - t_tr) * 1e3, log10a[0]))
             return np.array([back[0]])
         if not self.warm_enabled():
-            al = {n: (np.power(10., log10a) if n == name else np.zeros(B)) for n in self.regularization_list}
-            return self.chi2_batch(rec, al)
+            return self._cold_chi2(rec, np.power(10., log10a), name)
         alpha = np.power(10., log10a)
         if not is_int.all():
             # the root finder's abscissae: 10^x by the routine the device-side iteration uses (csrc/vi_exp10.h), so that
@@ -497,14 +506,56 @@ class FitEngine(object):
             _lib.check(_lib.lib.vi_exp10_f64(ni.ctypes.data_as(_lib.VOIDP), out_.ctypes.data_as(_lib.VOIDP), len(ni)), 'vi_exp10_f64')
             alpha[~is_int] = out_
         if (self.T == 1 and B >= 8 and is_int.all() and not forced.any() and not self._warm_slot and not self._spec_slot
-                and os.environ.get('VINTERP_SPECULATE', '1') != '0'):
+                and _flag('SPECULATE')):
             return self._walk_with_speculative_bases(rec, log10a, alpha, name, trace)
+        cold, shared, warm, rebase, order, need = self._route(rec, log10a, forced)
+        if need:
+            self._ensure_rotated(name, need)
+        nc, nsh, nw, nrb = int(cold.sum()), int(shared.sum()), int(warm.sum()), int(rebase.sum())
+        dCall = self._buf('w_C', (B, N))
+        drank = self._buf('w_rank', (B,), np.int32)
+        dsw = self._buf('w_sweeps', (B,), np.int32)
+        rec_o, alpha_o = rec[order], alpha[order]
+        drec = self._buf('w_rec', (B,), np.int32).upload(rec_o)
+        dal = self._buf('w_alpha', (B,)).upload(alpha_o)
+
+        def at(o):          # the round's arrays from request o (in launch order) on
+            return drec.offset_ptr(o), dal.offset_ptr(o), dCall.offset_ptr(o * N), drank.offset_ptr(o), dsw.offset_ptr(o)
+        if nc:
+            self._launch_cold(name, nc, at)
+        if nsh:
+            self._launch_shared(name, np.rint(log10a[order[nc:nc + nsh]]).astype(np.int64), at(nc))
+        if nw or nrb:
+            self._launch_warm(name, rec_o[nc + nsh:], nw, nrb, at(nc + nsh))
+        dchi = self._buf('w_chi2', (B,))
+        _lib.check(_lib.lib.vi_chi2_f64(self.ctx.handle, B, self.P, N, self.At.ptr, dCall.ptr, drec.ptr, self.dW.ptr,
+                                        self.db.ptr, dchi.ptr), 'vi_chi2_f64')
+        tmp = dchi.download(B)
+        if B > nc:
+            self._resolve_unconverged(name, tmp, dsw, nc, rec_o, alpha_o)
+        out = np.empty(B)
+        out[order] = tmp
+        if trace:
+            print('[search round] B=%d cold=%d shared=%d warm=%d rebase=%d  %.2f ms  log10a[0]=%.12f' %
+                  (B, nc, nsh, nw, nrb, (time.perf_counter() - t_tr) * 1e3, log10a[0]))
+        self.stats['solves'] += B
+        self.stats['launches'] += 1
+        self._count('warm_solves', nw + nrb)
+        self._count('shared_solves', nsh)
+        return out
+
+    def _route(self, rec, log10a, forced):
+        """Which path serves each request of a round: masks cold / shared / warm / rebase, the order the launches take them in
+        (cold, shared by decade, warm, rebase) and need = {record: midpoint} for the records whose rotated system does not
+        exist yet, sorted by record.  Keeps the books of the re-basing rule (_last_x, _nreq, _rebased, _basis_x); no
+        library call."""
+        B = len(rec)
+        is_int = log10a == np.floor(log10a)
         shared = (is_int & ~forced if (self._ref_rec is not None and self.shared_walk_enabled())
                   else np.zeros(B, dtype=bool))
-        # root-finder requests (non-integer): a record without a rotated system yet gets it from ONE of its
-        # requests - the middle one when a multisection round asks for many, so the basis is nearest to all
-        warm = np.zeros(B, dtype=bool)
-        rebase = np.zeros(B, dtype=bool)
+        cold = (is_int & ~shared) | forced               # forced: records whose search is being redone cold
+        # root-finder requests (non-integer), record by record; a multisection round asks for many of one record
+        warm, rebase = np.zeros(B, dtype=bool), np.zeros(B, dtype=bool)
         by_rec = {}
         for j in np.nonzero(~is_int & ~forced)[0].tolist():
             by_rec.setdefault(int(rec[j]), []).append(j)
@@ -521,130 +572,123 @@ class FitEngine(object):
                 self._last_x[r] = x
                 self._nreq[r] = self._nreq.get(r, 0) + 1
             if r not in self._warm_slot:
-                # The rotated system of a record is set up at the MIDDLE of its unit bracket, 10^(floor(x) + 1/2),
-                # whatever the request that triggers it (Brent's first iterate, a multisection sample): the warm chi^2 is
-                # then one function of alpha per record, independent of the batch the record is fitted in and of the
-                # root finder's path - alone or among 999 others, a record sees the same values and Brent takes the
-                # same steps.  (It used to be set up at the first request; a record fitted alone, whose first request
-                # is a multisection sample, then got another basis, other rounding and sometimes another of the several
-                # roots of a default-order bracket than the same record inside a batch.)
                 need[r] = math.floor(float(log10a[js[0]])) + 0.5
-                self._basis_x[r] = need[r]
-                if (r, need[r]) in self._spec_slot:      # decomposed alongside the walk (_walk_with_speculative_bases)
-                    self._finish_speculative(r, self._spec_slot[(r, need[r])])
-                    del need[r]
-        if need:
-            recs_n = sorted(need)
-            scratchC = self._buf('wp_scratchC', (len(recs_n), N))
-            scratchR = self._buf('wp_scratchR', (len(recs_n),), np.int32)
-            self._warm_prepare('w_', self._warm_slot, recs_n, [float(np.power(10., need[r])) for r in recs_n], name,
-                               scratchC.ptr, scratchR.ptr)
-        cold = (is_int & ~shared) | forced               # forced: records whose search is being redone cold
         sh_idx = np.nonzero(shared)[0]
         sh_idx = sh_idx[np.argsort(log10a[sh_idx], kind='stable')]          # by decade: one basis after the other
         # warm solves cost more the further alpha is from where the record's rotated system sits: longest first, so
         # that a launch does not end on one straggler started last
         w_idx = np.nonzero(warm)[0]
-        if len(w_idx) > 256 and os.environ.get('VINTERP_LPT', '1') != '0':
-            dist = np.abs(log10a[w_idx] - np.array([self._basis_x.get(int(r), 0.) for r in rec[w_idx].tolist()]))
-            w_idx = w_idx[np.argsort(-dist, kind='stable')]
+        if len(w_idx) > 256 and _flag('LPT'):
+            at = [need[r] if r in need else self._basis_x.get(r, 0.) for r in rec[w_idx].tolist()]
+            w_idx = w_idx[np.argsort(-np.abs(log10a[w_idx] - np.array(at)), kind='stable')]
         order = np.concatenate([np.nonzero(cold)[0], sh_idx, w_idx, np.nonzero(rebase)[0]])
-        nc, nsh, nw, nrb = int(cold.sum()), len(sh_idx), int(warm.sum()), int(rebase.sum())
-        h = self.ctx.handle
-        dCall = self._buf('w_C', (B, N))
-        drank = self._buf('w_rank', (B,), np.int32)
-        dsw = self._buf('w_sweeps', (B,), np.int32)
-        rec_o, alpha_o = rec[order], alpha[order]
-        drec = self._buf('w_rec', (B,), np.int32).upload(rec_o)
-        dal = self._buf('w_alpha', (B,)).upload(alpha_o)
-        if nc:
-            mb = self._max_batch()
-            dX = self._buf('w_X', (min(nc, mb), N, N))
-            for s0 in range(0, nc, mb):
-                bc = min(mb, nc - s0)
-                _lib.check(_lib.lib.vi_form_system_f64(h, bc, N, self.dAWA.ptr, drec.offset_ptr(s0), dal.offset_ptr(s0),
-                                                       self.R[name].ptr, dX.ptr), 'vi_form_system_f64')
-                _lib.check(_lib.lib.vi_solve_trunc_f64(h, bc, N, dX.ptr, self.dy.ptr, drec.offset_ptr(s0), EPS,
-                                                       dCall.offset_ptr(s0 * N), drank.offset_ptr(s0), N * EPS, None),
-                           'vi_solve_trunc_f64')
-        o = nc
-        if nsh:
-            decades = np.rint(log10a[sh_idx]).astype(np.int64)
-            new_k = sorted(set(decades.tolist()) - set(self._basis_slot), reverse=True)
-            if new_k and not self._basis_slot:
-                # the reference bases of ALL the decades the walk can ask for, in one launch: decade by decade as the walk
-                # proceeds, every round waited for its own cold decompositions (3.5 ms + eigenvectors, seven times)
-                kfl = self._same_below.get(name)
-                lowest = int(max(-101, np.min(kfl))) if kfl is not None and len(kfl) else -101
-                new_k = sorted(set(new_k) | set(range(0, min(lowest, min(new_k)) - 1, -1)), reverse=True)
-            dV, dD1, dD2, dyt = (self._buf('sb_V', (102, N, N)), self._buf('sb_D1', (102, N, N)),
-                                 self._buf('sb_D2', (102, N, N)), self._buf('sb_yt', (102, N)))
-            if new_k:
-                if len(self._basis_slot) + len(new_k) > 102:
-                    raise RuntimeError('shared walk: more than 102 decades requested')
-                slot0 = len(self._basis_slot)
-                for i, k in enumerate(new_k):
-                    self._basis_slot[k] = slot0 + i
-                n = len(new_k)
-                dr = self._buf('sb_prec', (n,), np.int32).upload(np.full(n, self._ref_rec, dtype=np.int32))
-                da = self._buf('sb_palpha', (n,)).upload(np.power(10., np.asarray(new_k, dtype=np.float64)))
-                scratchC = self._buf('sb_scratchC', (n, N))
-                scratchR = self._buf('sb_scratchR', (n,), np.int32)
-                _lib.check(_lib.lib.vi_warm_prepare_f64(h, n, N, self.dAWA.ptr, dr.ptr, da.ptr, self.R[name].ptr,
-                                                        self.dy.ptr, EPS, scratchC.ptr, scratchR.ptr,
-                                                        dV.offset_ptr(slot0 * N * N), dD1.offset_ptr(slot0 * N * N),
-                                                        dD2.offset_ptr(slot0 * N * N), dyt.offset_ptr(slot0 * N)),
-                           'vi_warm_prepare_f64')
-                self.stats['solves'] += n
-                self.stats['reference_solves'] = self.stats.get('reference_solves', 0) + n
-            dbs = self._buf('sb_slot', (nsh,), np.int32).upload(
-                np.array([self._basis_slot[k] for k in decades.tolist()], dtype=np.int32))
-            _lib.check(_lib.lib.vi_basis_solve_f64(h, nsh, N, self.dAWA.ptr, self.dy.ptr, drec.offset_ptr(o),
-                                                   dbs.ptr, dal.offset_ptr(o), dV.ptr, dD2.ptr, EPS,
-                                                   dCall.offset_ptr(o * N), drank.offset_ptr(o), dsw.offset_ptr(o)),
-                       'vi_basis_solve_f64')
-            o += nsh
-        if nw and not nrb:
-            self._warm_solve('w_', self._warm_slot, rec_o[o:o + nw], dal.offset_ptr(o), nw, dCall.offset_ptr(o * N),
-                             drank.offset_ptr(o), dsw.offset_ptr(o))
-        elif nrb:
-            # the plain warm solves of the round ride in the launch of the re-basing ones (a launch lasts as long as its
-            # slowest system, however few it holds)
-            n = nw + nrb
-            dV, dD1, dD2, dyt = self._warm_buffers('w_')
-            sl = np.array([self._warm_slot[int(r)] for r in rec_o[o:o + n]], dtype=np.int32)
-            dslot = self._buf('w_rbslot', (n,), np.int32).upload(sl)
-            _lib.check(_lib.lib.vi_warm_rebase_f64(h, n, nw, N, self.dAWA.ptr, self.R[name].ptr, self.dy.ptr, drec.offset_ptr(o),
-                                                   dslot.ptr, dal.offset_ptr(o), EPS, dV.ptr, dD1.ptr, dD2.ptr, dyt.ptr,
-                                                   dCall.offset_ptr(o * N), drank.offset_ptr(o), dsw.offset_ptr(o)),
-                       'vi_warm_rebase_f64')
-            self.stats['rebased'] = self.stats.get('rebased', 0) + nrb
-        dchi = self._buf('w_chi2', (B,))
-        _lib.check(_lib.lib.vi_chi2_f64(h, B, self.P, N, self.At.ptr, dCall.ptr, drec.ptr, self.dW.ptr, self.db.ptr,
-                                        dchi.ptr), 'vi_chi2_f64')
-        tmp = np.empty(B)
-        _lib.check(_lib.lib.vi_d2h(h, tmp.ctypes.data_as(_lib.VOIDP), dchi.ptr, tmp.nbytes), 'd2h')
-        if B > nc:
-            # solves in a rotated system (shared walk bases, warm iterates) that the sweep cap ended before they converged:
-            # their chi^2 must not decide a sign or steer Brent - the same systems again from X(alpha) itself.  How many
-            # sweeps a rotated system takes depends on how far the record lies from the basis it is solved in (a record
-            # with most of its points dropped sits far from the batch's mean system).
-            sw = np.empty(B - nc, dtype=np.int32)
-            _lib.check(_lib.lib.vi_d2h(h, sw.ctypes.data_as(_lib.VOIDP), dsw.offset_ptr(nc), sw.nbytes), 'd2h')
-            bad = nc + np.nonzero(sw > self.max_sweeps())[0]
-            if len(bad):
-                tmp[bad] = self._cold_chi2(rec_o[bad], alpha_o[bad], name)
-                self.stats['unconverged_resolved'] = self.stats.get('unconverged_resolved', 0) + len(bad)
-        out = np.empty(B)
-        out[order] = tmp
-        if trace:
-            print('[search round] B=%d cold=%d shared=%d warm=%d rebase=%d  %.2f ms  log10a[0]=%.12f' %
-                  (B, nc, nsh, nw, nrb, (time.perf_counter() - t_tr) * 1e3, log10a[0]))
-        self.stats['solves'] += B
-        self.stats['launches'] += 1
-        self.stats['warm_solves'] = self.stats.get('warm_solves', 0) + nw + nrb
-        self.stats['shared_solves'] = self.stats.get('shared_solves', 0) + nsh
-        return out
+        return cold, shared, warm, rebase, order, dict(sorted(need.items()))
+
+    def _ensure_rotated(self, name, mids):
+        """Set up the rotated systems of records that have none: mids = {record: log10 alpha of the middle of its unit
+        bracket}.  A basis decomposed alongside the walk (_walk_with_speculative_bases) is finished, the others are decomposed
+        in one launch, in the order given.  Returns how many were decomposed here (the callers' stats differ).
+
+        The MIDDLE of the unit bracket, 10^(floor(x) + 1/2), whatever triggers the set-up (Brent's first iterate, a
+        multisection sample, the device or the host-loop iteration): the warm chi^2 is then one function of alpha per record,
+        independent of the batch the record is fitted in and of the path that serves it - alone or among 999 others, a record
+        sees the same values and Brent takes the same steps.  (It used to be set up at the first request; a record fitted
+        alone, whose first request is a multisection sample, then got another basis, other rounding and sometimes another
+        of the several roots of a default-order bracket than the same record inside a batch.)"""
+        todo = []
+        for r, x in mids.items():
+            self._basis_x[r] = x
+            if (r, x) in self._spec_slot:
+                self._finish_speculative(r, self._spec_slot[(r, x)])
+            else:
+                todo.append(r)
+        if todo:
+            scratchC = self._buf('wp_scratchC', (len(todo), self.N))
+            scratchR = self._buf('wp_scratchR', (len(todo),), np.int32)
+            self._warm_prepare('w_', self._warm_slot, todo, [float(np.power(10., mids[r])) for r in todo], name,
+                               scratchC.ptr, scratchR.ptr)
+        return len(todo)
+
+    def _launch_cold(self, name, nc, at):
+        """The first nc requests of the round from X(alpha) itself."""
+        N, h = self.N, self.ctx.handle
+        mb = self._max_batch()
+        dX = self._buf('w_X', (min(nc, mb), N, N))
+        for s0 in range(0, nc, mb):
+            bc = min(mb, nc - s0)
+            prec, pal, pC, prank, _ = at(s0)
+            _lib.check(_lib.lib.vi_form_system_f64(h, bc, N, self.dAWA.ptr, prec, pal, self.R[name].ptr, dX.ptr),
+                       'vi_form_system_f64')
+            _lib.check(_lib.lib.vi_solve_trunc_f64(h, bc, N, dX.ptr, self.dy.ptr, prec, EPS, pC, prank, N * EPS, None),
+                       'vi_solve_trunc_f64')
+
+    def _reference_bases(self, name, decades):
+        """The eigenbases of the reference system at the given decades (shared walk): slots in _basis_slot, the missing ones
+        decomposed in one launch.  Returns the device arrays vi_basis_solve_f64 reads (V, D2)."""
+        N = self.N
+        new_k = sorted(set(decades.tolist()) - set(self._basis_slot), reverse=True)
+        if new_k and not self._basis_slot:
+            # the reference bases of ALL the decades the walk can ask for, in one launch: decade by decade as the walk
+            # proceeds, every round waited for its own cold decompositions (3.5 ms + eigenvectors, seven times)
+            kfl = self._same_below.get(name)
+            lowest = int(max(-101, np.min(kfl))) if kfl is not None and len(kfl) else -101
+            new_k = sorted(set(new_k) | set(range(0, min(lowest, min(new_k)) - 1, -1)), reverse=True)
+        dV, dD1, dD2, dyt = (self._buf('sb_V', (102, N, N)), self._buf('sb_D1', (102, N, N)),
+                             self._buf('sb_D2', (102, N, N)), self._buf('sb_yt', (102, N)))
+        if new_k:
+            if len(self._basis_slot) + len(new_k) > 102:
+                raise RuntimeError('shared walk: more than 102 decades requested')
+            slot0 = len(self._basis_slot)
+            for i, k in enumerate(new_k):
+                self._basis_slot[k] = slot0 + i
+            n = len(new_k)
+            dr = self._buf('sb_prec', (n,), np.int32).upload(np.full(n, self._ref_rec, dtype=np.int32))
+            da = self._buf('sb_palpha', (n,)).upload(np.power(10., np.asarray(new_k, dtype=np.float64)))
+            scratchC = self._buf('sb_scratchC', (n, N))
+            scratchR = self._buf('sb_scratchR', (n,), np.int32)
+            _lib.check(_lib.lib.vi_warm_prepare_f64(self.ctx.handle, n, N, self.dAWA.ptr, dr.ptr, da.ptr, self.R[name].ptr,
+                                                    self.dy.ptr, EPS, scratchC.ptr, scratchR.ptr,
+                                                    dV.offset_ptr(slot0 * N * N), dD1.offset_ptr(slot0 * N * N),
+                                                    dD2.offset_ptr(slot0 * N * N), dyt.offset_ptr(slot0 * N)),
+                       'vi_warm_prepare_f64')
+            self.stats['solves'] += n
+            self._count('reference_solves', n)
+        return dV, dD2
+
+    def _launch_shared(self, name, decades, ptrs):
+        """Walk requests (one decade each, sorted) in the eigenbases of the reference system."""
+        dV, dD2 = self._reference_bases(name, decades)
+        prec, pal, pC, prank, psw = ptrs
+        dbs = self._buf('sb_slot', (len(decades),), np.int32).upload(
+            np.array([self._basis_slot[k] for k in decades.tolist()], dtype=np.int32))
+        _lib.check(_lib.lib.vi_basis_solve_f64(self.ctx.handle, len(decades), self.N, self.dAWA.ptr, self.dy.ptr, prec,
+                                               dbs.ptr, pal, dV.ptr, dD2.ptr, EPS, pC, prank, psw), 'vi_basis_solve_f64')
+
+    def _launch_warm(self, name, recs, nw, nrb, ptrs):
+        """Root-finder requests in the records' rotated systems: nw plain ones, then nrb that move the system to the request."""
+        prec, pal, pC, prank, psw = ptrs
+        if not nrb:
+            self._warm_solve('w_', self._warm_slot, recs, pal, nw, pC, prank, psw)
+            return
+        # the plain warm solves of the round ride in the launch of the re-basing ones (a launch lasts as long as its
+        # slowest system, however few it holds)
+        dV, dD1, dD2, dyt = self._warm_buffers('w_')
+        dslot = self._slots('w_rbslot', recs)
+        _lib.check(_lib.lib.vi_warm_rebase_f64(self.ctx.handle, nw + nrb, nw, self.N, self.dAWA.ptr, self.R[name].ptr,
+                                               self.dy.ptr, prec, dslot.ptr, pal, EPS, dV.ptr, dD1.ptr, dD2.ptr, dyt.ptr,
+                                               pC, prank, psw), 'vi_warm_rebase_f64')
+        self._count('rebased', nrb)
+
+    def _resolve_unconverged(self, name, chi2, dsw, nc, rec_o, alpha_o):
+        """Solves in a rotated system (shared walk bases, warm iterates: the requests from nc on) that the sweep cap ended
+        before they converged: their chi^2 must not decide a sign or steer Brent - the same systems again from X(alpha)
+        itself, written into chi2.  How many sweeps a rotated system takes depends on how far the record lies from the basis
+        it is solved in (a record with most of its points dropped sits far from the batch's mean system)."""
+        sw = dsw.download(len(chi2) - nc, offset=nc)
+        bad = nc + np.nonzero(sw > self.max_sweeps())[0]
+        if len(bad):
+            chi2[bad] = self._cold_chi2(rec_o[bad], alpha_o[bad], name)
+            self._count('unconverged_resolved', len(bad))
 
     DEVICE_BRENT_MIN_RECORDS = 8
 
@@ -666,28 +710,24 @@ class FitEngine(object):
             return False
         return e == '1' or self.T >= self.DEVICE_BRENT_MIN_RECORDS
 
+    @staticmethod
+    def _bracket_middle(b):
+        return math.floor(min(b['alpha'], b['alpha0'])) + 0.5
+
     def _device_brent(self, recs, brackets, name):
         """Brent's iteration for the records `recs` (brackets: dicts with alpha, alpha0, val, val0, nu) on the device.
         Rotated systems are set up at the middle of each record's unit bracket, as the host path does; returns one
         (root, iterations, funcalls, other_end) per record, None where the kernel gave up (a solve ended by the sweep cap)."""
         N, h, n = self.N, self.ctx.handle, len(recs)
         recs = [int(r) for r in recs]
-        need = [r for r in recs if r not in self._warm_slot]
-        if need:
-            mids = {r: math.floor(min(b['alpha'], b['alpha0'])) + 0.5 for r, b in zip(recs, brackets)}
-            scratchC = self._buf('wp_scratchC', (len(need), N))
-            scratchR = self._buf('wp_scratchR', (len(need),), np.int32)
-            for r in need:
-                self._basis_x[r] = mids[r]
-            self._warm_prepare('w_', self._warm_slot, need, [float(np.power(10., mids[r])) for r in need], name,
-                               scratchC.ptr, scratchR.ptr)
-            self.stats['solves'] += len(need)
+        mids = {r: self._bracket_middle(b) for r, b in zip(recs, brackets) if r not in self._warm_slot}
+        if mids:
+            self.stats['solves'] += self._ensure_rotated(name, mids)
         dV, dD1, dD2, dyt = self._warm_buffers('w_')
         up = lambda key, a, dt: self._buf('db_' + key, (n,), dt).upload(np.asarray(a, dtype=dt))      # noqa: E731
-        drec, dslot = up('rec', recs, np.int32), up('slot', [self._warm_slot[r] for r in recs], np.int32)
-        dxa, dxb = up('xa', [b['alpha'] for b in brackets], np.float64), up('xb', [b['alpha0'] for b in brackets], np.float64)
-        dfa, dfb = up('fa', [b['val'] for b in brackets], np.float64), up('fb', [b['val0'] for b in brackets], np.float64)
-        dnu = up('nu', [b['nu'] for b in brackets], np.float64)
+        drec, dslot = up('rec', recs, np.int32), self._slots('db_slot', recs)
+        dxa, dxb, dfa, dfb, dnu = (up(k, [b[f] for b in brackets], np.float64) for k, f in
+                                   (('xa', 'alpha'), ('xb', 'alpha0'), ('fa', 'val'), ('fb', 'val0'), ('nu', 'nu')))
         droot, dother = self._buf('db_root', (n,)), self._buf('db_other', (n,))
         dit, dfc, dst = (self._buf('db_' + k, (n,), np.int32) for k in ('it', 'fc', 'st'))
         rule = self._brent_rule()
@@ -695,30 +735,24 @@ class FitEngine(object):
                                               self.R[name].ptr, self.dy.ptr, rule.ctypes.data_as(_lib.VOIDP), self.At.ptr,
                                               self.dW.ptr, self.db.ptr, drec.ptr, dslot.ptr, dxa.ptr, dxb.ptr, dfa.ptr, dfb.ptr, dnu.ptr,
                                               EPS, droot.ptr, dother.ptr, dit.ptr, dfc.ptr, dst.ptr), 'vi_brent_warm_f64')
-
-        def down(d, dt):
-            a = np.empty(n, dtype=dt)
-            _lib.check(_lib.lib.vi_d2h(h, a.ctypes.data_as(_lib.VOIDP), d.ptr, a.nbytes), 'd2h')
-            return a
-        root, other, its, fcs, sts = down(droot, np.float64), down(dother, np.float64), down(dit, np.int32), \
-            down(dfc, np.int32), down(dst, np.int32)
-        self.stats['rebased'] = self.stats.get('rebased', 0) + int((sts >> 8).sum())
+        root, other, its, fcs, sts = (d.download(n) for d in (droot, dother, dit, dfc, dst))
+        self._count('rebased', int((sts >> 8).sum()))
         sts = sts & 0xff
         if np.any(sts == 3):
             raise RuntimeError('Failed to converge after %d iterations.' % alpha_search.MAXITER)
         self.stats['solves'] += int(fcs.sum())
         self.stats['launches'] += 1
-        self.stats['warm_solves'] = self.stats.get('warm_solves', 0) + int(fcs.sum())
-        self.stats['device_brent_records'] = self.stats.get('device_brent_records', 0) + int((sts == 0).sum())
+        self._count('warm_solves', int(fcs.sum()))
+        self._count('device_brent_records', int((sts == 0).sum()))
         if np.any(sts == 2):
-            self.stats['unconverged_resolved'] = self.stats.get('unconverged_resolved', 0) + int((sts == 2).sum())
+            self._count('unconverged_resolved', int((sts == 2).sum()))
         return [(float(root[j]), int(its[j]), int(fcs[j]), float(other[j])) if sts[j] == 0 else None for j in range(n)]
 
     def host_loop_brent_enabled(self):
         """Brent's iteration of a record fitted ALONE as one library call (vi_brent_host_one_f64: the host-driven loop in C,
         the state machine of the device kernel compiled for the host) instead of one call per function value with the search
         coroutine in between: same requests, same values, same bits.  VINTERP_HOST_LOOP_BRENT=0 keeps the loop in Python."""
-        if os.environ.get('VINTERP_HOST_LOOP_BRENT', '1') == '0' or not self.warm_enabled() or len(self.regularization_list) != 1:
+        if not _flag('HOST_LOOP_BRENT') or not self.warm_enabled() or len(self.regularization_list) != 1:
             return False
         return self.T == 1 and len(self._rebase_schedule()) <= 4
 
@@ -729,16 +763,7 @@ class FitEngine(object):
         rule = self._brent_rule()
         for r, b in zip([int(r) for r in recs], brackets):
             if r not in self._warm_slot:
-                # the rotated system at the middle of the record's unit bracket: decomposed alongside the walk, or now
-                mid = math.floor(min(b['alpha'], b['alpha0'])) + 0.5
-                self._basis_x[r] = mid
-                if (r, mid) in self._spec_slot:
-                    self._finish_speculative(r, self._spec_slot[(r, mid)])
-                else:
-                    scratchC = self._buf('wp_scratchC', (1, N))
-                    scratchR = self._buf('wp_scratchR', (1,), np.int32)
-                    self._warm_prepare('w_', self._warm_slot, [r], [float(np.power(10., mid))], name, scratchC.ptr, scratchR.ptr)
-                    self.stats['solves'] += 1
+                self.stats['solves'] += self._ensure_rotated(name, {r: self._bracket_middle(b)})
             dV, dD1, dD2, dyt = self._warm_buffers('w_')
             scratch = self._buf('w_one', (N + 8,))
             res = np.zeros(6)
@@ -752,10 +777,10 @@ class FitEngine(object):
                 raise RuntimeError('Failed to converge after %d iterations.' % alpha_search.MAXITER)
             self.stats['solves'] += fc
             self.stats['launches'] += fc
-            self.stats['warm_solves'] = self.stats.get('warm_solves', 0) + fc
-            self.stats['rebased'] = self.stats.get('rebased', 0) + int(res[5])
+            self._count('warm_solves', fc)
+            self._count('rebased', int(res[5]))
             if st == 2:
-                self.stats['unconverged_resolved'] = self.stats.get('unconverged_resolved', 0) + 1
+                self._count('unconverged_resolved')
                 out.append(None)
             else:
                 out.append((float(res[0]), int(res[2]), fc, float(res[1])))
@@ -815,11 +840,10 @@ class FitEngine(object):
         dchi = self._buf('sp_chi2', (B,))
         _lib.check(_lib.lib.vi_chi2_f64(h, B, self.P, N, self.At.ptr, dC.ptr, dr.ptr, self.dW.ptr, self.db.ptr, dchi.ptr),
                    'vi_chi2_f64')
-        out = np.empty(B)
-        _lib.check(_lib.lib.vi_d2h(h, out.ctypes.data_as(_lib.VOIDP), dchi.ptr, out.nbytes), 'd2h')
+        out = dchi.download(B)
         self.stats['solves'] += n
         self.stats['launches'] += 1
-        self.stats['speculative_bases'] = self.stats.get('speculative_bases', 0) + len(mids)
+        self._count('speculative_bases', len(mids))
         if trace:
             print('[search round] B=%d walk + %d speculative bracket bases in one launch' % (B, len(mids)))
         return out
@@ -915,12 +939,10 @@ class FitEngine(object):
             # elements is several times the coroutine's step)
             solver = None
             if self.device_brent_enabled() and not cold and not multisection:
-                def solver(recs, brs, _name=name):
-                    return self._device_brent(recs, brs, _name)
+                solver = functools.partial(self._device_brent, name=name)
             elif self.host_loop_brent_enabled() and not cold and not multisection:
-                def solver(recs, brs, _name=name):
-                    return self._host_loop_brent(recs, brs, _name)
-            if not multisection and T >= 16 and os.environ.get('VINTERP_TABLE_WALK', '1') != '0':
+                solver = functools.partial(self._host_loop_brent, name=name)
+            if not multisection and T >= 16 and _flag('TABLE_WALK'):
                 # the walks of the whole batch on one (records x decades) table: the coroutines' requests and decisions
                 # without the coroutines (110 ms of interpreter per 1000 records, which concurrent pipelines cannot share)
                 alphas, outcomes, info, nev = alpha_search.run_table_batched(npts, evaluate, prefetch=prefetch, refine=refine,
@@ -947,8 +969,7 @@ class FitEngine(object):
                                              self.dAWA.offset_ptr(t * N * N), self.dy.offset_ptr(t * N),
                                              self.dW.offset_ptr(t * P), self.db.offset_ptr(t * P), alpha,
                                              self.R[name].ptr, EPS, dres.ptr), 'vi_gcv_terms_f64')
-        res = np.empty(npnt)
-        _lib.check(_lib.lib.vi_d2h(self.ctx.handle, res.ctypes.data_as(_lib.VOIDP), dres.ptr, res.nbytes), 'd2h')
+        res = dres.download(npnt)
         self.stats['solves'] += npnt
         self.stats['launches'] += 1
         return sum(res.tolist())                    # the reference's left-to-right Python sum
@@ -994,18 +1015,11 @@ class FitEngine(object):
         good = [t for t in range(T) if (only is None or t in only)
                 and not np.any(np.isnan([params[t][n] for n in self.regularization_list]))]
         if compact:
-            R = len(good)
-            Coeffs, Cov = np.empty((R, N)), (np.empty((R, N, N)) if calccov else None)
-            chi, ranks = np.empty(R), np.empty(R, dtype=np.int32)
-            rows = np.arange(R, dtype=np.int64)
+            Coeffs, Cov, chi, ranks = self._result_arrays(len(good), calccov)
+            rows = np.arange(len(good), dtype=np.int64)
         else:
-            if out is not None:                     # caller's arrays (a pipeline's share of the batch's result)
-                Coeffs, Cov, chi, ranks = out
-            else:
-                Coeffs = np.empty((T, N))
-                Cov = np.empty((T, N, N)) if calccov else None
-                chi = np.empty(T)
-                ranks = np.empty(T, dtype=np.int32)
+            # out: the caller's arrays (a pipeline's share of the batch's result)
+            Coeffs, Cov, chi, ranks = out if out is not None else self._result_arrays(T, calccov)
             rows = np.asarray(good, dtype=np.int64)
             miss = np.ones(T, dtype=bool)
             miss[rows] = False
@@ -1017,16 +1031,13 @@ class FitEngine(object):
                     Cov[miss] = np.nan
         h = self.ctx.handle
 
-        def down(dst, dev, r0, B, shape, dtype):
+        def down(dst, dev, r0, B):
             """B rows of `dev` into dst[rows[r0 : r0 + B]]"""
             rr = rows[r0:r0 + B]
             if B and int(rr[-1] - rr[0]) == B - 1 and dst.flags['C_CONTIGUOUS']:
-                view = dst[int(rr[0]):int(rr[0]) + B]                  # consecutive rows: the download lands in place
-                _lib.check(_lib.lib.vi_d2h(h, view.ctypes.data_as(_lib.VOIDP), dev.ptr, view.nbytes), 'd2h')
+                dev.download(out=dst[int(rr[0]):int(rr[0]) + B])       # consecutive rows: the download lands in place
             else:
-                tmp = np.empty((B,) + shape, dtype=dtype)
-                _lib.check(_lib.lib.vi_d2h(h, tmp.ctypes.data_as(_lib.VOIDP), dev.ptr, tmp.nbytes), 'd2h')
-                dst[rr] = tmp
+                dst[rr] = dev.download((B,) + dst.shape[1:])
         step = max(1, min(len(good), 2048))
         for s in range(0, len(good), step):
             idx = np.asarray(good[s:s + step], dtype=np.int32)
@@ -1036,9 +1047,9 @@ class FitEngine(object):
             dchi = self._buf('f_chi2', (B,))
             _lib.check(_lib.lib.vi_chi2_f64(h, B, self.P, N, self.At.ptr, dC.ptr, drec.ptr, self.dW.ptr,
                                             self.db.ptr, dchi.ptr), 'vi_chi2_f64')
-            down(Coeffs, dC, s, B, (N,), np.float64)
-            down(chi, dchi, s, B, (), np.float64)
-            down(ranks, drank, s, B, (), np.int32)
+            down(Coeffs, dC, s, B)
+            down(chi, dchi, s, B)
+            down(ranks, drank, s, B)
             if calccov:
                 # dC = H AWA H needs AWA of the selected records, contiguous
                 dsel = self._buf('f_AWAsel', (B, N, N))
@@ -1050,7 +1061,7 @@ class FitEngine(object):
                 else:
                     ddC = self._buf('f_dC', (B, N, N))
                     _lib.check(_lib.lib.vi_cov_f64(h, B, N, dH.ptr, dsel.ptr, ddC.ptr), 'vi_cov_f64')
-                    down(Cov, ddC, s, B, (N, N), np.float64)
+                    down(Cov, ddC, s, B)
         if compact:
             return Coeffs, Cov, chi, ranks, good
         if defer_cov and calccov and len(good):
@@ -1079,7 +1090,7 @@ class FitEngine(object):
             th = threading.Thread(target=bring)
             th.start()
             self._cov_pending = (th, err)
-            self.stats['cov_side_downloads'] = self.stats.get('cov_side_downloads', 0) + 1
+            self._count('cov_side_downloads')
         return Coeffs, Cov, chi, ranks
 
     def join_cov(self):
@@ -1087,7 +1098,7 @@ class FitEngine(object):
         pend, self._cov_pending = getattr(self, '_cov_pending', None), None
         if pend is not None:
             pend[0].join()
-            self.stats['cov_side_joined'] = self.stats.get('cov_side_joined', 0) + 1
+            self._count('cov_side_joined')
             if pend[1]:
                 raise pend[1][0]
 
@@ -1142,7 +1153,7 @@ class FitEngine(object):
     def _guard(self, npts, calccov, prefetch, params, infos, Coeffs, Cov, chi, ranks, cov_rows, stamp):
         """The consistency guard of _search_and_finalize; Cov is not touched here (its download may still be running): rows
         to replace go to cov_rows."""
-        if len(self.regularization_list) != 1 or os.environ.get('VINTERP_GUARD', '1') == '0':
+        if len(self.regularization_list) != 1 or not _flag('GUARD'):
             return params, infos, Coeffs, Cov, chi, ranks
         name = self.regularization_list[0]
         inf = infos[name]
@@ -1230,13 +1241,7 @@ class FitEngine(object):
                     params[t][name] = float(np.power(10., root))
                     inf['info'][t].update(log10_alpha=root, other_end=oe, polished_cold=True, polish_iterations=iters,
                                           polish_end=how, warm_log10_alpha=root_of[t])
-                C2, V2, c2, r2, g2 = self.finalize(params, calccov=calccov, only=set(done), compact=True)
-                at = {t: i for i, t in enumerate(g2)}
-                for t in done:
-                    i = at.get(t)
-                    Coeffs[t], chi[t], ranks[t] = (C2[i], c2[i], r2[i]) if i is not None else (np.nan, np.nan, -1)
-                    if calccov:
-                        cov_rows.append((t, V2[i] if i is not None else np.nan))
+                self._replace_rows(params, done, calccov, Coeffs, chi, ranks, cov_rows)
                 inf['polished_cold'] = done
                 for t in violators():
                     if t in sol:
@@ -1247,20 +1252,26 @@ class FitEngine(object):
         stamp('guard')
         if bad and self.warm_enabled():
             p2, i2 = self.search(npts, prefetch=prefetch, only=bad, cold=True)
-            C2, V2, c2, r2, g2 = self.finalize(p2, calccov=calccov, only=set(bad), compact=True)
-            at = {t: i for i, t in enumerate(g2)}
+            self._replace_rows(p2, bad, calccov, Coeffs, chi, ranks, cov_rows)
             for t in bad:
                 params[t] = p2[t]
                 inf['outcomes'][t] = i2[name]['outcomes'][t]
                 inf['info'][t] = i2[name]['info'][t]
                 inf['info'][t]['redone_cold'] = True
-                i = at.get(t)
-                Coeffs[t], chi[t], ranks[t] = (C2[i], c2[i], r2[i]) if i is not None else (np.nan, np.nan, -1)
-                if calccov:
-                    cov_rows.append((t, V2[i] if i is not None else np.nan))
             inf['evaluations'] += i2[name]['evaluations']
             violators()
         return params, infos, Coeffs, Cov, chi, ranks
+
+    def _replace_rows(self, params, recs, calccov, Coeffs, chi, ranks, cov_rows):
+        """The guard's re-finalise: the final solve of the records `recs` again, with `params`, and its rows put in place
+        of theirs (NaN rows where the parameters are NaN); the covariance rows go to cov_rows."""
+        C2, V2, c2, r2, g2 = self.finalize(params, calccov=calccov, only=set(recs), compact=True)
+        at = {t: i for i, t in enumerate(g2)}
+        for t in recs:
+            i = at.get(t)
+            Coeffs[t], chi[t], ranks[t] = (C2[i], c2[i], r2[i]) if i is not None else (np.nan, np.nan, -1)
+            if calccov:
+                cov_rows.append((t, V2[i] if i is not None else np.nan))
 
     def _stage_stamp(self, name):
         """VINTERP_STAGE_TIMES=1: wall time per stage of a fit (device drained at the boundaries) into stats['ms_<stage>']."""
@@ -1270,7 +1281,7 @@ class FitEngine(object):
         self.ctx.sync()
         now = time.perf_counter()
         if name is not None:
-            self.stats['ms_' + name] = self.stats.get('ms_' + name, 0.) + (now - self._stage_t0) * 1e3
+            self._count('ms_' + name, (now - self._stage_t0) * 1e3)
         self._stage_t0 = now
 
     def result_buffers(self, calccov=True, pinned=True):
@@ -1279,9 +1290,12 @@ class FitEngine(object):
         (one shard of timesteps after the other, results written out in between) hands the same arrays to every fit instead of
         receiving 8 T N^2 bytes of fresh pages each time - 1.66 GB per 10 000 records at N = 144, whose first touch and release
         cost a fit of 2.1 s about 0.1 s - and the covariances come down at the rate of the link."""
-        T, N = self.T, self.N
-        mk = _lib.pinned_empty if pinned else np.empty
-        return (mk((T, N)), mk((T, N, N)) if calccov else None, mk((T,)), mk((T,), np.int32))
+        return self._result_arrays(self.T, calccov, _lib.pinned_empty if pinned else np.empty)
+
+    def _result_arrays(self, T, calccov, mk=np.empty):
+        """(Coeffs (T, N), Covariance (T, N, N) or None, chi_sq (T,), ranks (T,) int32), not initialised."""
+        N = self.N
+        return mk((T, N)), (mk((T, N, N)) if calccov else None), mk((T,)), mk((T,), np.int32)
 
     def _check_out(self, out, calccov):
         T, N = self.T, self.N
@@ -1317,7 +1331,6 @@ class FitEngine(object):
         1430 records/s with three pipelines, 4000 records 1330 -> 1670 with four).  Records are independent and a record's
         numbers do not depend on the batch it is in (test_c1_fit_is_independent_of_the_batch_and_consistent), so the
         split changes nothing but the time."""
-        import threading
         T, N, K = self.T, self.N, len(self._bounds) - 1
         if self._subs is None or len(self._subs) != K:
             self._close_subs()
@@ -1328,13 +1341,7 @@ class FitEngine(object):
                                 self.regularization_list)
                 sub._no_pipeline = True
                 self._subs.append(sub)
-        if out is not None:
-            Coeffs, Cov, chi, ranks = out
-        else:
-            Coeffs = np.empty((T, N))
-            Cov = np.empty((T, N, N)) if calccov else None
-            chi = np.empty(T)
-            ranks = np.empty(T, dtype=np.int32)
+        Coeffs, Cov, chi, ranks = out if out is not None else self._result_arrays(T, calccov)
         results, errors = [None] * K, [None] * K
 
         def run(k):
@@ -1369,7 +1376,7 @@ class FitEngine(object):
                 m['polished_cold'] += [lo + t for t in inf.get('polished_cold', [])]
                 m['redone_cold'] += [lo + t for t in inf.get('redone_cold', [])]
             for key, v in self._subs[k].stats.items():
-                self.stats[key] = self.stats.get(key, 0) + v
+                self._count(key, v)
         self.stats['pipelines'] = K
         return dict(Coeffs=Coeffs, Covariance=Cov, chi_sq=chi, reg_params=params, ranks=ranks, search=infos)
 
