@@ -50,6 +50,18 @@ __device__ unsigned long long g_jacobi_stamps[16];
             g_jacobi_stamps[(threadIdx.x == 0 ? 0 : 8) + (k)] += t_ - stamp_t;               \
         stamp_t = __builtin_readcyclecounter();                                              \
     } while (0)
+// the same build: cycle sums of thread 0 of EVERY workgroup per phase of a solve in the role-separated kernel - 0 set-up, 1 load,
+// 2 rounds, 3 truncation and outputs, 4 replay, 5 copy-out of C, 7 the number of solves - for the solves of the bracket walk
+// (conv_tol > 0: slots 0-7) and all others (slots 8-15); read and reset by vi_debug_jacobi_phases (tools/perf_k3_walk.py)
+__device__ unsigned long long g_jacobi_phases[16];
+#define VI_PHASE(k)                                                                                          \
+    do {                                                                                                     \
+        const unsigned long long t_ = __builtin_readcyclecounter();                                          \
+        if (threadIdx.x == 0) atomicAdd(&g_jacobi_phases[(conv_tol > 0.0 ? 0 : 8) + (k)], t_ - phase_t);     \
+        phase_t = __builtin_readcyclecounter();                                                              \
+    } while (0)
+#define VI_PHASE_COUNT()                                                                                     \
+    do { if (threadIdx.x == 0) atomicAdd(&g_jacobi_phases[(conv_tol > 0.0 ? 0 : 8) + 7], 1ull); } while (0)
 #else
 #define VI_STAMP(k)
 #endif
@@ -97,10 +109,11 @@ __global__ __launch_bounds__(768) void k_jacobi_solve_v2(
 {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     const int64_t sys = blockIdx.x;
-    jacobi_system_v2(lds_raw, N, X + sys * (int64_t)N * N, scl ? scl[sys] : 1.0, y + (int64_t)(rec ? rec[sys] : sys) * N, rcond,
-                     abs_floor, C + sys * N, rank ? rank + sys : nullptr, rotlog + sys * log_stride, max_sweeps,
-                     sweeps_out ? sweeps_out + sys : nullptr, lam_out ? lam_out + sys * N : nullptr, lam_raw,
-                     nround_out ? nround_out + sys : nullptr, round_acc, conv_tol);
+    jacobi_system_v2<V2_REPLAY_AHEAD>(lds_raw, N, X + sys * (int64_t)N * N, scl ? scl[sys] : 1.0,
+                                      y + (int64_t)(rec ? rec[sys] : sys) * N, rcond, abs_floor, C + sys * N,
+                                      rank ? rank + sys : nullptr, rotlog + sys * log_stride, max_sweeps,
+                                      sweeps_out ? sweeps_out + sys : nullptr, lam_out ? lam_out + sys * N : nullptr, lam_raw,
+                                      nround_out ? nround_out + sys : nullptr, round_acc, conv_tol);
 }
 
 // Eigenvectors from the rotation log: V = J_1 J_2 ... J_K, so column k of V is the reverse replay applied to the unit
@@ -128,6 +141,20 @@ extern "C" int vi_debug_jacobi_stamps(double* out, int reset)
     if (reset) {
         memset(h, 0, sizeof(h));
         if (hipMemcpyToSymbol(HIP_SYMBOL(g_jacobi_stamps), h, sizeof(h)) != hipSuccess) return -1;
+    }
+    return 0;
+}
+#endif
+
+#ifdef VI_STAMPS
+extern "C" int vi_debug_jacobi_phases(double* out, int reset)
+{
+    unsigned long long h[16];
+    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_jacobi_phases), sizeof(h)) != hipSuccess) return -1;
+    for (int i = 0; i < 16; ++i) out[i] = (double)h[i];
+    if (reset) {
+        memset(h, 0, sizeof(h));
+        if (hipMemcpyToSymbol(HIP_SYMBOL(g_jacobi_phases), h, sizeof(h)) != hipSuccess) return -1;
     }
     return 0;
 }

@@ -54,42 +54,75 @@ __device__ __forceinline__ void lds_wait(int* w, int target, int& bad)
     asm volatile("" ::: "memory");
 }
 
+// A solve is four phases - set-up (a function of N alone), load, iterate, finish (truncation, replay) - which jacobi_system_v2 runs
+// one after the other; the stamped build times them one by one (VI_PHASE).  A kernel with persistent workgroups that arranged them
+// differently - the load of the next system under the replay of the current one - was built on them, measured and dropped
+// (tools/experiments/k3_persistent_workgroups.patch, profiles/r14_k3_fixed_cost.txt).
+
 // blockDim.x = 64 + NU, NU = the number of super-blocks rounded up to whole waves; requires 3 <= M <= 64 (N >= 9).
 // LDS: vi_jacobi_v2_lds_bytes(N).
-__device__ __forceinline__ void jacobi_system_v2(
-    unsigned char* lds_raw, int N, const double* __restrict__ Xs, double sc, const double* __restrict__ ys, double rcond,
-    double abs_floor, double* __restrict__ Cs, int* __restrict__ rank_s, double2* __restrict__ logp, int max_sweeps,
-    int* __restrict__ sweeps_s, double* __restrict__ lam_s, int lam_raw, int* __restrict__ nround_s,
-    unsigned long long* __restrict__ round_acc, double conv_tol = 0.0)
-{
-    const int NT = blockDim.x;
-    const int Np = (N + 3) & ~3;
-    const int m = Np >> 1;
-    const int M = Np >> 2;
-    const int nsb = (M * (M - 1)) >> 1;
-    const int ntri = 16 * nsb + 10 * M;
-    const int dg = 16 * nsb;
-    double* A = reinterpret_cast<double*>(lds_raw);                          // [ntri] the slot-indexed image, as in jacobi_system
-    double* yv = A + ntri;                                                   // [2][Np]
-    double2* cs0 = reinterpret_cast<double2*>(yv + 2 * Np);                  // [2][4][M] rotations of a round, double-buffered
-    double* nd = reinterpret_cast<double*>(cs0 + 8 * M);                     // [16]
-    double* mb = nd + 16;                                                    // [4][M] mailbox: cross parts of the next diagonal blocks
-    int* sync = reinterpret_cast<int*>(mb + 4 * M);                          // [0] mailbox posted [2] stores of the round landed
-    int* dtab = sync + 4;                                                    // [14][M] permuted destinations of diagonal blocks and y
+struct V2Frame {
+    int N, NT, Np, m, M, nsb, ntri, dg, tid, nw;
+    double* A;                  // [ntri] the slot-indexed image, as in jacobi_system
+    double* yv;                 // [2][Np]
+    double2* cs0;               // [2][4][M] rotations of a round, double-buffered
+    double* nd;                 // [16]
+    double* mb;                 // [4][M] mailbox: cross parts of the next diagonal blocks
+    int* sync;                  // [0] mailbox posted [2] stores of the round landed
+    int* dtab;                  // [14][M] permuted destinations of diagonal blocks and y
+    __device__ __forceinline__ V2Frame(unsigned char* lds_raw, int N_)
+    {
+        N = N_;
+        NT = blockDim.x;
+        Np = (N + 3) & ~3;
+        m = Np >> 1;
+        M = Np >> 2;
+        nsb = (M * (M - 1)) >> 1;
+        ntri = 16 * nsb + 10 * M;
+        dg = 16 * nsb;
+        A = reinterpret_cast<double*>(lds_raw);
+        yv = A + ntri;
+        cs0 = reinterpret_cast<double2*>(yv + 2 * Np);
+        nd = reinterpret_cast<double*>(cs0 + 8 * M);
+        mb = nd + 16;
+        sync = reinterpret_cast<int*>(mb + 4 * M);
+        dtab = sync + 4;
+        tid = threadIdx.x;
+        nw = NT >> 6;
+    }
+};
 
-    const int tid = threadIdx.x;
-    const int nw = NT >> 6;
+// What the set-up leaves in the registers of an update thread: its super-block (a < b), k = b(b-1)/2 + a, and where its sixteen
+// elements go after a round.
+struct V2Geo {
+    int ka, kb, ksrc, dst[16];
+    bool live;
+    int serves, q0;             // my block holds the cross part of the next diagonal block of match `serves`, at q0 + {0,1,4,5}
+};
+
+// Where a solve stands between its phases.
+struct V2Run {
+    int sweep, ycur;            // ycur: the half of yv that holds the right-hand side (in: where the load put it)
+    bool converged;
+    int64_t nround;
+};
+
+// ---- set-up: the block -> thread map, the destinations, wave 0's table.  Three barriers; uses the image as scratch. ----------
+__device__ __forceinline__ void v2_setup(const V2Frame& f, V2Geo& g)
+{
+    const int NT = f.NT, M = f.M, nsb = f.nsb, tid = f.tid;
+    int* dtab = f.dtab;
     const bool setup = tid < 64;                                             // wave 0
 
     // ---- update threads: my super-block (a < b), k = b(b-1)/2 + a = tid - 64
     int ka = 0, kb = 1, ksrc = 0, dst[16];
     bool live = false;
-    int serves = -1, q0 = 0;            // my block holds the cross part of the next diagonal block of match `serves`, at q0 + {0,1,4,5}
+    int serves = -1, q0 = 0;
     // ---- which update thread owns which super-block: the M blocks that hold the cross part of a next diagonal block go to the
     //      first M update threads (wave 1, which runs its update at raised priority and posts the mailbox early), thread 64 + a'
     //      holding the block of match a'; the others follow in natural order.  The table lives where the image goes afterwards.
     {
-        int* otab = reinterpret_cast<int*>(A);                       // [NT] block of update thread u
+        int* otab = reinterpret_cast<int*>(f.A);                     // [NT] block of update thread u
         int* wcnt = otab + NT;                                       // [nw] non-designated blocks per wave
         const int lane = tid & 63, wv = tid >> 6;
         const int kn = tid - 64;                                     // natural block of this thread
@@ -156,27 +189,105 @@ __device__ __forceinline__ void jacobi_system_v2(
             }
         }
     }
+    g.ka = ka;
+    g.kb = kb;
+    g.ksrc = ksrc;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) g.dst[e] = dst[e];
+    g.live = live;
+    g.serves = serves;
+    g.q0 = q0;
+}
 
-    // ---- load (slot s holds original index s) ---------------------------------------------------------
+// ---- load (slot s holds original index s), row by row: wave w of the nwl loading waves takes rows w, w + nwl, ... of the lower
+//      triangle, lane l the elements j = 2l, 2l + 1 (and 128 + 2l, 128 + 2l + 1: Np <= 256) up to the diagonal - one 16-byte load
+//      where the row starts on a 16-byte boundary, four rows (eight loads) in flight per thread.  Rows N ... Np - 1 are the
+//      padding: zeros.  yd[0 .. Np) takes the right-hand side (thread tl of ntl).  Returns this thread's share of max|diag| (a
+//      maximum: the order it is taken in does not show).  No barrier.  (The element-wise loop it replaces - an integer division
+//      per element, half of its iterations above the diagonal, one load in flight - was 4.2 % of a walk solve's cycles.)
+__device__ __forceinline__ double v2_load_rows(const V2Frame& f, const double* __restrict__ Xs, const double* __restrict__ ys,
+                                               double* yd, int w, int nwl, int tl, int ntl)
+{
+    constexpr int UR = 4;
+    const int N = f.N, Np = f.Np, M = f.M, nsb = f.nsb, dg = f.dg, lane = f.tid & 63;
+    double* A = f.A;
     double mxd = 0.0;
-    for (int e = tid; e < Np * Np; e += NT) {
-        const int i = e / Np, j = e - i * Np;
-        if (j > i) continue;
-        const double v = (i < N && j < N) ? Xs[(int64_t)i * N + j] : 0.0;
-        A[tri4(i, j, M)] = v;
-        if (i == j) mxd = fmax(mxd, fabs(v));
+    for (int i0 = w; i0 < Np; i0 += UR * nwl) {
+        double2 v[UR][2];
+#pragma unroll
+        for (int u = 0; u < UR; ++u) {
+            const int i = i0 + u * nwl;
+            const double* row = Xs + (int64_t)i * N;
+            const bool al = (reinterpret_cast<uintptr_t>(row) & 15) == 0;
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                const int j = 2 * lane + 128 * p;
+                v[u][p] = make_double2(0.0, 0.0);
+                if (i < N && j <= i) {
+                    if (al && j < i) {
+                        v[u][p] = *reinterpret_cast<const double2*>(row + j);
+                    } else {
+                        v[u][p].x = row[j];
+                        if (j < i) v[u][p].y = row[j + 1];
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < UR; ++u) {
+            const int i = i0 + u * nwl;
+            const int a = i >> 2, r = i & 3, base = (a * (a - 1)) >> 1;
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                const int j = 2 * lane + 128 * p;
+                if (i < Np && j <= i) {
+                    // tri4(i, j, M) and tri4(i, j + 1, M) for j <= i, j even: both in block column b <= a
+                    const int b = j >> 2, c = j & 3;
+                    const int s0 = b == a ? dg + j10(c, r) * M + a : (4 * c + r) * nsb + base + b;
+                    const int s1 = b == a ? dg + j10(c + 1, r) * M + a : s0 + 4 * nsb;
+                    A[s0] = v[u][p].x;
+                    if (j < i) A[s1] = v[u][p].y;
+                    if (j == i) mxd = fmax(mxd, fabs(v[u][p].x));
+                    if (j + 1 == i) mxd = fmax(mxd, fabs(v[u][p].y));
+                }
+            }
+        }
     }
-    for (int s = tid; s < Np; s += NT) yv[s] = s < N ? ys[s] : 0.0;
+    for (int s = tl; s < Np; s += ntl) yd[s] = s < N ? ys[s] : 0.0;
+    return mxd;
+}
+
+// ---- end of a load: max|diag| of the workgroup, the counters at zero (v2_iterate counts its targets from zero); one barrier.
+__device__ __forceinline__ double v2_load_close(const V2Frame& f, double mxd)
+{
+    const int tid = f.tid;
     for (int o = 32; o > 0; o >>= 1) mxd = fmax(mxd, __shfl_xor(mxd, o));
-    if ((tid & 63) == 0) nd[tid >> 6] = mxd;
-    if (tid == 0) { sync[0] = 0; sync[1] = 0; sync[2] = 0; }
+    if ((tid & 63) == 0) f.nd[tid >> 6] = mxd;
+    if (tid == 0) { f.sync[0] = 0; f.sync[1] = 0; f.sync[2] = 0; }
     __syncthreads();
     mxd = 0.0;
-    for (int w = 0; w < nw; ++w) mxd = fmax(mxd, nd[w]);
-    const double drop = rcond * mxd;
-    const double eps2 = 2.220446049250313e-16 * 2.220446049250313e-16;
-    const double conv2 = conv_tol > 0.0 ? conv_tol * conv_tol : VI_CONV_FACTOR * VI_CONV_FACTOR * eps2;
-    int sweep = 0, ycur = 0;
+    for (int w = 0; w < f.nw; ++w) mxd = fmax(mxd, f.nd[w]);
+    return mxd;
+}
+
+// ---- iterate: sweeps until the votes end them or the cap does.  r.ycur says where the right-hand side lies (in and out). -------
+__device__ __forceinline__ void v2_iterate(const V2Frame& f, const V2Geo& g, double drop, double abs_floor, double conv2,
+                                           int max_sweeps, double2* __restrict__ logp, V2Run& run)
+{
+    const int Np = f.Np, m = f.m, M = f.M, nsb = f.nsb, dg = f.dg, tid = f.tid, nw = f.nw;
+    double* A = f.A;
+    double* yv = f.yv;
+    double2* cs0 = f.cs0;
+    double* mb = f.mb;
+    int* sync = f.sync;
+    const int* dtab = f.dtab;
+    const bool setup = tid < 64;                                             // wave 0
+    const int ka = g.ka, kb = g.kb, ksrc = g.ksrc, serves = g.serves, q0 = g.q0;
+    const bool live = g.live;
+    int dst[16];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) dst[e] = g.dst[e];
+    int sweep = 0, ycur = run.ycur;
     bool converged = false;
     int64_t nround = 0;
     int bad = 0;                                   // a counter did not arrive (never seen; ends as "not converged")
@@ -389,8 +500,25 @@ __device__ __forceinline__ void jacobi_system_v2(
         }
     }
     if (__syncthreads_or(bad)) converged = false;
-    // ---- truncated solve in the eigenbasis (slot order = original order): as jacobi_system -----------------------------
-    double* yc = yv + ycur * Np;
+    run.sweep = sweep;
+    run.ycur = ycur;
+    run.converged = converged;
+    run.nround = nround;
+}
+
+// ---- finish, first part: the truncated solve in the eigenbasis (slot order = original order), as jacobi_system, and the
+//      per-system outputs.  Three barriers; behind the second one nobody reads the image any more.
+__device__ __forceinline__ void v2_truncate(const V2Frame& f, const V2Run& run, double sc, double rcond, int* __restrict__ rank_s,
+                                            int max_sweeps, int* __restrict__ sweeps_s, double* __restrict__ lam_s, int lam_raw,
+                                            int* __restrict__ nround_s, unsigned long long* __restrict__ round_acc)
+{
+    const int N = f.N, NT = f.NT, Np = f.Np, M = f.M, dg = f.dg, tid = f.tid, nw = f.nw;
+    const double* A = f.A;
+    double* nd = f.nd;
+    const int sweep = run.sweep;
+    const bool converged = run.converged;
+    const int64_t nround = run.nround;
+    double* yc = f.yv + run.ycur * Np;
     double mx = 0.0;
     for (int i = tid; i < Np; i += NT) mx = fmax(mx, fabs(A[dg + (i & 3) * M + (i >> 2)]));
     for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
@@ -419,9 +547,18 @@ __device__ __forceinline__ void jacobi_system_v2(
         if (nround_s) *nround_s = (int)nround;
         if (round_acc) atomicAdd(round_acc, (unsigned long long)nround);
     }
-    if (tid < 64) {
+}
+
+// ---- finish, second part, WAVE 0 ONLY: C = V g, the rotation log replayed in reverse on the vector in the wave's registers
+//      (lane a: the four entries of match a).  Reads yv[run.ycur] once at the start; no other LDS access, no barrier.
+__device__ __forceinline__ WaveReplay v2_replay(const V2Frame& f, const V2Run& run, const double2* __restrict__ logp)
+{
+    const int m = f.m, M = f.M, tid = f.tid;
+    const int64_t nround = run.nround;
+    const double* yc = f.yv + run.ycur * f.Np;
+    WaveReplay W;
+    {
         constexpr int PF = 4;
-        WaveReplay W;
         W.init(tid, M);
         W.load(yc, M);
         const bool has = tid < M;
@@ -442,10 +579,102 @@ __device__ __forceinline__ void jacobi_system_v2(
             for (int u = 0; u < PF; ++u)
                 if (u < nb) W.round(pf[u], ((r1 - 1 - u) % m) == 0);
         }
-        W.store(yc, M);
     }
-    __syncthreads();
-    for (int s = tid; s < N; s += NT) Cs[s] = yc[s];
+    return W;
 }
+
+// The same replay with the log read AHEAD: the batches above wait for the memory latency once per four rounds (stamped, walk
+// systems of N = 144: 690 cycles a round, 16 % of a solve, for ~150 cycles of arithmetic).  Here DEPTH rounds are in flight at any
+// time: a slot of the window is loaded again, for the round DEPTH further down, as soon as its round is applied.  The same rounds
+// in the same order with the same (c, s): the same bits.  (DEPTH x 16 registers: for the kernels that only solve, not k_brent_warm.)
+template <int DEPTH>
+__device__ __forceinline__ WaveReplay v2_replay_ahead(const V2Frame& f, const V2Run& run, const double2* __restrict__ logp)
+{
+    const int m = f.m, M = f.M, tid = f.tid;
+    const int nround = (int)run.nround;
+    const double* yc = f.yv + run.ycur * f.Np;
+    WaveReplay W;
+    W.init(tid, M);
+    W.load(yc, M);
+    const bool has = tid < M;
+    // The loads carry no condition (a lane without a match reads lane 0's entry, a slot past the first round reads round 0: the
+    // log of a system holds at least one sweep) and the choice between what was loaded and (1, 0) is made where the round is
+    // applied: conditional loads made the compiler wait for all of them at the head of the loop.
+    const double2* lbase = logp + (has ? tid : 0);
+    double2 pf[DEPTH][4];
+    auto issue = [&](double2 (&p)[4], int rr) {
+        const double2* lp = lbase + (rr > 0 ? rr : 0) * (int64_t)(4 * M);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) p[j] = lp[j * M];
+    };
+    int rm = nround > 0 ? (nround - 1) % m : 0;                    // the round's place in its sweep: 0 = the intra-unit round
+    auto apply = [&](const double2 (&p)[4]) {
+        double2 q[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) q[j] = has ? p[j] : make_double2(1.0, 0.0);
+        W.round(q, rm == 0);
+        rm = rm == 0 ? m - 1 : rm - 1;
+    };
+#pragma unroll
+    for (int u = 0; u < DEPTH; ++u) issue(pf[u], nround - 1 - u);
+    int r1 = nround;
+    for (; r1 >= DEPTH; r1 -= DEPTH) {
+#pragma unroll
+        for (int u = 0; u < DEPTH; ++u) {
+            apply(pf[u]);
+            issue(pf[u], r1 - 1 - u - DEPTH);
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < DEPTH; ++u)
+        if (u < r1) apply(pf[u]);
+    return W;
+}
+
+// diagnostic build (vi_jacobi.hip under VI_STAMPS): cycles of thread 0 per phase, summed over every workgroup
+#ifndef VI_PHASE
+#define VI_PHASE(k)
+#define VI_PHASE_COUNT()
+#endif
+
+// One system, the phases one after the other.  AHEAD > 0: the replay reads the log that many rounds ahead.
+template <int AHEAD = 0>
+__device__ __forceinline__ void jacobi_system_v2(
+    unsigned char* lds_raw, int N, const double* __restrict__ Xs, double sc, const double* __restrict__ ys, double rcond,
+    double abs_floor, double* __restrict__ Cs, int* __restrict__ rank_s, double2* __restrict__ logp, int max_sweeps,
+    int* __restrict__ sweeps_s, double* __restrict__ lam_s, int lam_raw, int* __restrict__ nround_s,
+    unsigned long long* __restrict__ round_acc, double conv_tol = 0.0)
+{
+    const V2Frame f(lds_raw, N);
+    V2Geo g;
+#ifdef VI_STAMPS
+    unsigned long long phase_t = __builtin_readcyclecounter();
+#endif
+    v2_setup(f, g);
+    VI_PHASE(0);
+    const double mxd = v2_load_close(f, v2_load_rows(f, Xs, ys, f.yv, f.tid >> 6, f.nw, f.tid, f.NT));
+    VI_PHASE(1);
+    const double drop = rcond * mxd;
+    const double eps2 = 2.220446049250313e-16 * 2.220446049250313e-16;
+    const double conv2 = conv_tol > 0.0 ? conv_tol * conv_tol : VI_CONV_FACTOR * VI_CONV_FACTOR * eps2;
+    V2Run run;
+    run.ycur = 0;
+    v2_iterate(f, g, drop, abs_floor, conv2, max_sweeps, logp, run);
+    VI_PHASE(2);
+    v2_truncate(f, run, sc, rcond, rank_s, max_sweeps, sweeps_s, lam_s, lam_raw, nround_s, round_acc);
+    VI_PHASE(3);
+    double* yc = f.yv + run.ycur * f.Np;
+    if (f.tid < 64) {                                            // back into the buffer it came from
+        if (AHEAD > 0) v2_replay_ahead<(AHEAD > 0 ? AHEAD : 1)>(f, run, logp).store(yc, f.M);
+        else v2_replay(f, run, logp).store(yc, f.M);
+    }
+    VI_PHASE(4);
+    __syncthreads();
+    for (int s = f.tid; s < N; s += f.NT) Cs[s] = yc[s];
+    VI_PHASE(5);
+    VI_PHASE_COUNT();
+}
+
+constexpr int V2_REPLAY_AHEAD = 8;       // rounds of the log in flight in the replay of the kernel that only solves
 
 }  // namespace
