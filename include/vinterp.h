@@ -167,6 +167,25 @@ int  vi_eval_f64(vi_model* model, int64_t Q, const double* d_lat, const double* 
 int  vi_eval_track_f64(vi_model* model, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt,
                        const int32_t* d_rec, const double* d_w, int64_t R, const double* d_C,
                        const double* d_hull_eq, int32_t F, double hull_tol, double* d_out);
+/* The gradient of the fitted parameter at points that each carry their OWN time: vi_eval_grad_f64's values with
+ * vi_eval_track_f64's row selection, one call for a whole trajectory in place of one vi_eval_grad_f64 call per record.
+ * d_out[q*3 + c], the layout of vi_eval_grad_f64: c = z, theta', phi' as vi_grad_basis_f64 defines them (VI_FRAME_MODEL, below)
+ * or east, north, geodetic up (VI_FRAME_ENU: each point's triple turned by the point's own matrix in the kernel).  With
+ * G(r, q)[c] = sum_n grad_basis[q][c][n] * d_C[r*N + n]:
+ *   nearest mode (d_w == NULL):   d_out[q] = G(d_rec[q], q)
+ *   interpolation (d_w != NULL):  d_out[q] = (1 - d_w[q]) * G(d_rec[q], q) + d_w[q] * G(d_rec[q] + 1, q), as written: a NaN in
+ *                                 either row of the pair gives NaN at any d_w
+ * A NaN triple where the point fails the hull test (the mask pass of vi_eval_track_f64; F = 0: no test), where d_rec[q] < 0,
+ * where a row the point needs is >= R (R = 0: every point) and where such a row holds a NaN; a NaN row reaches no other row's
+ * points (rows are selected, never multiplied by zero).  d_C (R x N, as stored) is never read outside its R rows.  A point's
+ * bits depend on the point, its row(s) and d_w[q], not on the other points or their order.  Correct for ANY order of d_rec;
+ * the cost grows with the span of rows in a group of 64 consecutive points as in vi_eval_track_f64 (windows of 4 rows, 3 when
+ * blending): SORT the points by d_rec.  sphharmlag only, at the orders of vi_grad_basis_f64 - (MAXL, MAXK) within (6, 4),
+ * (12, 8) or (2, 12) -, else VI_ERR_UNSUPPORTED.  Kernel K2tg (csrc/vi_basis.hip).  Asynchronous on the context's stream;
+ * timed for vi_eval_kernel_ms like its siblings (tests/test_gpu_track_gradient.py). */
+int  vi_eval_track_grad_f64(vi_model* model, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt,
+                            const int32_t* d_rec, const double* d_w, int64_t R, const double* d_C,
+                            const double* d_hull_eq, int32_t F, double hull_tol, int32_t frame, double* d_out);
 /* Line integrals of the fitted parameter along straight rays that each carry their OWN time (slant TEC between a receiver and a
  * satellite, an occultation link, an optical column): one call for all rays.  d_a, d_b: start and end of the P rays in ECEF
  * metres, planar (3 x P: X of all rays, then Y, then Z); d_rec, d_w, R, d_C select and blend the coefficient rows as in
@@ -274,7 +293,7 @@ int    vi_reduce_basis_f64(vi_model* model, int64_t outer, int64_t L, int64_t in
  * BASELINE configs[4] sweeps against the 1e-6 tolerance.  Orders with an fp32 kernel: (MAXL, MAXK) = (6,4), (2,8), (12,8);
  * others return VI_ERR_UNSUPPORTED from vi_eval_f64 while the flag is set. */
 int  vi_model_set_eval_precision(vi_model* model, int32_t chain_f32);
-/* device time (ms) of the evaluation kernel launches of the last vi_eval_f64 / vi_eval_track_f64 / vi_eval_slant_f64 / vi_eval_slant_basis_f64 / vi_eval_resident_f64 /
+/* device time (ms) of the evaluation kernel launches of the last vi_eval_f64 / vi_eval_track_f64 / vi_eval_track_grad_f64 / vi_eval_slant_f64 / vi_eval_slant_basis_f64 / vi_eval_resident_f64 /
  * vi_eval_resident_err_f64 / vi_eval_resident_peak_f64 call on this context, from HIP events recorded on the context's stream around them (the preparation kernels are excluded).
  * The events are recorded only while vi_ctx_set_eval_timing(ctx, 1) is in force (default: off - the pair costs a 0.2 ms call about 7 us);
  * vi_eval_kernel_ms fails with VI_ERR_ARG while it is off or before a call has been timed. */

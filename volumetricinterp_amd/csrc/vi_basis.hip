@@ -163,35 +163,12 @@ __device__ __forceinline__ void enu_frame(const SphDev& M, const Geom& g, double
     }
 }
 
-template <int LCAP, int KCAP, int MODE, bool ENU>
-__global__ __launch_bounds__(BLOCK) void k_grad_sph(SphDev M, int64_t P, const double* __restrict__ lat,
-                                                    const double* __restrict__ lon, const double* __restrict__ alt,
-                                                    const double* __restrict__ Cv, const unsigned char* __restrict__ mask,
-                                                    double* __restrict__ Gout, int64_t ld_p, int64_t ld_c, int64_t ld_n)
+// The chains of the gradient basis at one point, the one copy k_grad_sph and K2tg (k_track_grad_sph) instantiate:
+// sink.term(n, tz, tt, tp, L0k, L1k) is called once per basis function n = k L2 + r; its three gradient components at the point
+// are tz (L0k + 2 L1k), tt L0k and tp L0k - handed over as factors, so that k_grad_sph's sink forms them where that kernel did.
+template <int LCAP, int KCAP, class Sink>
+__device__ __forceinline__ void grad_point(const SphDev& M, const Geom& g, Sink& sink)
 {
-    constexpr bool CONTRACT = MODE == GRAD_CONTRACT;
-    double az = 0.0, at = 0.0, ap = 0.0;
-    const int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    const int64_t pc = p < P ? p : P - 1;
-    bool active = p < P;
-    double* Gp = Gout + pc * ld_p;
-    if (MODE == GRAD_RESIDENT && mask) {
-        const bool in = mask[pc] != 0;
-        if (active && !in) {
-            const double nan = __builtin_nan("");
-            for (int n = 0; n < M.N; ++n) {
-                double* o = Gp + (int64_t)n * ld_n;
-                o[0] = nan;
-                o[ld_c] = nan;
-                o[2 * ld_c] = nan;
-            }
-        }
-        active = active && in;
-        if (!__any(active)) return;           // whole wave outside the hull: skip the chains
-    }
-    const Geom g = sph_geom(M, lat[pc], lon[pc], alt[pc]);
-    double F[9];
-    if (ENU) enu_frame(M, g, lat[pc], lon[pc], F);
     const int maxl = M.maxl, maxk = M.maxk, L2 = maxl * maxl;
     double L0[KCAP], L1[KCAP];          // L_k(z) and L^(1)_{k-1}(z)
     laguerre<KCAP>(maxk, g.z, L0);
@@ -264,38 +241,86 @@ __global__ __launch_bounds__(BLOCK) void k_grad_sph(SphDev M, int64_t P, const d
                             const double tt = e * (-(v + 1.0) * x * Q0 + (v - ms + 1.0) * Q1) * trig * inv_hr;
                             const double tp = e * Q0 * dtrig * inv_hr;
 #pragma unroll
-                            for (int k = 0; k < KCAP; ++k) {
-                                if (CONTRACT) {
-                                    if (k < maxk) {
-                                        const double cf = Cv[k * L2 + r];
-                                        az = fma(tz * (L0[k] + 2.0 * L1[k]), cf, az);
-                                        at = fma(tt * L0[k], cf, at);
-                                        ap = fma(tp * L0[k], cf, ap);
-                                    }
-                                } else if (k < maxk && active) {
-                                    double* o = Gp + (int64_t)(k * L2 + r) * ld_n;
-                                    const double gz = tz * (L0[k] + 2.0 * L1[k]), gt = tt * L0[k], gp = tp * L0[k];
-                                    if (ENU) {
-                                        o[0] = fma(F[0], gz, fma(F[1], gt, F[2] * gp));
-                                        o[ld_c] = fma(F[3], gz, fma(F[4], gt, F[5] * gp));
-                                        o[2 * ld_c] = fma(F[6], gz, fma(F[7], gt, F[8] * gp));
-                                    } else {
-                                        o[0] = gz;
-                                        o[ld_c] = gt;
-                                        o[2 * ld_c] = gp;
-                                    }
-                                }
-                            }
+                            for (int k = 0; k < KCAP; ++k)
+                                if (k < maxk) sink.term(k * L2 + r, tz, tt, tp, L0[k], L1[k]);
                         }
                     }
                 }
             }
         }
     }
-    if (CONTRACT && active) {
-        Gp[0] = az;
-        Gp[ld_c] = at;
-        Gp[2 * ld_c] = ap;
+}
+
+// what k_grad_sph does with a term: adds its product with the coefficient to the point's triple (GRAD_CONTRACT), or stores it
+template <int MODE, bool ENU>
+struct GradSink {
+    const double* __restrict__ Cv;
+    double* Gp;
+    int64_t ld_c, ld_n;
+    double F[9];
+    bool active;
+    double az, at, ap;
+    __device__ __forceinline__ void term(int n, double tz, double tt, double tp, double L0k, double L1k)
+    {
+        if (MODE == GRAD_CONTRACT) {
+            const double cf = Cv[n];
+            az = fma(tz * (L0k + 2.0 * L1k), cf, az);
+            at = fma(tt * L0k, cf, at);
+            ap = fma(tp * L0k, cf, ap);
+        } else if (active) {
+            double* o = Gp + (int64_t)n * ld_n;
+            const double gz = tz * (L0k + 2.0 * L1k), gt = tt * L0k, gp = tp * L0k;
+            if (ENU) {
+                o[0] = fma(F[0], gz, fma(F[1], gt, F[2] * gp));
+                o[ld_c] = fma(F[3], gz, fma(F[4], gt, F[5] * gp));
+                o[2 * ld_c] = fma(F[6], gz, fma(F[7], gt, F[8] * gp));
+            } else {
+                o[0] = gz;
+                o[ld_c] = gt;
+                o[2 * ld_c] = gp;
+            }
+        }
+    }
+};
+
+template <int LCAP, int KCAP, int MODE, bool ENU>
+__global__ __launch_bounds__(BLOCK) void k_grad_sph(SphDev M, int64_t P, const double* __restrict__ lat,
+                                                    const double* __restrict__ lon, const double* __restrict__ alt,
+                                                    const double* __restrict__ Cv, const unsigned char* __restrict__ mask,
+                                                    double* __restrict__ Gout, int64_t ld_p, int64_t ld_c, int64_t ld_n)
+{
+    const int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const int64_t pc = p < P ? p : P - 1;
+    bool active = p < P;
+    double* Gp = Gout + pc * ld_p;
+    if (MODE == GRAD_RESIDENT && mask) {
+        const bool in = mask[pc] != 0;
+        if (active && !in) {
+            const double nan = __builtin_nan("");
+            for (int n = 0; n < M.N; ++n) {
+                double* o = Gp + (int64_t)n * ld_n;
+                o[0] = nan;
+                o[ld_c] = nan;
+                o[2 * ld_c] = nan;
+            }
+        }
+        active = active && in;
+        if (!__any(active)) return;           // whole wave outside the hull: skip the chains
+    }
+    const Geom g = sph_geom(M, lat[pc], lon[pc], alt[pc]);
+    GradSink<MODE, ENU> sink;
+    sink.Cv = Cv;
+    sink.Gp = Gp;
+    sink.ld_c = ld_c;
+    sink.ld_n = ld_n;
+    sink.active = active;
+    sink.az = sink.at = sink.ap = 0.0;
+    if (ENU) enu_frame(M, g, lat[pc], lon[pc], sink.F);
+    grad_point<LCAP, KCAP>(M, g, sink);
+    if (MODE == GRAD_CONTRACT && active) {
+        Gp[0] = sink.az;
+        Gp[ld_c] = sink.at;
+        Gp[2 * ld_c] = sink.ap;
     }
 }
 
@@ -1133,6 +1158,109 @@ __global__ __launch_bounds__(BLOCK) void k_track_sph(SphDev M, int64_t Q, const 
 }
 
 // ---------------------------------------------------------------------------------------------
+// K2tg: gradients along a trajectory, every point at its own time (vi_eval_track_grad_f64): k_grad_sph's chains (grad_point) in
+// K2t's frame.  A workgroup is ONE wave of 64 points; it finds the lowest and highest row its live lanes need (shuffles: nothing
+// assumes sorted input) and stages a window of TT RAW coefficient rows from the lowest one in LDS - the gradient needs
+// scale[r] P(nu) and scale1[r] P(nu + 1), so the rows k_prep_coef prepares for the density do not serve; rows past R - 1 are
+// zero-filled and never selected - then runs the chains once for 3 TT accumulators, the coefficients read from LDS at
+// wave-uniform addresses.  Each lane takes the triple of its own row (the pair of triples, when blending) by compare-select,
+// never a product with zero, from the one window that holds its rows; windows follow each other as in K2t (one shared row when
+// blending) until the wave's highest row is covered.  Every row's accumulators see the terms in the order k_grad_sph adds them,
+// whatever the row's place in the window: a point's bits depend on the point, its row(s) and w only.  With ENU the point's
+// matrix (enu_frame) turns the finished triple in the epilogue.  A wave without a live lane leaves before anything is staged.
+constexpr int TRACK_GRAD_TT = 4;    // the window
+
+template <int TT>
+struct GradTrackSink {
+    const double* shC;      // LDS [TT][N], raw rows
+    int N;
+    double az[TT], at[TT], ap[TT];
+    __device__ __forceinline__ void term(int n, double tz, double tt, double tp, double L0k, double L1k)
+    {
+        const double gz = tz * (L0k + 2.0 * L1k), gt = tt * L0k, gp = tp * L0k;
+#pragma unroll
+        for (int t = 0; t < TT; ++t) {
+            const double cf = shC[t * N + n];
+            az[t] = fma(gz, cf, az[t]);
+            at[t] = fma(gt, cf, at[t]);
+            ap[t] = fma(gp, cf, ap[t]);
+        }
+    }
+};
+
+template <int LCAP, int KCAP, int TT, bool INTERP, bool ENU>
+__global__ __launch_bounds__(TRACK_BLOCK) void k_track_grad_sph(SphDev M, int64_t Q, const double* __restrict__ lat,
+                                                                const double* __restrict__ lon, const double* __restrict__ alt,
+                                                                const int* __restrict__ rec, const double* __restrict__ wgt, int R,
+                                                                const double* __restrict__ C,
+                                                                const unsigned char* __restrict__ mask, int F,
+                                                                double* __restrict__ out)
+{
+    constexpr int PAIR = INTERP ? 1 : 0;
+    constexpr int STEP = TT - PAIR;                     // rows from one window to the next
+    static_assert(STEP >= 1, "a blending window holds at least two rows");
+    extern __shared__ __align__(16) double sh[];        // [TT][N] the window
+    const double nan = __builtin_nan("");
+    const int64_t q = (int64_t)blockIdx.x * TRACK_BLOCK + threadIdx.x;
+    const int64_t qc = q < Q ? q : Q - 1;
+    const int r = rec[qc];
+    const bool live = track_live(q, qc, Q, r, R, PAIR, mask, F);
+    if (!__any(live)) {                                 // (the whole workgroup: no barrier has been met)
+        if (q < Q) out[3 * q] = out[3 * q + 1] = out[3 * q + 2] = nan;
+        return;
+    }
+    int lo = live ? r : 0x7fffffff, hi = live ? r + PAIR : -1;
+#pragma unroll
+    for (int off = TRACK_BLOCK / 2; off > 0; off >>= 1) {
+        lo = min(lo, __shfl_xor(lo, off, TRACK_BLOCK));
+        hi = max(hi, __shfl_xor(hi, off, TRACK_BLOCK));
+    }
+    lo = __builtin_amdgcn_readfirstlane(lo);            // 0 <= lo <= hi <= R - 1
+    hi = __builtin_amdgcn_readfirstlane(hi);
+    const int N = M.N;
+    const Geom g = sph_geom(M, lat[qc], lon[qc], alt[qc]);
+    const double w = INTERP ? wgt[qc] : 0.0;
+    double vz = nan, vt = nan, vp = nan;
+    for (int base = lo;; base += STEP) {                // lo <= base <= hi
+        __syncthreads();                                // the pass before has read the window
+        for (int i = threadIdx.x; i < TT * N; i += TRACK_BLOCK) sh[i] = i / N < R - base ? C[(int64_t)base * N + i] : 0.0;
+        __syncthreads();
+        GradTrackSink<TT> S;
+        S.shC = sh;
+        S.N = N;
+#pragma unroll
+        for (int t = 0; t < TT; ++t) S.az[t] = S.at[t] = S.ap[t] = 0.0;
+        grad_point<LCAP, KCAP>(M, g, S);
+        const int d = live ? r - base : -1;             // the lane's row in this window
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0, b0 = 0.0, b1 = 0.0, b2 = 0.0;
+#pragma unroll
+        for (int t = 0; t < TT; ++t) {
+            if (d == t) { a0 = S.az[t]; a1 = S.at[t]; a2 = S.ap[t]; }
+            if (INTERP && d + 1 == t) { b0 = S.az[t]; b1 = S.at[t]; b2 = S.ap[t]; }
+        }
+        if (d >= 0 && d < STEP) {
+            vz = INTERP ? (1.0 - w) * a0 + w * b0 : a0;
+            vt = INTERP ? (1.0 - w) * a1 + w * b1 : a1;
+            vp = INTERP ? (1.0 - w) * a2 + w * b2 : a2;
+        }
+        if (hi - base <= TT - 1) break;                 // wave-uniform
+    }
+    if (ENU) {
+        double Fm[9];
+        enu_frame(M, g, lat[qc], lon[qc], Fm);
+        const double gz = vz, gt = vt, gp = vp;
+        vz = fma(Fm[0], gz, fma(Fm[1], gt, Fm[2] * gp));
+        vt = fma(Fm[3], gz, fma(Fm[4], gt, Fm[5] * gp));
+        vp = fma(Fm[6], gz, fma(Fm[7], gt, Fm[8] * gp));
+    }
+    if (q < Q) {
+        out[3 * q] = live ? vz : nan;
+        out[3 * q + 1] = live ? vt : nan;
+        out[3 * q + 2] = live ? vp : nan;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // K2l: line integrals along straight rays, every ray at its own time (vi_eval_slant_f64).  Ray p runs from a_p to b_p (ECEF);
 // the part of it inside the hull is ONE interval [s0, s1] of the segment parameter (the hull is convex, its facets half-spaces),
 // and the integral is the caller's rule on [-1, 1] mapped onto that interval:
@@ -1940,33 +2068,62 @@ extern "C" int vi_basis_f64(vi_model* m, int64_t P, const double* d_lat, const d
     return VI_OK;
 }
 
-// The gradient kernel at the compiled order that holds the model's: (MAXL, MAXK) up to (6, 4), (12, 8) or (2, 12).
+// The gradient kernels at the compiled order that holds the model's: (MAXL, MAXK) up to (6, 4), (12, 8) or (2, 12).
 namespace {
-template <int MODE, bool ENU>
-int launch_grad_sph(vi_model* m, const char* who, int64_t P, const double* d_lat, const double* d_lon, const double* d_alt,
-                    const double* d_C, const unsigned char* d_mask, double* d_G, int64_t ld_p, int64_t ld_c, int64_t ld_n)
+// whether the model has a gradient basis at all (else the error is set)
+int grad_model_check(const vi_model* m, const char* who)
 {
     if (m->kind != VI_MODEL_SPHHARMLAG || !m->sph.scale1 || !m->sph.nu) {
         vi_set_error("%s: only the sphharmlag model provides a gradient basis", who);
         return VI_ERR_UNSUPPORTED;
     }
-    if (P == 0) return VI_OK;
-    VI_HIP(hipSetDevice(m->ctx->device));
-    const int L = m->sph.maxl, K = m->sph.maxk;
-    const dim3 grid(nblocks(P, BLOCK)), block(BLOCK);
-#define VI_GRAD(LL, KK)                                                                                                    \
-    hipLaunchKernelGGL((k_grad_sph<LL, KK, MODE, ENU>), grid, block, 0, m->ctx->stream, m->sph, P, d_lat, d_lon, d_alt, d_C, \
-                       d_mask, d_G, ld_p, ld_c, ld_n)
-    if (L <= 6 && K <= 4) VI_GRAD(6, 4);
-    else if (L <= 12 && K <= 8) VI_GRAD(12, 8);
-    else if (L <= 2 && K <= 12) VI_GRAD(2, 12);
-    else {
-        vi_set_error("%s: order MAXL=%d MAXK=%d beyond the compiled limits (6, 4), (12, 8) and (2, 12)", who, L, K);
-        return VI_ERR_UNSUPPORTED;
-    }
-#undef VI_GRAD
-    VI_HIP(hipGetLastError());
     return VI_OK;
+}
+
+// f(integral_constant LCAP, KCAP) at the first of those orders that holds the model's
+template <class F>
+int at_grad_cap(const vi_model* m, const char* who, F&& f)
+{
+    const int L = m->sph.maxl, K = m->sph.maxk;
+#define VI_CAP(LC, KC) \
+    if (L <= LC && K <= KC) return f(std::integral_constant<int, LC>{}, std::integral_constant<int, KC>{});
+    VI_CAP(6, 4) VI_CAP(12, 8) VI_CAP(2, 12)
+#undef VI_CAP
+    vi_set_error("%s: order MAXL=%d MAXK=%d beyond the compiled limits (6, 4), (12, 8) and (2, 12)", who, L, K);
+    return VI_ERR_UNSUPPORTED;
+}
+
+template <int MODE, bool ENU>
+int launch_grad_sph(vi_model* m, const char* who, int64_t P, const double* d_lat, const double* d_lon, const double* d_alt,
+                    const double* d_C, const unsigned char* d_mask, double* d_G, int64_t ld_p, int64_t ld_c, int64_t ld_n)
+{
+    const int rc = grad_model_check(m, who);
+    if (rc != VI_OK || P == 0) return rc;
+    VI_HIP(hipSetDevice(m->ctx->device));
+    return at_grad_cap(m, who, [&](auto lc, auto kc) -> int {
+        hipLaunchKernelGGL((k_grad_sph<lc, kc, MODE, ENU>), dim3(nblocks(P, BLOCK)), dim3(BLOCK), 0, m->ctx->stream, m->sph, P,
+                           d_lat, d_lon, d_alt, d_C, d_mask, d_G, ld_p, ld_c, ld_n);
+        VI_HIP(hipGetLastError());
+        return VI_OK;
+    });
+}
+
+// K2tg launch (vi_eval_track_grad_f64): w == nullptr is nearest mode.  C: the R raw rows.
+template <int LCAP, int KCAP>
+int launch_track_grad_sph(vi_model* m, int64_t Q, const double* lat, const double* lon, const double* alt, const int* rec,
+                          const double* w, int R, const double* C, const unsigned char* hull, int F, bool enu, double* out)
+{
+    const size_t shm = (size_t)TRACK_GRAD_TT * m->N * sizeof(double);       // at most 4 x 1152 doubles: 36 KB
+    return with_flag(w != nullptr, [&](auto interp) -> int {
+        return with_flag(enu, [&](auto e) -> int {
+            VI_HIP(hipFuncSetAttribute((const void*)k_track_grad_sph<LCAP, KCAP, TRACK_GRAD_TT, interp, e>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+            hipLaunchKernelGGL((k_track_grad_sph<LCAP, KCAP, TRACK_GRAD_TT, interp, e>), dim3(nblocks(Q, TRACK_BLOCK)),
+                               dim3(TRACK_BLOCK), shm, m->ctx->stream, m->sph, Q, lat, lon, alt, rec, w, R, C, hull, F, out);
+            VI_HIP(hipGetLastError());
+            return VI_OK;
+        });
+    });
 }
 }  // namespace
 
@@ -2411,6 +2568,31 @@ extern "C" int vi_eval_track_f64(vi_model* m, int64_t Q, const double* d_lat, co
     }
     return at_order_cap(m, "vi_eval_track_f64", [&](auto lc, auto kc) {
         return launch_track_sph<lc, kc>(m, Q, d_lat, d_lon, d_alt, d_rec, d_w, Ri, coef, d_mask, F, d_out);
+    });
+}
+
+// Gradients along a trajectory (include/vinterp.h): K2tg.  The hull pass of vi_eval_track_f64 and no coefficient preparation -
+// the kernel reads the R raw rows of d_C -, then one launch at the compiled gradient order that holds the model's.
+extern "C" int vi_eval_track_grad_f64(vi_model* m, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt,
+                                      const int32_t* d_rec, const double* d_w, int64_t R, const double* d_C,
+                                      const double* d_hull_eq, int32_t F, double hull_tol, int32_t frame, double* d_out)
+{
+    VI_REQUIRE(m && d_lat && d_lon && d_alt && d_rec && d_out, "null argument");
+    VI_REQUIRE(Q >= 0 && R >= 0 && F >= 0, "negative size");
+    VI_REQUIRE(R == 0 || d_C, "record count given without coefficients");
+    VI_REQUIRE(R <= 0x7fffffffLL, "more records than a 32-bit record index");
+    VI_REQUIRE(Q <= (int64_t)TRACK_BLOCK * 0x7fffffffLL, "more points than one launch takes");
+    VI_REQUIRE(F == 0 || d_hull_eq, "hull facet count given without facet equations");
+    VI_REQUIRE(frame == VI_FRAME_MODEL || frame == VI_FRAME_ENU, "frame must be VI_FRAME_MODEL or VI_FRAME_ENU");
+    int rc = grad_model_check(m, "vi_eval_track_grad_f64");
+    if (rc != VI_OK || Q == 0) return rc;
+    VI_HIP(hipSetDevice(m->ctx->device));
+    return at_grad_cap(m, "vi_eval_track_grad_f64", [&](auto lc, auto kc) -> int {
+        rc = prepare_call(m, Q, d_lat, d_lon, d_alt, d_hull_eq, F, hull_tol, 0, nullptr);
+        if (rc != VI_OK) return rc;
+        EvalTimer timer(m->ctx);
+        return launch_track_grad_sph<lc, kc>(m, Q, d_lat, d_lon, d_alt, d_rec, d_w, (int)R, d_C, F > 0 ? m->d_mask : nullptr,
+                                             (int)F, frame == VI_FRAME_ENU, d_out);
     });
 }
 

@@ -407,10 +407,29 @@ class Estimate(object):
         profiles.  times: naive-UTC datetimes or float unix seconds, of the shape of gdlat or one value for all points.
         outside='raise': a time out of range of the file raises as get_C does; 'nan': those points are NaN.  Same shape as
         gdlat; `out`: optional C-contiguous float64 array of that shape to write into."""
+        return self._along_track('vi_eval_track_f64', (), (), times, gdlat, gdlon, gdalt, check_hull, outside, out)
+
+    def track_gradient(self, times, gdlat, gdlon, gdalt, check_hull=True, outside='raise', frame='model', out=None):
+        """Gradients along a trajectory: element q is what self.gradient(times[q], gdlat[q], gdlon[q], gdalt[q], check_hull,
+        frame) returns - the record of get_C per point (with timeinterp the blend of the gradients of the two neighbours,
+        the gradient being linear in the coefficients), NaN triples outside the hull and where a record the point needs holds
+        a NaN - in ONE library call for all points (vi_eval_track_grad_f64, kernel K2tg) instead of one gradient call per
+        record.  times, outside as in track; frame as in gradient ('model': along z, theta, phi; 'enu': along local east,
+        north, up, rotated on the device).  Shape gdlat.shape + (3,); `out`: optional C-contiguous float64 array of that
+        shape to write into."""
+        if frame not in GRADIENT_FRAMES:
+            raise ValueError("frame must be 'model' or 'enu', not %r" % (frame,))
+        return self._along_track('vi_eval_track_grad_f64', (3,), (GRADIENT_FRAMES[frame],), times, gdlat, gdlon, gdalt, check_hull,
+                                 outside, out)
+
+    def _along_track(self, entry, width, extra, times, gdlat, gdlon, gdalt, check_hull, outside, out):
+        """What track and track_gradient share: the record (rec, w) of every point's time, the points sorted by record (stable),
+        the library's `entry` - points, the arguments of _upload_records, `extra` arguments in, (Q,) + width out - on device
+        copies, the result back in the caller's order: an array of shape gdlat.shape + width."""
         lat, lon, alt = ravel_points(gdlat, gdlon, gdalt)
         shape, Q = np.shape(gdlat), lat.size
         t0 = self._times_for(times, shape, 'gdlat')
-        out = _check_out(out, shape)
+        out = _check_out(out, shape + width)
         if Q == 0:
             return out
         rec, w = self.select_records(t0, outside)
@@ -418,10 +437,10 @@ class Estimate(object):
         with self.model.ctx.scope() as dev:
             dlat, dlon, dalt = dev.up(lat[order]), dev.up(lon[order]), dev.up(alt[order])
             records = self._upload_records(dev, rec[order], None if w is None else w[order], check_hull)
-            dO = dev.empty(Q)
-            _lib.check(_lib.lib.vi_eval_track_f64(self.model.handle(), Q, dlat.ptr, dlon.ptr, dalt.ptr, *records, dO.ptr),
-                       'vi_eval_track_f64')
-            out.reshape(-1)[order] = dO.download()
+            dO = dev.empty((Q,) + width)
+            _lib.check(getattr(_lib.lib, entry)(self.model.handle(), Q, dlat.ptr, dlon.ptr, dalt.ptr, *records, *extra, dO.ptr),
+                       entry)
+            out.reshape((Q,) + width)[order] = dO.download()
         return out
 
     def _times_for(self, times, shape, what):
