@@ -259,6 +259,24 @@ int  vi_eval_grad_basis_f64(vi_model* model, int64_t Q, const double* d_lat, con
  * K2e takes N <= 144 with Q even and d_Y / d_out 16-byte aligned; other shapes, and VINTERP_EVAL_RESIDENT=blas, go through
  * the library's product and a row dot, as vi_eval_err_f64 (tests/test_gpu_resident_error.py). */
 int  vi_eval_resident_err_f64(vi_model* model, int64_t Q, int64_t T, const double* d_Y, const double* d_dC, double* d_out);
+/* The uncertainty of the GRADIENT (the `graderr` the reference's Estimate.__call__ advertises, estimate.py:125-147): the 3 x 3
+ * covariance of the gradient at each point from the coefficient covariance, first-order error propagation through the three
+ * columns g_0, g_1, g_2 of the gradient basis at the point (components in the frame of the basis),
+ *   cov[c][d] = g_c^T 1/2 (dC + dC^T) g_d,
+ * its six distinct entries packed in the order (0,0) (1,1) (2,2) (0,1) (0,2) (1,2).  The standard error of component c is
+ * sqrt(cov[c][c]) - also vi_eval_resident_err_f64 on d_G with 3Q columns -, that of the gradient along a unit vector u
+ * sqrt(u^T cov u).  dC as stored, never assumed symmetric.  All six entries are NaN for a point outside the hull (a NaN column)
+ * and for a covariance holding a NaN; a negative diagonal entry of an indefinite dC is returned as it is.
+ *   vi_eval_resident_gradcov_f64  d_out[(t*6 + k)*Q + q] for the T row-major N x N covariances d_dC on the resident gradient
+ *                         basis d_G of vi_eval_grad_basis_f64 (N x 3 x Q).  The matrix-core kernel K2c takes N <= 144, any Q;
+ *                         other orders, and VINTERP_EVAL_RESIDENT=blas, go through the library's product and row dots.
+ *   vi_eval_grad_cov_f64  d_out[k*Q + q] for ONE covariance at arbitrary points: the gradient basis of a chunk of points is
+ *                         built in the context workspace (hull, F, hull_tol and frame as in vi_eval_grad_basis_f64) and the
+ *                         same kernel runs on it.  Models and orders as vi_eval_grad_basis_f64.
+ * Asynchronous on the context's stream; timed for vi_eval_kernel_ms like their siblings (tests/test_gpu_resident_gradcov.py). */
+int  vi_eval_resident_gradcov_f64(vi_model* model, int64_t Q, int64_t T, const double* d_G, const double* d_dC, double* d_out);
+int  vi_eval_grad_cov_f64(vi_model* model, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt,
+                          const double* d_dC, const double* d_hull_eq, int32_t F, double hull_tol, int32_t frame, double* d_out);
 /* Column maps of many timesteps on the same resident grid, without the volume.  The grid is seen as (outer, L, inner), point
  * q = (o*L + l)*inner + i, column m = o*inner + i: any axis of a C-ordered grid, the last one with inner = 1.  What a user of
  * Estimate.__call__ (estimate.py:110-123) takes from a (lat, lon, alt) volume per column: the peak of the parameter along
@@ -294,7 +312,7 @@ int    vi_reduce_basis_f64(vi_model* model, int64_t outer, int64_t L, int64_t in
  * others return VI_ERR_UNSUPPORTED from vi_eval_f64 while the flag is set. */
 int  vi_model_set_eval_precision(vi_model* model, int32_t chain_f32);
 /* device time (ms) of the evaluation kernel launches of the last vi_eval_f64 / vi_eval_track_f64 / vi_eval_track_grad_f64 / vi_eval_slant_f64 / vi_eval_slant_basis_f64 / vi_eval_resident_f64 /
- * vi_eval_resident_err_f64 / vi_eval_resident_peak_f64 call on this context, from HIP events recorded on the context's stream around them (the preparation kernels are excluded).
+ * vi_eval_resident_err_f64 / vi_eval_resident_gradcov_f64 / vi_eval_grad_cov_f64 (its last chunk) / vi_eval_resident_peak_f64 call on this context, from HIP events recorded on the context's stream around them (the preparation kernels are excluded).
  * The events are recorded only while vi_ctx_set_eval_timing(ctx, 1) is in force (default: off - the pair costs a 0.2 ms call about 7 us);
  * vi_eval_kernel_ms fails with VI_ERR_ARG while it is off or before a call has been timed. */
 int  vi_ctx_set_eval_timing(vi_ctx* ctx, int32_t on);

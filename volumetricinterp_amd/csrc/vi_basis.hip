@@ -2469,6 +2469,148 @@ extern "C" int vi_eval_resident_err_f64(vi_model* m, int64_t Q, int64_t T, const
     return VI_OK;
 }
 
+// Gradient-covariance maps on a resident gradient basis: out[(t*6 + k)*ldo + q] = g_c^T 1/2 (dC_t + dC_t^T) g_d, (c, d) the
+// k-th of (0,0) (1,1) (2,2) (0,1) (0,2) (1,2), g_c = column (c, q) of d_G[(n*3 + c)*Q + q].  K2c (vi_eval_resident.hip) for
+// N <= 144; other orders, and VINTERP_EVAL_RESIDENT=blas: per chunk of points the three components are turned point-major
+// (row d * qc + q of A), then per timestep B = A dC_t^T by the library and the nine row dots M[c][d] = A_c[q] . B_d[q]
+// = g_c^T dC_t g_d, symmetrised as K2c does: 1/2 (M[c][d] + M[d][c]).
+namespace {
+// A[(d*P + q)*N + n] = G[(n*3 + d)*ldg + q]
+__global__ void k_points_major3(int64_t P, int N, const double* __restrict__ G, int64_t ldg, double* __restrict__ A)
+{
+    const int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;     // e = (n * 3 + d) * P + q: the reads along the rows
+    if (e >= 3 * P * N) return;
+    const int64_t nd = e / P, q = e - nd * P;
+    const int64_t n = nd / 3, d = nd - 3 * n;
+    A[(d * P + q) * N + n] = G[nd * ldg + q];
+}
+
+// a wave per point: the nine dots of its three rows of A with its three rows of B, the six entries of the symmetric part
+__global__ void k_rowdot_gradcov(int64_t P, int N, const double* __restrict__ A, const double* __restrict__ B,
+                                 double* __restrict__ out, int64_t ldo)
+{
+    const int64_t p = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (p >= P) return;
+    double M[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+    for (int n = lane; n < N; n += 64) {
+        double a[3], b[3];
+        for (int c = 0; c < 3; ++c) {
+            a[c] = A[(c * P + p) * N + n];
+            b[c] = B[(c * P + p) * N + n];
+        }
+        for (int c = 0; c < 3; ++c)
+            for (int d = 0; d < 3; ++d) M[c][d] = fma(a[c], b[d], M[c][d]);
+    }
+    for (int c = 0; c < 3; ++c)
+        for (int d = 0; d < 3; ++d)
+            for (int o = 32; o > 0; o >>= 1) M[c][d] += __shfl_down(M[c][d], o);
+    if (lane == 0) {
+        out[0 * ldo + p] = M[0][0];
+        out[1 * ldo + p] = M[1][1];
+        out[2 * ldo + p] = M[2][2];
+        out[3 * ldo + p] = 0.5 * (M[0][1] + M[1][0]);
+        out[4 * ldo + p] = 0.5 * (M[0][2] + M[2][0]);
+        out[5 * ldo + p] = 0.5 * (M[1][2] + M[2][1]);
+    }
+}
+
+// points per chunk of the library path: a workspace of at most 512 MB for A and B (77 000 points at N = 144)
+int64_t gradcov_chunk(int N) { return std::max<int64_t>(1, ((int64_t)1 << 25) / (3 * (int64_t)N)); }
+
+// The maps of T covariances on the Q points of the gradient basis d_G (N x 3 x Q) into d_out with plane stride ldo.  AB: 6 min(Q, gradcov_chunk(N)) N doubles for the library path, or nullptr: taken from the
+// context workspace when that path runs.
+int eval_resident_gradcov(vi_model* m, int64_t Q, int64_t T, const double* d_G, const double* d_dC, double* d_out, int64_t ldo,
+                          double* AB)
+{
+    vi_ctx* c = m->ctx;
+    const int N = m->N;
+    int handled = 0;
+    int rc = vi_eval_resident_gradcov_mfma(c, N, Q, T, d_G, d_dC, d_out, ldo, &handled);      // K2c
+    if (rc != VI_OK || handled) return rc;
+    int64_t chunk = gradcov_chunk(N);
+    if (chunk > Q) chunk = Q;
+    if (!AB) {
+        void* ws = nullptr;
+        rc = vi_ctx_workspace(c, (size_t)6 * chunk * N * sizeof(double), &ws);
+        if (rc != VI_OK) return rc;
+        AB = (double*)ws;
+    }
+    double* A = AB;
+    double* B = A + 3 * chunk * N;
+    const double one = 1.0, zero = 0.0;
+    for (int64_t q0 = 0; q0 < Q; q0 += chunk) {
+        const int64_t qc = (Q - q0) < chunk ? (Q - q0) : chunk;
+        hipLaunchKernelGGL(k_points_major3, dim3(nblocks(3 * qc * N, 256)), dim3(256), 0, c->stream, qc, N, d_G + q0, Q, A);
+        VI_HIP(hipGetLastError());
+        for (int64_t t = 0; t < T; ++t) {
+            // row-major B (3 qc x N) = A (3 qc x N) dC_t^T, B[d*qc + q][i] = sum_k dC_t[i][k] g_d,k (as in vi_eval_resident_err_f64)
+            VI_ROCBLAS(rocblas_dgemm(c->blas, rocblas_operation_transpose, rocblas_operation_none, N, (rocblas_int)(3 * qc), N, &one,
+                                     d_dC + t * N * N, N, A, N, &zero, B, N));
+            hipLaunchKernelGGL(k_rowdot_gradcov, dim3(nblocks(qc, 4)), dim3(256), 0, c->stream, qc, N, A, B,
+                               d_out + t * 6 * ldo + q0, ldo);
+            VI_HIP(hipGetLastError());
+        }
+    }
+    return VI_OK;
+}
+}  // namespace
+
+extern "C" int vi_eval_resident_gradcov_f64(vi_model* m, int64_t Q, int64_t T, const double* d_G, const double* d_dC,
+                                            double* d_out)
+{
+    VI_REQUIRE(m && d_G && d_dC && d_out, "null argument");
+    VI_REQUIRE(Q >= 0 && T >= 0, "negative size");
+    if (Q == 0 || T == 0) return VI_OK;
+    vi_ctx* c = m->ctx;
+    VI_HIP(hipSetDevice(c->device));
+    EvalTimer timer(c);
+    return eval_resident_gradcov(m, Q, T, d_G, d_dC, d_out, Q, nullptr);
+}
+
+// The gradient covariance of ONE covariance at arbitrary points, d_out[k*Q + q]: in chunks of points the planar gradient basis
+// of the chunk (the launcher of vi_eval_grad_basis_f64: hull mask and frame on the device) goes into the context workspace,
+// then K2c or the library path with T = 1 writes the chunk's six planes at their place in the (6, Q) result.
+// VINTERP_GRADCOV_CHUNK: points per chunk (tests: several chunks at a small Q).
+extern "C" int vi_eval_grad_cov_f64(vi_model* m, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt,
+                                    const double* d_dC, const double* d_hull_eq, int32_t F, double hull_tol, int32_t frame,
+                                    double* d_out)
+{
+    VI_REQUIRE(m && d_lat && d_lon && d_alt && d_dC && d_out, "null argument");
+    VI_REQUIRE(Q >= 0 && F >= 0, "negative size");
+    VI_REQUIRE(F == 0 || d_hull_eq, "hull facet count given without facet equations");
+    VI_REQUIRE(frame == VI_FRAME_MODEL || frame == VI_FRAME_ENU, "frame must be VI_FRAME_MODEL or VI_FRAME_ENU");
+    int rc = grad_model_check(m, "vi_eval_grad_cov_f64");
+    if (rc != VI_OK || Q == 0) return rc;
+    vi_ctx* c = m->ctx;
+    VI_HIP(hipSetDevice(c->device));
+    const int N = m->N;
+    if (F > 0 && (rc = prepare_call(m, Q, d_lat, d_lon, d_alt, d_hull_eq, F, hull_tol, 0, nullptr)) != VI_OK) return rc;
+    int64_t chunk = gradcov_chunk(N);
+    if (const char* e = getenv("VINTERP_GRADCOV_CHUNK")) { const long long v = atoll(e); if (v >= 1 && v < chunk) chunk = v; }
+    if (chunk > Q) chunk = Q;
+    const bool own = vi_eval_resident_gradcov_shape(N);
+    void* ws = nullptr;
+    rc = vi_ctx_workspace(c, (size_t)(own ? 3 : 9) * chunk * N * sizeof(double), &ws);
+    if (rc != VI_OK) return rc;
+    double* G = (double*)ws;
+    double* AB = own ? nullptr : G + 3 * chunk * N;
+    for (int64_t q0 = 0; q0 < Q; q0 += chunk) {
+        const int64_t qc = (Q - q0) < chunk ? (Q - q0) : chunk;
+        const unsigned char* d_mask = F > 0 ? m->d_mask + q0 : nullptr;
+        rc = frame == VI_FRAME_ENU
+                 ? launch_grad_sph<GRAD_RESIDENT, true>(m, "vi_eval_grad_cov_f64", qc, d_lat + q0, d_lon + q0, d_alt + q0, nullptr,
+                                                        d_mask, G, 1, qc, 3 * qc)
+                 : launch_grad_sph<GRAD_RESIDENT, false>(m, "vi_eval_grad_cov_f64", qc, d_lat + q0, d_lon + q0, d_alt + q0, nullptr,
+                                                         d_mask, G, 1, qc, 3 * qc);
+        if (rc != VI_OK) return rc;
+        EvalTimer timer(c);
+        rc = eval_resident_gradcov(m, qc, 1, G, d_dC, d_out + q0, Q, AB);
+        if (rc != VI_OK) return rc;
+    }
+    return VI_OK;
+}
+
 extern "C" int vi_eval_f64(vi_model* m, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt,
                            int64_t T, const double* d_C, const double* d_hull_eq, int32_t F, double hull_tol,
                            double* d_out)

@@ -864,3 +864,179 @@ int vi_eval_resident_err_mfma(vi_ctx* c, int N, int64_t Q, int64_t T, const doub
     default: return launch_eval_resident_err<9>(c, N, Q, T, d_Y, d_dC, d_out, handled);
     }
 }
+
+// K2c: gradient-covariance maps of many timesteps on the resident GRADIENT basis of the grid (vi_eval_grad_basis_f64,
+// G[(n*3 + c)*Q + q]): the 3 x 3 covariance of the gradient at every point, first-order error propagation of the coefficient
+// covariance through the three gradient components g_0, g_1, g_2 (columns of G),
+//
+//   cov[t][c][d][q] = g_c^T 1/2 (dC[t] + dC[t]^T) g_d,   out[(t*6 + k)*ldo + q], k over (0,0) (1,1) (2,2) (0,1) (0,2) (1,2)
+//
+// K2e gives the diagonal (its square root) of any resident matrix; the cross terms need the three components of a point side
+// by side.  With K2e's S (S_II = dC_II, S_IJ = dC_IJ + dC_JI^T for I < J) and U(c, d) = sum_{I <= J} g_c,I^T S_IJ g_d,J:
+// U(c, d) + U(d, c) = g_c^T dC g_d + g_d^T dC g_c, so cov[c][d] = 1/2 (U(c, d) + U(d, c)) and cov[c][c] = U(c, c), K2e's sum.
+//  * S of the workgroup's timestep in LDS in operand order exactly as in K2e (90 KB at N = 144), staged once per workgroup and
+//    reused for `groups` x 64 points; one workgroup of 4 waves per CU, ONE wave per SIMD: the 3 NB accumulator quads (216
+//    registers at N = 144) and the B registers of two block columns need the whole unified file of a SIMD lane (VGPR + AGPR).
+//  * A wave takes 16 points as three 16-column tiles, tile c = component c of the same 16 points: lane (p = lane & 15,
+//    g = lane >> 4) reads G[16 J + 4 u + g][c][q0 + p], one 8-byte load per component (a row of 16 lanes: 128 contiguous
+//    bytes).  No condition on Q or on the alignment of G.  The rows from N on of the last block column are zero and not loaded.
+//  * Z_I[d] = sum_{J >= I} S_IJ g_d,J with J descending; Z_I[d] is complete right after block column I, whose B registers
+//    hold rows 16 I + 4 u + g of all three components - the rows of Z_I's accumulator in this lane - so the nine dots
+//    M[c][d] += g_c,I^T Z_I[d] are lane-local.  Two cross-lane adds, the symmetrising half-sum, six 8-byte stores per point
+//    (the 16 lanes with g = 0: 128 contiguous bytes of each plane).
+//  * Per k-step the MFMAs run over I and the three tiles: no accumulator is touched again before 3 J + 2 others.
+// Bound: the fp64 matrix peak, 3 N_p (N_p + 16) flop issued per point-timestep (three times K2e's: the least for three
+// vectors) against 8 (3 N / T_concurrent + 6) bytes.
+namespace {
+
+constexpr int COV_WAVES = 4;                              // waves per workgroup: one per SIMD
+constexpr int COV_PTS = COV_WAVES * 16;                   // points per workgroup and group
+
+template <int NB>
+__global__ __launch_bounds__(COV_WAVES * 64) void k_eval_resident_gradcov(int N, int64_t Q, int64_t T, int groups, int64_t npg,
+                                                                          int64_t ldo, const double* __restrict__ G,
+                                                                          const double* __restrict__ dC, double* __restrict__ out)
+{
+    constexpr int NBLK = NB * (NB + 1) / 2;
+    extern __shared__ __align__(16) double shS[];         // [block J (J + 1) / 2 + I][k-step u][lane]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int g = lane >> 4;
+    const int64_t bid = blockIdx.x;
+    const int xcd = (int)(bid & 7);
+    const int64_t r = bid >> 3;
+    const int64_t t = r % T;
+    const int64_t pg = (r / T) * 8 + xcd;
+    if (pg >= npg) return;
+    // ---- S of timestep t in operand order (as K2e): shS[(blk * 4 + u) * 64 + (g * 16 + p)] = S_IJ[16 I + p][16 J + 4 u + g]
+    const double* D = dC + t * N * N;
+    for (int e = tid; e < NBLK * 256; e += COV_WAVES * 64) {
+        const int l = e & 63, u = (e >> 6) & 3, blk = e >> 8;
+        int J = 0;
+        while ((J + 1) * (J + 2) / 2 <= blk) ++J;
+        const int I = blk - J * (J + 1) / 2;
+        const int i = 16 * I + (l & 15), k = 16 * J + 4 * u + (l >> 4);
+        double v = 0.0;
+        if (i < N && k < N) {
+            v = D[(int64_t)i * N + k];
+            if (I != J) v += D[(int64_t)k * N + i];
+        }
+        shS[e] = v;
+    }
+    __syncthreads();
+    double* const ot = out + t * 6 * ldo;
+    for (int grp = 0; grp < groups; ++grp) {
+        const int64_t q = (pg * groups + grp) * COV_PTS + wave * 16 + (lane & 15);         // this lane's point
+        const bool valid = q < Q;
+        if (__ballot(valid) == 0) break;
+        const double* gp = G + (valid ? q : 0) + (int64_t)g * 3 * Q;   // row g, component 0; row 16 J + 4 u + g is a uniform offset away
+        v4f64 Z[NB][3];
+#pragma unroll
+        for (int I = 0; I < NB; ++I) Z[I][0] = Z[I][1] = Z[I][2] = (v4f64){0.0, 0.0, 0.0, 0.0};
+        double y[2][3][4];                                 // B of block column J (y[J & 1][c][u]) and of the next one, in flight
+        auto load = [&](double (&b)[3][4], int J) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const double* src = gp + (int64_t)(16 * J + 4 * u) * 3 * Q;
+                // the last block column: rows from N on are zero padding, never loaded (a loaded infinity times a zero of S
+                // would be NaN)
+                const bool in = J < NB - 1 || 16 * J + 4 * u + g < N;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    double v = 0.0;
+                    if (in) v = src[c * Q];
+                    b[c][u] = v;
+                }
+            }
+        };
+        double M[3][3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) M[c][0] = M[c][1] = M[c][2] = 0.0;
+        load(y[(NB - 1) & 1], NB - 1);
+#pragma unroll
+        for (int J = NB - 1; J >= 0; --J) {
+            if (J > 0) load(y[(J - 1) & 1], J - 1);
+            __builtin_amdgcn_sched_barrier(0);            // the next block column's loads in flight before this one's products
+            const double(&b)[3][4] = y[J & 1];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+#pragma unroll
+                for (int I = 0; I <= J; ++I) {
+                    const double a = shS[((J * (J + 1) / 2 + I) * 4 + u) * 64 + lane];
+                    Z[I][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b[0][u], Z[I][0], 0, 0, 0);
+                    Z[I][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b[1][u], Z[I][1], 0, 0, 0);
+                    Z[I][2] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b[2][u], Z[I][2], 0, 0, 0);
+                }
+                // the LDS reads of one k-step at a time; reading them a k-step ahead measured 0.7 % faster: not worth its code
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            // Z_J[d] is complete; its row g + 4 v is basis row 16 J + 4 v + g, the one b[c][v] holds
+#pragma unroll
+            for (int v = 0; v < 4; ++v)
+#pragma unroll
+                for (int c = 0; c < 3; ++c)
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) M[c][d] = fma(b[c][v], Z[J][d][v], M[c][d]);
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int d = 0; d < 3; ++d) {
+                M[c][d] += __shfl_xor(M[c][d], 16);
+                M[c][d] += __shfl_xor(M[c][d], 32);
+            }
+        if (valid && g == 0) {                              // a negative diagonal entry (indefinite dC) is stored as it is
+            ot[0 * ldo + q] = M[0][0];
+            ot[1 * ldo + q] = M[1][1];
+            ot[2 * ldo + q] = M[2][2];
+            ot[3 * ldo + q] = 0.5 * (M[0][1] + M[1][0]);
+            ot[4 * ldo + q] = 0.5 * (M[0][2] + M[2][0]);
+            ot[5 * ldo + q] = 0.5 * (M[1][2] + M[2][1]);
+        }
+    }
+}
+
+template <int NB>
+int launch_eval_resident_gradcov(vi_ctx* c, int N, int64_t Q, int64_t T, const double* d_G, const double* d_dC, double* d_out,
+                                 int64_t ldo, int* handled)
+{
+    const size_t shm = (size_t)(NB * (NB + 1) / 2) * 4 * 64 * sizeof(double);
+    // points per workgroup: 64 x groups, by the size of Q as in K2e and up to K2e's 2048 - S (up to 166 KB of covariance through
+    // L2, by 4 waves) is staged once per workgroup, against 17 us of matrix-core work per group of 64 points at N = 144, and
+    // no second workgroup fits the CU to hide it: 42.1 ms at 8 groups, 36.8 at 32, 35.9 at 64 (128^3 x 16 timesteps)
+    int groups = (int)((Q >> 14) < 1 ? 1 : ((Q >> 14) > 32 ? 32 : (Q >> 14)));
+    if (const char* e = getenv("VINTERP_K2C_GROUPS")) { const int gr = atoi(e); if (gr >= 1 && gr <= 256) groups = gr; }  // tests, experiments
+    const int64_t npg = (Q + (int64_t)COV_PTS * groups - 1) / ((int64_t)COV_PTS * groups);
+    const int64_t nblk = ((npg + 7) / 8) * 8 * T;
+    if (nblk > 0x7fffffffLL) return VI_OK;
+    VI_HIP(hipFuncSetAttribute((const void*)k_eval_resident_gradcov<NB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+    hipLaunchKernelGGL(k_eval_resident_gradcov<NB>, dim3((unsigned)nblk), dim3(COV_WAVES * 64), shm, c->stream, N, Q, T, groups,
+                       npg, ldo, d_G, d_dC, d_out);
+    VI_HIP(hipGetLastError());
+    *handled = 1;
+    return VI_OK;
+}
+
+}  // namespace
+
+// whether K2c takes gradient bases of N rows at all (what a caller that carves a workspace for the library path asks first)
+bool vi_eval_resident_gradcov_shape(int N) { return use_own_kernel() && N >= 1 && N <= 16 * ERR_NBMAX; }
+
+// out[(t*6 + k)*ldo + q] = g_c^T 1/2 (dC_t + dC_t^T) g_d of the gradient basis d_G[(n*3 + c)*Q + q] by K2c, (c, d) the k-th of
+// (0,0) (1,1) (2,2) (0,1) (0,2) (1,2); *handled = 0 when the shape is not the kernel's (the caller then uses the library): N <= 144.
+int vi_eval_resident_gradcov_mfma(vi_ctx* c, int N, int64_t Q, int64_t T, const double* d_G, const double* d_dC, double* d_out,
+                                  int64_t ldo, int* handled)
+{
+    *handled = 0;
+    if (!vi_eval_resident_gradcov_shape(N)) return VI_OK;
+    switch ((N + 15) / 16) {
+    case 1: return launch_eval_resident_gradcov<1>(c, N, Q, T, d_G, d_dC, d_out, ldo, handled);
+    case 2: return launch_eval_resident_gradcov<2>(c, N, Q, T, d_G, d_dC, d_out, ldo, handled);
+    case 3: return launch_eval_resident_gradcov<3>(c, N, Q, T, d_G, d_dC, d_out, ldo, handled);
+    case 4: return launch_eval_resident_gradcov<4>(c, N, Q, T, d_G, d_dC, d_out, ldo, handled);
+    case 5: return launch_eval_resident_gradcov<5>(c, N, Q, T, d_G, d_dC, d_out, ldo, handled);
+    case 6: return launch_eval_resident_gradcov<6>(c, N, Q, T, d_G, d_dC, d_out, ldo, handled);
+    case 7: return launch_eval_resident_gradcov<7>(c, N, Q, T, d_G, d_dC, d_out, ldo, handled);
+    case 8: return launch_eval_resident_gradcov<8>(c, N, Q, T, d_G, d_dC, d_out, ldo, handled);
+    default: return launch_eval_resident_gradcov<9>(c, N, Q, T, d_G, d_dC, d_out, ldo, handled);
+    }
+}

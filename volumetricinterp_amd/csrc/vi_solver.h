@@ -40,6 +40,9 @@ int vi_eval_sph_split(vi_model* m, int64_t Q, const double* lat, const double* l
 int vi_eval_resident_mfma(vi_ctx* c, int N, int64_t Q, int64_t T, const double* d_Y, const double* d_C, double* d_out, int* handled);
 int vi_eval_resident_err_mfma(vi_ctx* c, int N, int64_t Q, int64_t T, const double* d_Y, const double* d_dC, double* d_out,
                               int* handled);
+bool vi_eval_resident_gradcov_shape(int N);
+int vi_eval_resident_gradcov_mfma(vi_ctx* c, int N, int64_t Q, int64_t T, const double* d_G, const double* d_dC, double* d_out,
+                                  int64_t ldo, int* handled);
 // peak maps and reduced bases of a resident grid seen as (outer, L, inner) (vi_eval_resident.hip)
 bool vi_peak_fused_shape(int N, int64_t outer, int64_t L, int64_t inner);
 size_t vi_peak_fused_work_bytes(int64_t outer, int64_t L, int64_t T);

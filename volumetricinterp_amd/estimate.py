@@ -248,6 +248,20 @@ def _ptr(a):
 GRADIENT_FRAMES = {'model': _lib.VI_FRAME_MODEL, 'enu': _lib.VI_FRAME_ENU}
 PEAK_KINDS = {'max': 0, 'min': 1}                 # vi_eval_resident_peak_f64's kind
 REDUCED_BASES = 8                                  # reduced bases a ResidentGrid keeps (evaluate_integrals), oldest out
+# the six distinct entries (c, d) of a gradient covariance in the packed order of vi_eval_resident_gradcov_f64
+GRADCOV_PAIRS = ((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2))
+
+
+def gradcov_matrix(packed):
+    """The symmetric 3 x 3 matrices of packed gradient covariances: (..., 6, Q-like) - the six entries in the order of
+    GRADCOV_PAIRS on axis -2 - to (...) + (Q-like) + (3, 3), on the host."""
+    packed = np.asarray(packed, dtype=np.float64)
+    if packed.ndim < 2 or packed.shape[-2] != 6:
+        raise ValueError('packed gradient covariances must have shape (..., 6, Q), not %r' % (packed.shape,))
+    cov = np.empty(packed.shape[:-2] + packed.shape[-1:] + (3, 3))
+    for k, (c, d) in enumerate(GRADCOV_PAIRS):
+        cov[..., c, d] = cov[..., d, c] = packed[..., k, :]
+    return cov
 
 
 class Estimate(object):
@@ -377,6 +391,45 @@ class Estimate(object):
         advertises but never computes (estimate.py:139-145).  Same shape as gdlat, NaN outside the hull."""
         C, dC = self.get_C(time)
         return self._at_points('vi_eval_err_f64', dC, gdlat, gdlon, gdalt, (), check_hull)[0].reshape(np.shape(gdlat))
+
+    def gradient_covariance(self, time, gdlat, gdlon, gdalt, check_hull=True, frame='model'):
+        """Covariance of the gradient of the fitted parameter at the points: array of shape gdlat.shape + (3, 3), symmetric,
+        cov[c][d] = g_c^T 1/2 (dC + dC^T) g_d with g_c the gradient basis of component c at the point and dC the coefficient
+        covariance of the record (get_C: with timeinterp the blend of the two neighbours) - first-order error propagation, the
+        ``graderr`` the reference advertises but never computes (estimate.py:125-147).  Components and frame as in gradient;
+        NaN outside the hull.  The standard error of the gradient along a unit vector u is
+        np.sqrt(np.einsum('...i,...ij,...j', u, cov, u)).  One library call (vi_eval_grad_cov_f64): hull test, frame and the
+        form on the device, the (Q, 3, N) gradient basis never leaves it."""
+        packed = self._gradient_covariance(time, gdlat, gdlon, gdalt, check_hull, frame)
+        return gradcov_matrix(packed).reshape(np.shape(gdlat) + (3, 3))
+
+    def gradient_error(self, time, gdlat, gdlon, gdalt, check_hull=True, frame='model'):
+        """Standard errors of the three gradient components at the points, shape gdlat.shape + (3,): the square root of the
+        diagonal of gradient_covariance (NaN where it is negative, as error gives it)."""
+        packed = self._gradient_covariance(time, gdlat, gdlon, gdalt, check_hull, frame)
+        with np.errstate(invalid='ignore'):
+            return np.sqrt(packed[:3].T).reshape(np.shape(gdlat) + (3,))
+
+    def _gradient_covariance(self, time, gdlat, gdlon, gdalt, check_hull, frame):
+        """What gradient_covariance and gradient_error share: the packed (6, Q) result of vi_eval_grad_cov_f64."""
+        if frame not in GRADIENT_FRAMES:
+            raise ValueError("frame must be 'model' or 'enu', not %r" % (frame,))
+        if self.Covariance is None:
+            raise ValueError('this Estimate holds no covariance (Covariance is None): no standard error to evaluate')
+        C, dC = self.get_C(time)
+        lat, lon, alt = ravel_points(gdlat, gdlon, gdalt)
+        Q = lat.size
+        if Q == 0:
+            return np.empty((6, 0))
+        eq, F, tol = self._hull_args(check_hull)
+        with self.model.ctx.scope() as dev:
+            dlat, dlon, dalt = dev.up(lat), dev.up(lon), dev.up(alt)
+            dD = dev.up(np.ascontiguousarray(dC, dtype=np.float64))
+            dO = dev.empty((6, Q))
+            _lib.check(_lib.lib.vi_eval_grad_cov_f64(self.model.handle(), Q, dlat.ptr, dlon.ptr, dalt.ptr, dD.ptr,
+                                                     _ptr(None if eq is None else dev.up(eq)), F, tol, GRADIENT_FRAMES[frame],
+                                                     dO.ptr), 'vi_eval_grad_cov_f64')
+            return dO.download()
 
     def _at_points(self, entry, mat, gdlat, gdlon, gdalt, width, check_hull):
         """What gradient and error share: the library's `entry` (points and the record's matrix `mat` in, (Q,) + width
@@ -681,35 +734,82 @@ class ResidentGrid(object):
         self._need_gradient_basis()
         return self.evaluate_gradients(self._coeffs_at(times)).reshape((len(times), 3) + tuple(self.shape))
 
-    def evaluate_errors(self, dC, out=None):
-        """out[t] = standard error sqrt(a^T dC[t] a) of the fitted parameter on the grid for each covariance dC[t] (as stored
-        in /Coeffs/dC, not assumed symmetric); (T, Q) host array, NaN outside the hull, for a covariance holding a NaN and
-        where the form is negative.  `out` as in evaluate_coeffs."""
+    def _covariances(self, dC):
+        """The covariances of a batch as (T, N, N) float64, checked."""
         dC = np.ascontiguousarray(dC, dtype=np.float64)
         N = self.est.model.nbasis
         if dC.ndim != 3 or dC.shape[1:] != (N, N):
             raise ValueError('covariances must have shape (T, %d, %d)' % (N, N))
-        T = dC.shape[0]
-        out = _check_out(out, (T, self.Q))
-        if T == 0 or self.Q == 0:
-            return out
-        slab = self._slab(T, (self.Q + N * N) * 8)      # the covariances of a slab go up with it, not all T at once
-        h, dY = self.est.model.handle(), self._open(self.dY)
+        return dC
 
-        def call(tc, dD, dO):
-            _lib.check(_lib.lib.vi_eval_resident_err_f64(h, self.Q, tc, dY.ptr, dD, dO.ptr), 'vi_eval_resident_err_f64')
-        return self._run(slab, dC, (out,), call, once=False)[0]
-
-    def error(self, times):
-        """Standard-error maps at the grid for a list of datetimes (the covariance of Estimate.get_C per time, as __call__
-        selects the coefficients): array (len(times),) + grid shape."""
+    def _covariances_at(self, times):
+        """The covariances of Estimate.get_C per time: (len(times), N, N)."""
         if self.est.Covariance is None:
             raise ValueError('this Estimate holds no covariance (Covariance is None): no standard error to evaluate')
         N = self.est.model.nbasis
         dC = np.empty((len(times), N, N))
         for k, t in enumerate(times):
             dC[k] = self.est.get_C(t)[1]
-        return self.evaluate_errors(dC).reshape((len(times),) + tuple(self.shape))
+        return dC
+
+    def _forms(self, entry, dM, cols, dC, out, width):
+        """What the maps of covariances share: the library's `entry` (columns, timesteps, resident matrix, covariances in,
+        (T,) + width out) on the resident matrix dM with `cols` columns, out[t] of covariance dC[t], slab by slab - the
+        covariances of a slab go up with it, not all T at once."""
+        dC = self._covariances(dC)
+        T, N = dC.shape[0], dC.shape[1]
+        out = _check_out(out, (T,) + width)
+        if T == 0 or self.Q == 0:
+            return out
+        slab = self._slab(T, (int(np.prod(width)) + N * N) * 8)
+        h, dM = self.est.model.handle(), self._open(dM)
+
+        def call(tc, dD, dO):
+            _lib.check(getattr(_lib.lib, entry)(h, cols, tc, dM.ptr, dD, dO.ptr), entry)
+        return self._run(slab, dC, (out,), call, once=False)[0]
+
+    def evaluate_errors(self, dC, out=None):
+        """out[t] = standard error sqrt(a^T dC[t] a) of the fitted parameter on the grid for each covariance dC[t] (as stored
+        in /Coeffs/dC, not assumed symmetric); (T, Q) host array, NaN outside the hull, for a covariance holding a NaN and
+        where the form is negative.  `out` as in evaluate_coeffs."""
+        return self._forms('vi_eval_resident_err_f64', self.dY, self.Q, dC, out, (self.Q,))
+
+    def error(self, times):
+        """Standard-error maps at the grid for a list of datetimes (the covariance of Estimate.get_C per time, as __call__
+        selects the coefficients): array (len(times),) + grid shape."""
+        return self.evaluate_errors(self._covariances_at(times)).reshape((len(times),) + tuple(self.shape))
+
+    def evaluate_gradient_errors(self, dC, out=None):
+        """out[t, c] = standard error sqrt(g_c^T dC[t] g_c) of component c of the gradient on the grid for each covariance
+        dC[t]; (T, 3, Q) host array, c in the grid's frame, NaN as in evaluate_errors.  The same form as evaluate_errors on the
+        gradient basis: 3Q columns."""
+        self._need_gradient_basis()
+        return self._forms('vi_eval_resident_err_f64', self.dG, 3 * self.Q, dC, out, (3, self.Q))
+
+    def gradient_error(self, times):
+        """Standard-error maps of the gradient components at the grid for a list of datetimes (covariances as error takes
+        them): array (len(times), 3) + grid shape, components as gradient gives them."""
+        self._need_gradient_basis()
+        return self.evaluate_gradient_errors(self._covariances_at(times)).reshape((len(times), 3) + tuple(self.shape))
+
+    def evaluate_gradient_covariances(self, dC, out=None):
+        """out[t, k] = entry GRADCOV_PAIRS[k] = (c, d) of the covariance of the gradient on the grid for each covariance dC[t],
+        g_c^T 1/2 (dC[t] + dC[t]^T) g_d; (T, 6, Q) host array, packed (gradcov_matrix unpacks it), components in the grid's
+        frame.  All six NaN outside the hull and for a covariance holding a NaN; a negative diagonal entry of an indefinite
+        dC[t] is returned as it is.  `out` as in evaluate_coeffs."""
+        self._need_gradient_basis()
+        return self._forms('vi_eval_resident_gradcov_f64', self.dG, self.Q, dC, out, (6, self.Q))
+
+    def gradient_covariance(self, times):
+        """Covariance maps of the gradient at the grid for a list of datetimes (covariances as error takes them): array
+        (len(times), 3, 3) + grid shape, symmetric in the two component axes, components as gradient gives them.  The standard
+        error of the gradient along a unit vector u is the square root of u^T cov u."""
+        self._need_gradient_basis()
+        packed = self.evaluate_gradient_covariances(self._covariances_at(times))
+        cov = np.empty((len(times), 3, 3, self.Q))
+        for k, (c, d) in enumerate(GRADCOV_PAIRS):
+            cov[:, c, d] = cov[:, d, c] = packed[:, k]
+        return cov.reshape((len(times), 3, 3) + tuple(self.shape))
 
     def _columns(self, axis):
         """The grid as (outer, L, inner) about `axis`: point q = (o * L + l) * inner + i, column m = o * inner + i."""
