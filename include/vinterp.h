@@ -259,6 +259,46 @@ int  vi_eval_grad_basis_f64(vi_model* model, int64_t Q, const double* d_lat, con
  * K2e takes N <= 144 with Q even and d_Y / d_out 16-byte aligned; other shapes, and VINTERP_EVAL_RESIDENT=blas, go through
  * the library's product and a row dot, as vi_eval_err_f64 (tests/test_gpu_resident_error.py). */
 int  vi_eval_resident_err_f64(vi_model* model, int64_t Q, int64_t T, const double* d_Y, const double* d_dC, double* d_out);
+/* Standard errors where every column has its OWN record (the points of a track, rays at their own times): the covariance is
+ * chosen per column of d_Y instead of per map.  d_Y: any N x Q matrix laid out as vi_eval_basis_f64 / vi_eval_slant_basis_f64
+ * make it; d_dC: the R row-major N x N covariances as stored, the full matrix, never assumed symmetric; d_rec[q], d_w select and
+ * blend the records as in vi_eval_track_f64.  With F(r, q) = sum_i sum_k d_Y[i*Q + q] * d_dC[r*N*N + i*N + k] * d_Y[k*Q + q]:
+ *   nearest mode (d_w == NULL):   d_out[q] = sqrt(F(d_rec[q], q))
+ *   interpolation (d_w != NULL):  d_out[q] = sqrt((1 - d_w[q]) * F(d_rec[q], q) + d_w[q] * F(d_rec[q] + 1, q)), computed as
+ *                                 written, no shortcut at d_w = 0 or 1: get_C's blend dC = (1 - T) dC_i + T dC_(i+1)
+ *                                 (estimate.py:578) pushed through the form, which is linear in dC
+ * NaN where the column is a NaN column of d_Y, where d_rec[q] < 0, where a row the point needs is >= R (R = 0: every point),
+ * where a covariance the point needs holds a NaN anywhere, and where the (blended) form is negative, as np.sqrt gives it.  A NaN
+ * covariance reaches only the points that select it; d_dC is never read outside its R matrices.
+ * Kernel K2te (csrc/vi_eval_resident.hip) takes the shapes of K2e - N <= 144, Q even, d_Y / d_out 16-byte aligned: a workgroup
+ * owns 256 consecutive columns, walks the runs of equal d_rec inside them and stages one covariance per run (two in
+ * interpolation mode) for K2e's matrix-core body.  Correct for ANY order of d_rec, but the cost grows with the number of runs:
+ * SORT the columns by d_rec - one staging per record and block.  A point's bits depend on its column of d_Y, its record(s) and
+ * d_w[q], not on Q, the other points or their order; in nearest mode they are the bits vi_eval_resident_err_f64's K2e gives for
+ * that column with that covariance.  Other shapes, N > 144 and VINTERP_EVAL_RESIDENT=blas go run by run through the library's
+ * product and a row dot, as vi_eval_resident_err_f64 does map by map; that route reads d_rec back and waits for the stream.
+ * Otherwise asynchronous on the context's stream; timed for vi_eval_kernel_ms like its siblings
+ * (tests/test_gpu_track_error.py). */
+int  vi_eval_records_err_f64(vi_model* model, int64_t Q, const double* d_Y, const int32_t* d_rec, const double* d_w, int64_t R,
+                             const double* d_dC, double* d_out);
+/* vi_eval_records_err_f64 for points and for rays, the matrix built chunk by chunk in the context workspace (at most 256 MB of
+ * it; VINTERP_TRACK_ERR_CHUNK: a smaller chunk, for tests) and never leaving the device:
+ *   vi_eval_track_err_f64  the standard error of the fitted parameter at points that each carry their own time - the columns of
+ *                          vi_eval_basis_f64 (the same bits, the NaN of a point that fails the hull test included; models and
+ *                          orders as that entry), then the form with the covariance of d_rec[q] (and d_w[q]).  What
+ *                          vi_eval_err_f64 gives record by record.
+ *   vi_eval_slant_err_f64  the standard error sqrt(b^T dC b) of the line integral of vi_eval_slant_f64, in the parameter's unit
+ *                          times metres - the columns of vi_eval_slant_basis_f64 (K1l: the same clip and rule, a NaN column
+ *                          for a ray that misses the hull or has a non-finite end point, N <= 7000).  Arguments as
+ *                          vi_eval_slant_f64 with the covariances d_dC in place of d_C; d_chord (or NULL) as there.
+ * NaN cases beyond the matrix's, and the cost of unsorted d_rec, as vi_eval_records_err_f64.  A chunk border inside a run of
+ * records changes no bits.  Timed for vi_eval_kernel_ms like their siblings. */
+int  vi_eval_track_err_f64(vi_model* model, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt,
+                           const int32_t* d_rec, const double* d_w, int64_t R, const double* d_dC,
+                           const double* d_hull_eq, int32_t F, double hull_tol, double* d_out);
+int  vi_eval_slant_err_f64(vi_model* model, int64_t P, const double* d_a, const double* d_b, const int32_t* d_rec, const double* d_w,
+                           int64_t R, const double* d_dC, const double* d_hull_eq, int32_t F, double hull_tol, int32_t n,
+                           const double* d_x, const double* d_wq, double* d_out, double* d_chord);
 /* The uncertainty of the GRADIENT (the `graderr` the reference's Estimate.__call__ advertises, estimate.py:125-147): the 3 x 3
  * covariance of the gradient at each point from the coefficient covariance, first-order error propagation through the three
  * columns g_0, g_1, g_2 of the gradient basis at the point (components in the frame of the basis),

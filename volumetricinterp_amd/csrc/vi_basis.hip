@@ -2238,6 +2238,14 @@ __global__ void k_mask_basis(int64_t Q, int N, const unsigned char* __restrict__
     const double nan = __builtin_nan("");
     for (int n = 0; n < N; ++n) Y[(int64_t)n * Q + q] = nan;
 }
+
+// the second half of vi_eval_basis_f64: NaN into the columns of the basis matrix d_Y (N x Q) whose mask byte is 0
+int mask_basis(vi_model* m, int64_t Q, const unsigned char* d_mask, double* d_Y)
+{
+    hipLaunchKernelGGL(k_mask_basis, dim3(nblocks(Q, 256)), dim3(256), 0, m->ctx->stream, Q, m->N, d_mask, d_Y);
+    VI_HIP(hipGetLastError());
+    return VI_OK;
+}
 }  // namespace
 
 namespace {
@@ -2297,9 +2305,7 @@ extern "C" int vi_eval_basis_f64(vi_model* m, int64_t Q, const double* d_lat, co
     if (rc != VI_OK || F == 0) return rc;
     rc = prepare_call(m, Q, d_lat, d_lon, d_alt, d_hull_eq, F, hull_tol, 0, nullptr);
     if (rc != VI_OK) return rc;
-    hipLaunchKernelGGL(k_mask_basis, dim3(nblocks(Q, 256)), dim3(256), 0, m->ctx->stream, Q, m->N, m->d_mask, d_Y);
-    VI_HIP(hipGetLastError());
-    return VI_OK;
+    return mask_basis(m, Q, m->d_mask, d_Y);
 }
 
 // The gradient basis of a resident grid: d_G[(n*3 + c)*Q + q], N x 3Q doubles, the matrix vi_eval_resident_f64 multiplies with
@@ -2467,6 +2473,104 @@ extern "C" int vi_eval_resident_err_f64(vi_model* m, int64_t Q, int64_t T, const
         }
     }
     return VI_OK;
+}
+
+// Standard errors with the covariance chosen per column (include/vinterp.h): K2te (vi_eval_resident.hip) for the shapes K2e
+// takes.  Other shapes and orders, and VINTERP_EVAL_RESIDENT=blas, go RUN BY RUN of equal d_rec through the library route of
+// vi_eval_resident_err_f64 - the columns of a chunk point-major once, per run B = A dC_r^T by the library and the row dot, raw,
+// into a work space of 2 forms per point (in blend mode again with dC_(r+1)) - and k_records_finish blends the forms and takes
+// the square root.  This route reads d_rec back to find the runs, so it waits for the stream.
+namespace {
+// the forms themselves: out[p] = A[p] . B[p], k_rowdot_sqrt without the square root
+__global__ void k_rowdot(int64_t P, int N, const double* __restrict__ A, const double* __restrict__ B, double* __restrict__ out)
+{
+    const int64_t p = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (p >= P) return;
+    double acc = 0.0;
+    for (int n = lane; n < N; n += 64) acc = fma(A[p * N + n], B[p * N + n], acc);
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o);
+    if (lane == 0) out[p] = acc;
+}
+
+// out[q] from the forms F0[q] of record rec[q] and - in blend mode, w != nullptr - F1[q] of the next one; NaN without a record
+__global__ void k_records_finish(int64_t P, const int* __restrict__ rec, const double* __restrict__ w, int R,
+                                 const double* __restrict__ F0, const double* __restrict__ F1, double* __restrict__ out)
+{
+    const int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (q >= P) return;
+    const int r = rec[q];
+    if (r < 0 || (int64_t)r + (w ? 1 : 0) >= R)
+        out[q] = __builtin_nan("");
+    else
+        out[q] = w ? vi_err_blend_sqrt(w[q], F0[q], F1[q]) : sqrt(F0[q]);
+}
+
+// points per chunk of the library route, as vi_eval_resident_err_f64 sizes it, and the doubles of its work space: A, B, forms
+int64_t records_err_chunk(int N, int64_t Q) { return std::min(Q, std::max<int64_t>(1, ((int64_t)1 << 25) / N)); }
+size_t records_err_work_doubles(int N, int64_t chunk) { return (size_t)2 * chunk * N + (size_t)2 * chunk; }
+
+// vi_eval_records_err_f64 without its checks and its timer.  work: records_err_work_doubles(N, records_err_chunk(N, Q)) doubles
+// for the library route, or nullptr: taken from the context workspace when that route runs.
+int records_err(vi_model* m, int64_t Q, const double* d_Y, const int32_t* d_rec, const double* d_w, int64_t R,
+                const double* d_dC, double* d_out, double* work)
+{
+    vi_ctx* c = m->ctx;
+    const int N = m->N;
+    int handled = 0;
+    int rc = vi_eval_records_err_mfma(c, N, Q, d_Y, d_rec, d_w, R, d_dC, d_out, &handled);     // K2te
+    if (rc != VI_OK || handled) return rc;
+    std::vector<int32_t> rec((size_t)Q);
+    VI_HIP(hipMemcpyAsync(rec.data(), d_rec, (size_t)Q * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    VI_HIP(hipStreamSynchronize(c->stream));
+    const int64_t chunk = records_err_chunk(N, Q);
+    if (!work) {
+        void* ws = nullptr;
+        rc = vi_ctx_workspace(c, records_err_work_doubles(N, chunk) * sizeof(double), &ws);
+        if (rc != VI_OK) return rc;
+        work = (double*)ws;
+    }
+    double* A = work;
+    double* B = A + chunk * N;
+    double* F[2] = {B + chunk * N, B + chunk * N + chunk};
+    const int npass = d_w ? 2 : 1;
+    const double one = 1.0, zero = 0.0;
+    for (int64_t q0 = 0; q0 < Q; q0 += chunk) {
+        const int64_t qc = (Q - q0) < chunk ? (Q - q0) : chunk;
+        hipLaunchKernelGGL(k_points_major, dim3(nblocks(qc * N, 256)), dim3(256), 0, c->stream, qc, N, d_Y + q0, Q, A);
+        VI_HIP(hipGetLastError());
+        for (int64_t a = 0, b; a < qc; a = b) {              // the run [a, b) of record r
+            const int64_t r = rec[q0 + a];
+            for (b = a + 1; b < qc && rec[q0 + b] == r; ++b) {}
+            if (r < 0 || r + npass - 1 >= R) continue;       // no record: k_records_finish reads no form
+            for (int pass = 0; pass < npass; ++pass) {
+                // row-major B (run x N) = A (run x N) dC^T, as in vi_eval_resident_err_f64
+                VI_ROCBLAS(rocblas_dgemm(c->blas, rocblas_operation_transpose, rocblas_operation_none, N, (rocblas_int)(b - a), N,
+                                         &one, d_dC + (r + pass) * N * N, N, A + a * N, N, &zero, B + a * N, N));
+                hipLaunchKernelGGL(k_rowdot, dim3(nblocks(b - a, 4)), dim3(256), 0, c->stream, b - a, N, A + a * N, B + a * N,
+                                   F[pass] + a);
+                VI_HIP(hipGetLastError());
+            }
+        }
+        hipLaunchKernelGGL(k_records_finish, dim3(nblocks(qc, 256)), dim3(256), 0, c->stream, qc, d_rec + q0,
+                           d_w ? d_w + q0 : nullptr, (int)R, F[0], F[1], d_out + q0);
+        VI_HIP(hipGetLastError());
+    }
+    return VI_OK;
+}
+}  // namespace
+
+extern "C" int vi_eval_records_err_f64(vi_model* m, int64_t Q, const double* d_Y, const int32_t* d_rec, const double* d_w,
+                                       int64_t R, const double* d_dC, double* d_out)
+{
+    VI_REQUIRE(m && d_Y && d_rec && d_out, "null argument");
+    VI_REQUIRE(Q >= 0 && R >= 0, "negative size");
+    VI_REQUIRE(R == 0 || d_dC, "record count given without covariances");
+    VI_REQUIRE(R <= 0x7fffffffLL, "more records than a 32-bit record index");
+    if (Q == 0) return VI_OK;
+    VI_HIP(hipSetDevice(m->ctx->device));
+    EvalTimer timer(m->ctx);
+    return records_err(m, Q, d_Y, d_rec, d_w, R, d_dC, d_out, nullptr);
 }
 
 // Gradient-covariance maps on a resident gradient basis: out[(t*6 + k)*ldo + q] = g_c^T 1/2 (dC_t + dC_t^T) g_d, (c, d) the
@@ -2738,6 +2842,62 @@ extern "C" int vi_eval_track_grad_f64(vi_model* m, int64_t Q, const double* d_la
     });
 }
 
+namespace {
+// Points (rays) per chunk of vi_eval_track_err_f64 and vi_eval_slant_err_f64: the basis of a chunk takes at most 256 MB of the
+// context workspace, half of what the library route of vi_eval_resident_err_f64 asks for its two matrices - with which the
+// library route of a chunk (records_err) fits beside it.  Even, so that every chunk of an even call keeps K2te's shape.
+// VINTERP_TRACK_ERR_CHUNK: a smaller chunk (tests: several chunks at a small Q).
+int64_t track_err_chunk(int N, int64_t Q)
+{
+    int64_t chunk = std::max<int64_t>(2, (((int64_t)1 << 25) / N) & ~(int64_t)1);
+    if (const char* e = getenv("VINTERP_TRACK_ERR_CHUNK")) { const long long v = atoll(e) & ~1LL; if (v >= 2 && v < chunk) chunk = v; }
+    return std::min(chunk, Q);
+}
+
+// The workspace of a chunked call: the basis Y (N x chunk), `extra` doubles for the caller, and - unless every chunk is K2te's -
+// the work space of the library route (else *work = nullptr)
+int track_err_workspace(vi_model* m, int64_t Q, int64_t chunk, const double* d_out, size_t extra, double** Y, double** X,
+                        double** work)
+{
+    const bool own = vi_eval_records_err_shape(m->N, Q, nullptr, d_out);      // (chunks are even, Y is the workspace's)
+    return ws_carve(m->ctx, [&](ws_carver& w) {
+        *Y = w.take<double>((size_t)chunk * m->N, 256);
+        *X = w.take<double>(extra, 256);
+        *work = w.take<double>(own ? 0 : records_err_work_doubles(m->N, chunk), 256);
+        if (own) *work = nullptr;
+    });
+}
+}  // namespace
+
+// Standard errors along a trajectory (include/vinterp.h).  The hull pass of vi_eval_track_f64 for all points, then per chunk:
+// the basis columns of vi_eval_basis_f64 (its builder and its mask kernel: the same bits) into the context workspace, and
+// vi_eval_records_err_f64's routes on them - vi_eval_grad_cov_f64's scheme with the covariance chosen per point.  A chunk
+// border inside a run of records changes no bits: a point's bits do not depend on the other points.
+extern "C" int vi_eval_track_err_f64(vi_model* m, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt,
+                                     const int32_t* d_rec, const double* d_w, int64_t R, const double* d_dC,
+                                     const double* d_hull_eq, int32_t F, double hull_tol, double* d_out)
+{
+    VI_REQUIRE(m && d_lat && d_lon && d_alt && d_rec && d_out, "null argument");
+    VI_REQUIRE(Q >= 0 && R >= 0 && F >= 0, "negative size");
+    VI_REQUIRE(R == 0 || d_dC, "record count given without covariances");
+    VI_REQUIRE(R <= 0x7fffffffLL, "more records than a 32-bit record index");
+    VI_REQUIRE(F == 0 || d_hull_eq, "hull facet count given without facet equations");
+    if (Q == 0) return VI_OK;
+    VI_HIP(hipSetDevice(m->ctx->device));
+    int rc = prepare_call(m, Q, d_lat, d_lon, d_alt, d_hull_eq, F, hull_tol, 0, nullptr);
+    if (rc != VI_OK) return rc;
+    const int64_t chunk = track_err_chunk(m->N, Q);
+    double *Y, *none, *work;
+    if ((rc = track_err_workspace(m, Q, chunk, d_out, 0, &Y, &none, &work)) != VI_OK) return rc;
+    EvalTimer timer(m->ctx);
+    return for_chunks(Q, chunk, [&](int64_t q0, int64_t qc) {
+        int rc = vi_basis_f64(m, qc, d_lat + q0, d_lon + q0, d_alt + q0, Y, 1, qc);
+        if (rc == VI_OK && F > 0) rc = mask_basis(m, qc, m->d_mask + q0, Y);
+        if (rc != VI_OK) return rc;
+        return records_err(m, qc, Y, d_rec + q0, d_w ? d_w + q0 : nullptr, R, d_dC, d_out + q0, work);
+    });
+}
+
 // Line integrals along straight rays (include/vinterp.h): K2l.  The coefficient preparation of vi_eval_track_f64 (all R rows
 // prepared once into m->d_coef) and no hull pass - the kernel clips each ray against the caller's facet list itself -, then one
 // launch: k_slant_sph_fast for the orders of vi_eval_f64's fast list, the per-lane kernels for every other order,
@@ -2798,6 +2958,15 @@ int launch_slant_basis(vi_model* m, K kernel, const Dev& dev, int TR, const Slan
     VI_HIP(hipGetLastError());
     return VI_OK;
 }
+
+// K1l on the rays of s (s.out: the matrix, N x s.P): what vi_eval_slant_basis_f64 and vi_eval_slant_err_f64 launch
+int slant_basis(vi_model* m, const char* who, const SlantArgs& s)
+{
+    if (m->kind != VI_MODEL_SPHHARMLAG) return launch_slant_basis(m, k_slant_basis_rbf, m->rbf, RAYB_RBF_TR, s);
+    return at_order_cap(m, who, [&](auto lc, auto kc) {
+        return launch_slant_basis(m, k_slant_basis_sph<lc, kc>, m->sph, RayBasisSink<kc>::TR, s);
+    });
+}
 }  // namespace
 
 extern "C" int vi_eval_slant_basis_f64(vi_model* m, int64_t P, const double* d_a, const double* d_b, const double* d_hull_eq,
@@ -2813,8 +2982,46 @@ extern "C" int vi_eval_slant_basis_f64(vi_model* m, int64_t P, const double* d_a
     VI_HIP(hipSetDevice(m->ctx->device));
     const SlantArgs s{P, d_a, d_b, nullptr, nullptr, 0, d_hull_eq, (int)F, hull_tol, (int)n, d_x, d_wq, d_Y, d_chord};
     EvalTimer timer(m->ctx);
-    if (m->kind != VI_MODEL_SPHHARMLAG) return launch_slant_basis(m, k_slant_basis_rbf, m->rbf, RAYB_RBF_TR, s);
-    return at_order_cap(m, "vi_eval_slant_basis_f64", [&](auto lc, auto kc) {
-        return launch_slant_basis(m, k_slant_basis_sph<lc, kc>, m->sph, RayBasisSink<kc>::TR, s);
+    return slant_basis(m, "vi_eval_slant_basis_f64", s);
+}
+
+// Standard errors of line integrals (include/vinterp.h): per chunk of rays K1l's matrix into the context workspace - the same
+// clip, the same rule, a NaN column for a miss - and vi_eval_records_err_f64's routes on it, as vi_eval_track_err_f64 does with
+// the basis of its points.  K1l takes planar end points and gives a planar chord, each with the ray count as its pitch: a chunk
+// that is not the whole call has its end points copied side by side into the workspace and its chord copied out of it.
+extern "C" int vi_eval_slant_err_f64(vi_model* m, int64_t P, const double* d_a, const double* d_b, const int32_t* d_rec,
+                                     const double* d_w, int64_t R, const double* d_dC, const double* d_hull_eq, int32_t F,
+                                     double hull_tol, int32_t n, const double* d_x, const double* d_wq, double* d_out,
+                                     double* d_chord)
+{
+    VI_REQUIRE(m && d_a && d_b && d_rec && d_x && d_wq && d_out, "null argument");
+    VI_REQUIRE(P >= 0 && R >= 0 && F >= 0, "negative size");
+    VI_REQUIRE(n >= 1, "a rule has at least one node");
+    VI_REQUIRE(R == 0 || d_dC, "record count given without covariances");
+    VI_REQUIRE(R <= 0x7fffffffLL, "more records than a 32-bit record index");
+    VI_REQUIRE(F == 0 || d_hull_eq, "hull facet count given without facet equations");
+    if (P == 0) return VI_OK;
+    vi_ctx* c = m->ctx;
+    VI_HIP(hipSetDevice(c->device));
+    const int64_t chunk = track_err_chunk(m->N, P);
+    double *Y, *ends, *work;                              // ends: a (3 x chunk), b (3 x chunk), chord (2 x chunk) of a chunk
+    const int rc = track_err_workspace(m, P, chunk, d_out, chunk < P ? (size_t)8 * chunk : 0, &Y, &ends, &work);
+    if (rc != VI_OK) return rc;
+    const size_t row = sizeof(double);
+    EvalTimer timer(c);
+    return for_chunks(P, chunk, [&](int64_t p0, int64_t pc) -> int {
+        SlantArgs s{pc, d_a, d_b, nullptr, nullptr, 0, d_hull_eq, (int)F, hull_tol, (int)n, d_x, d_wq, Y, d_chord};
+        if (pc < P) {
+            VI_HIP(hipMemcpy2DAsync(ends, pc * row, d_a + p0, P * row, pc * row, 3, hipMemcpyDeviceToDevice, c->stream));
+            VI_HIP(hipMemcpy2DAsync(ends + 3 * pc, pc * row, d_b + p0, P * row, pc * row, 3, hipMemcpyDeviceToDevice, c->stream));
+            s.a = ends;
+            s.b = ends + 3 * pc;
+            s.chord = d_chord ? ends + 6 * pc : nullptr;
+        }
+        int rc = slant_basis(m, "vi_eval_slant_err_f64", s);
+        if (rc != VI_OK) return rc;
+        if (pc < P && d_chord)
+            VI_HIP(hipMemcpy2DAsync(d_chord + p0, P * row, s.chord, pc * row, pc * row, 2, hipMemcpyDeviceToDevice, c->stream));
+        return records_err(m, pc, Y, d_rec + p0, d_w ? d_w + p0 : nullptr, R, d_dC, d_out + p0, work);
     });
 }

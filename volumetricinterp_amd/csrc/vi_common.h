@@ -167,6 +167,11 @@ int with_flag(bool b, F&& f)
     return b ? f(std::true_type{}) : f(std::false_type{});
 }
 
+// The standard error of a point between two records from its two forms f0 = y^T dC_r y, f1 = y^T dC_(r+1) y: get_C's blend
+// of the covariances pushed through the form, as written - a NaN in either form gives NaN at any w, a negative blend NaN as
+// np.sqrt gives it.  One definition for K2te and the library route of vi_eval_records_err_f64.
+__device__ __forceinline__ double vi_err_blend_sqrt(double w, double f0, double f1) { return sqrt((1.0 - w) * f0 + w * f1); }
+
 // The VINTERP_* switches.  A switch is read once per process into a function-local `static const` where it is used: the
 // language initialises such a variable once and thread-safely, and FitEngine calls in from several host threads.
 inline int vi_env_int(const char* name, int dflt)

@@ -733,23 +733,12 @@ constexpr int ERR_WAVES = 8;                              // waves per workgroup
 constexpr int ERR_PTS = ERR_WAVES * 32;                   // points per workgroup and group
 constexpr int ERR_NBMAX = 9;                              // N <= 144
 
+// K2e's staging, shared with K2te: S of the covariance D in operand order,
+// shS[(blk * 4 + u) * 64 + (g * 16 + p)] = S_IJ[16 I + p][16 J + 4 u + g], by the 8 waves of the workgroup
 template <int NB>
-__global__ __launch_bounds__(ERR_WAVES * 64) void k_eval_resident_err(int N, int64_t Q, int64_t T, int groups, int64_t npg,
-                                                                      const double* __restrict__ Y, const double* __restrict__ dC,
-                                                                      double* __restrict__ out)
+__device__ __forceinline__ void err_stage(int N, const double* __restrict__ D, double* shS, int tid)
 {
     constexpr int NBLK = NB * (NB + 1) / 2;
-    extern __shared__ __align__(16) double shS[];         // [block J (J + 1) / 2 + I][k-step u][lane]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int g = lane >> 4;
-    const int64_t bid = blockIdx.x;
-    const int xcd = (int)(bid & 7);
-    const int64_t r = bid >> 3;
-    const int64_t t = r % T;
-    const int64_t pg = (r / T) * 8 + xcd;
-    if (pg >= npg) return;
-    // ---- S of timestep t in operand order: shS[(blk * 4 + u) * 64 + (g * 16 + p)] = S_IJ[16 I + p][16 J + 4 u + g]
-    const double* D = dC + t * N * N;
     for (int e = tid; e < NBLK * 256; e += ERR_WAVES * 64) {
         const int l = e & 63, u = (e >> 6) & 3, blk = e >> 8;
         int J = 0;
@@ -763,60 +752,88 @@ __global__ __launch_bounds__(ERR_WAVES * 64) void k_eval_resident_err(int N, int
         }
         shS[e] = v;
     }
+}
+
+// K2e's per-tile body, shared with K2te: the forms y^T S y of the wave's 32 points with the staged S - acc0, acc1 those of the
+// lane's two points yp[0], yp[1] (columns of Y, row stride Q), complete in every lane after the two cross-lane adds
+template <int NB>
+__device__ __forceinline__ void err_forms(int N, int64_t Q, const double* __restrict__ yp, const double* shS, int lane,
+                                          double& acc0, double& acc1)
+{
+    const int g = lane >> 4;
+    const double* yg = yp + (int64_t)g * Q;             // basis row g; row 16 J + 4 u + g is a uniform offset away
+    v4f64 Z[NB][2];
+#pragma unroll
+    for (int I = 0; I < NB; ++I) Z[I][0] = Z[I][1] = (v4f64){0.0, 0.0, 0.0, 0.0};
+    v2f64 y[2][4];                                     // B of block column J (y[J & 1]) and of the next one, in flight
+    auto load = [&](v2f64 (&b)[4], int J) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const double* src = yg + (int64_t)(16 * J + 4 * u) * Q;
+            if (J < NB - 1) {
+                b[u] = *reinterpret_cast<const v2f64*>(src);
+            } else {                                    // the last block column: rows from N on are zero padding
+                const bool in = 16 * J + 4 * u + g < N;
+                const v2f64 v = *reinterpret_cast<const v2f64*>(in ? src : yp);
+                b[u] = in ? v : (v2f64){0.0, 0.0};
+            }
+        }
+    };
+    acc0 = acc1 = 0.0;
+    load(y[(NB - 1) & 1], NB - 1);
+#pragma unroll
+    for (int J = NB - 1; J >= 0; --J) {
+        if (J > 0) load(y[(J - 1) & 1], J - 1);
+        // scheduling barriers: the next block column's loads and one k-step's LDS reads in flight, not all of them (254 VGPRs
+        // at NB = 9, no scratch)
+        __builtin_amdgcn_sched_barrier(0);
+        const v2f64(&b)[4] = y[J & 1];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+#pragma unroll
+            for (int I = 0; I <= J; ++I) {
+                const double a = shS[((J * (J + 1) / 2 + I) * 4 + u) * 64 + lane];
+                Z[I][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b[u].x, Z[I][0], 0, 0, 0);
+                Z[I][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b[u].y, Z[I][1], 0, 0, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);        // the LDS reads of one k-step at a time (J + 1 register pairs)
+        }
+        // Z_J is complete; its row g + 4 v is basis row 16 J + 4 v + g, the one b[v] holds
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            acc0 = fma(Z[J][0][v], b[v].x, acc0);
+            acc1 = fma(Z[J][1][v], b[v].y, acc1);
+        }
+    }
+    acc0 += __shfl_xor(acc0, 16);
+    acc1 += __shfl_xor(acc1, 16);
+    acc0 += __shfl_xor(acc0, 32);
+    acc1 += __shfl_xor(acc1, 32);
+}
+
+template <int NB>
+__global__ __launch_bounds__(ERR_WAVES * 64) void k_eval_resident_err(int N, int64_t Q, int64_t T, int groups, int64_t npg,
+                                                                      const double* __restrict__ Y, const double* __restrict__ dC,
+                                                                      double* __restrict__ out)
+{
+    extern __shared__ __align__(16) double shS[];         // [block J (J + 1) / 2 + I][k-step u][lane]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int g = lane >> 4;
+    const int64_t bid = blockIdx.x;
+    const int xcd = (int)(bid & 7);
+    const int64_t r = bid >> 3;
+    const int64_t t = r % T;
+    const int64_t pg = (r / T) * 8 + xcd;
+    if (pg >= npg) return;
+    err_stage<NB>(N, dC + t * N * N, shS, tid);
     __syncthreads();
     for (int grp = 0; grp < groups; ++grp) {
         const int64_t qa = (pg * groups + grp) * ERR_PTS + wave * 32 + 2 * (lane & 15);   // this lane's two points
         const bool valid = qa < Q;                                                         // Q even: both or none
         if (__ballot(valid) == 0) break;
         const double* yp = Y + (valid ? qa : 0);
-        const double* yg = yp + (int64_t)g * Q;             // basis row g; row 16 J + 4 u + g is a uniform offset away
-        v4f64 Z[NB][2];
-#pragma unroll
-        for (int I = 0; I < NB; ++I) Z[I][0] = Z[I][1] = (v4f64){0.0, 0.0, 0.0, 0.0};
-        v2f64 y[2][4];                                     // B of block column J (y[J & 1]) and of the next one, in flight
-        auto load = [&](v2f64 (&b)[4], int J) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const double* src = yg + (int64_t)(16 * J + 4 * u) * Q;
-                if (J < NB - 1) {
-                    b[u] = *reinterpret_cast<const v2f64*>(src);
-                } else {                                    // the last block column: rows from N on are zero padding
-                    const bool in = 16 * J + 4 * u + g < N;
-                    const v2f64 v = *reinterpret_cast<const v2f64*>(in ? src : yp);
-                    b[u] = in ? v : (v2f64){0.0, 0.0};
-                }
-            }
-        };
-        double acc0 = 0.0, acc1 = 0.0;
-        load(y[(NB - 1) & 1], NB - 1);
-#pragma unroll
-        for (int J = NB - 1; J >= 0; --J) {
-            if (J > 0) load(y[(J - 1) & 1], J - 1);
-            // scheduling barriers: the next block column's loads and one k-step's LDS reads in flight, not all of them (254 VGPRs
-            // at NB = 9, no scratch)
-            __builtin_amdgcn_sched_barrier(0);
-            const v2f64(&b)[4] = y[J & 1];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-#pragma unroll
-                for (int I = 0; I <= J; ++I) {
-                    const double a = shS[((J * (J + 1) / 2 + I) * 4 + u) * 64 + lane];
-                    Z[I][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b[u].x, Z[I][0], 0, 0, 0);
-                    Z[I][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b[u].y, Z[I][1], 0, 0, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);        // the LDS reads of one k-step at a time (J + 1 register pairs)
-            }
-            // Z_J is complete; its row g + 4 v is basis row 16 J + 4 v + g, the one b[v] holds
-#pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                acc0 = fma(Z[J][0][v], b[v].x, acc0);
-                acc1 = fma(Z[J][1][v], b[v].y, acc1);
-            }
-        }
-        acc0 += __shfl_xor(acc0, 16);
-        acc1 += __shfl_xor(acc1, 16);
-        acc0 += __shfl_xor(acc0, 32);
-        acc1 += __shfl_xor(acc1, 32);
+        double acc0, acc1;
+        err_forms<NB>(N, Q, yp, shS, lane, acc0, acc1);
         if (valid && g == 0)                                // a negative form gives NaN, as np.sqrt does
             *reinterpret_cast<v2f64*>(out + t * Q + qa) = (v2f64){sqrt(acc0), sqrt(acc1)};
     }
@@ -842,7 +859,147 @@ int launch_eval_resident_err(vi_ctx* c, int N, int64_t Q, int64_t T, const doubl
     return VI_OK;
 }
 
+// K2te: K2e with the covariance chosen per COLUMN (vi_eval_records_err_f64: every point of a track, every ray, has its own
+// record), F(r, q) = sum_ik Y[i][q] dC[r][i][k] Y[k][q]:
+//
+//   nearest mode:   out[q] = sqrt(F(rec[q], q))          blend: out[q] = sqrt((1 - w[q]) F(rec[q], q) + w[q] F(rec[q] + 1, q))
+//
+// K2t's rule: correct for any order of rec, the cost grows with the disorder, callers sort.
+//  * A workgroup owns the 256 consecutive columns 256 b ... - 8 waves x 32 points, a lane's two points one 16-byte load, every
+//    column at its natural place as in K2e - and walks the RUNS of equal rec inside them: the block's rec and a bit mask of its
+//    run starts (four ballots) sit in LDS, every wave holds the mask in scalar registers and finds the next run with a
+//    count of trailing zeros - the walk is uniform, costs no vector register and needs no table from the host.
+//  * Per run: S of the run's record is staged as in K2e (err_stage; 90 KB at N = 144: one record fits the LDS, two do not),
+//    the waves whose 32 columns meet the run compute their tile with K2e's body (err_forms; the others skip it, a
+//    wave-uniform branch), and a lane keeps the result only for those of its two columns that lie in the run.  Sorted input
+//    costs one staging per record and block; a tile that two runs share is computed once for each.
+//  * Blend mode: two stagings per run, records r and r + 1; the first form waits in LDS (a lane reads back what it wrote
+//    itself) - no register lives across the second pass.  (1 - w) F0 + w F1 as written: a NaN in either covariance gives NaN
+//    at any w.
+//  * A run without a record (rec < 0, or a row it needs >= R) stages nothing and stores NaN; dC is never read outside its R
+//    matrices.  A NaN anywhere in a staged S reaches every column of the tile, of which only the run's own are kept.
+// A point's bits depend on its column of Y, its record(s) and its weight alone - K2e's order of operations per point (J
+// descending, k-steps ascending, the lane-local fma chain, the two cross-lane adds) - and in nearest mode they are K2e's bits
+// for that column with that covariance.
+template <int NB, bool INTERP>
+__global__ __launch_bounds__(ERR_WAVES * 64) void k_eval_records_err(int N, int64_t Q, const double* __restrict__ Y,
+                                                                     const int* __restrict__ rec, const double* __restrict__ w,
+                                                                     int R, const double* __restrict__ dC,
+                                                                     double* __restrict__ out)
+{
+    constexpr int NBLK = NB * (NB + 1) / 2;
+    extern __shared__ __align__(16) double shS[];         // S as in K2e | ERR_PTS first forms | ERR_PTS records | run starts
+    double* const shF = shS + NBLK * 256;
+    int* const shRec = reinterpret_cast<int*>(shF + ERR_PTS);
+    uint64_t* const shStart = reinterpret_cast<uint64_t*>(shRec + ERR_PTS);
+    const int tid = threadIdx.x;
+    const int64_t q0 = (int64_t)blockIdx.x * ERR_PTS;
+    const int nq = (int)((Q - q0) < ERR_PTS ? (Q - q0) : ERR_PTS);       // the block's columns
+    if (tid < ERR_PTS) {                                  // waves 0 ... 3, a column each: bit c of the mask <=> a run starts at c
+        const int mine = tid < nq ? rec[q0 + tid] : 0;
+        const bool start = tid < nq && (tid == 0 || rec[q0 + tid - 1] != mine);
+        const uint64_t mask = __ballot(start);
+        shRec[tid] = mine;
+        if ((tid & 63) == 0) shStart[tid >> 6] = mask;
+    }
+    __syncthreads();
+    // the walk is scalar: the masks, the run [p, e) and its record r are the same in every lane and held as such
+    uint64_t starts[ERR_PTS / 64];
+#pragma unroll
+    for (int k = 0; k < ERR_PTS / 64; ++k) {
+        const uint64_t v = shStart[k];
+        starts[k] = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)v) |
+                    (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32;
+    }
+    for (int p = 0, e; p < nq; p = e) {
+        const int r = __builtin_amdgcn_readfirstlane(shRec[p]);
+        e = nq;                                           // the next run start after p, or the end of the block
+#pragma unroll
+        for (int k = ERR_PTS / 64 - 1; k >= 0; --k) {
+            const int from = p + 1 - 64 * k;              // the bits of word k from this one on
+            const uint64_t x = from >= 64 ? 0 : from > 0 ? starts[k] & (~(uint64_t)0 << from) : starts[k];
+            if (x) e = 64 * k + __builtin_ctzll(x);
+        }
+        if (r < 0 || (int64_t)r + (INTERP ? 1 : 0) >= R) {               // no record: NaN for the run's columns
+            if (tid >= p && tid < e) out[q0 + tid] = __builtin_nan("");
+            continue;
+        }
+#pragma unroll 1
+        for (int pass = 0; pass <= (INTERP ? 1 : 0); ++pass) {
+            // the lane's view of the run, from an opaque copy of its index: what derives from it is made again for every
+            // staging, not kept in registers over the tiles (K2e's body leaves two free at N = 144)
+            int t = tid;
+            asm volatile("" : "+v"(t));
+            const int lane = t & 63, wave = t >> 6;
+            // its two columns of the block, ca and ca + 1 (Q even: both in the block or none), kept where they lie in the run
+            const int ca = wave * 32 + 2 * (lane & 15);
+            auto keep = [&](int c) { return (lane >> 4) == 0 && c >= p && c < e; };
+            __syncthreads();                              // the tiles of the previous staging are done with S
+            err_stage<NB>(N, dC + (int64_t)(r + pass) * N * N, shS, t);
+            __syncthreads();
+            if (wave * 32 >= e || wave * 32 + 32 <= p) continue;          // the wave's columns do not meet the run
+            double f0, f1;
+            err_forms<NB>(N, Q, Y + (ca < nq ? q0 + ca : 0), shS, lane, f0, f1);
+            if (INTERP && pass == 0) {                    // the first form waits in LDS for the lane that wrote it
+                if (keep(ca)) shF[ca] = f0;
+                if (keep(ca + 1)) shF[ca + 1] = f1;
+            } else if (INTERP) {
+                if (keep(ca)) out[q0 + ca] = vi_err_blend_sqrt(w[q0 + ca], shF[ca], f0);
+                if (keep(ca + 1)) out[q0 + ca + 1] = vi_err_blend_sqrt(w[q0 + ca + 1], shF[ca + 1], f1);
+            } else {                                      // a negative form gives NaN, as np.sqrt does
+                if (keep(ca)) out[q0 + ca] = sqrt(f0);
+                if (keep(ca + 1)) out[q0 + ca + 1] = sqrt(f1);
+            }
+        }
+    }
+}
+
+template <int NB>
+int launch_eval_records_err(vi_ctx* c, int N, int64_t Q, const double* d_Y, const int32_t* d_rec, const double* d_w, int64_t R,
+                            const double* d_dC, double* d_out, int* handled)
+{
+    const size_t shm = ((size_t)(NB * (NB + 1) / 2) * 4 * 64 + ERR_PTS) * sizeof(double) + ERR_PTS * sizeof(int) + ERR_PTS / 8;
+    const int64_t nblk = (Q + ERR_PTS - 1) / ERR_PTS;
+    if (nblk > 0x7fffffffLL) return VI_OK;
+    const int rc = with_flag(d_w != nullptr, [&](auto interp) -> int {
+        VI_HIP(hipFuncSetAttribute((const void*)k_eval_records_err<NB, interp>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)shm));
+        hipLaunchKernelGGL((k_eval_records_err<NB, interp>), dim3((unsigned)nblk), dim3(ERR_WAVES * 64), shm, c->stream, N, Q,
+                           d_Y, d_rec, d_w, (int)R, d_dC, d_out);
+        VI_HIP(hipGetLastError());
+        return VI_OK;
+    });
+    if (rc == VI_OK) *handled = 1;
+    return rc;
+}
+
 }  // namespace
+
+// whether K2te takes this call: K2e's shapes - N <= 144, Q even, Y / out 16-byte aligned - unless VINTERP_EVAL_RESIDENT=blas
+bool vi_eval_records_err_shape(int N, int64_t Q, const double* d_Y, const double* d_out)
+{
+    return use_own_kernel() && N >= 1 && N <= 16 * ERR_NBMAX && (Q & 1) == 0 && (((uintptr_t)d_Y | (uintptr_t)d_out) & 15) == 0;
+}
+
+// out[q] of vi_eval_records_err_f64 by K2te; *handled = 0 when the shape is not the kernel's (the caller then goes run by run
+// through the library)
+int vi_eval_records_err_mfma(vi_ctx* c, int N, int64_t Q, const double* d_Y, const int32_t* d_rec, const double* d_w, int64_t R,
+                             const double* d_dC, double* d_out, int* handled)
+{
+    *handled = 0;
+    if (!vi_eval_records_err_shape(N, Q, d_Y, d_out)) return VI_OK;
+    switch ((N + 15) / 16) {
+    case 1: return launch_eval_records_err<1>(c, N, Q, d_Y, d_rec, d_w, R, d_dC, d_out, handled);
+    case 2: return launch_eval_records_err<2>(c, N, Q, d_Y, d_rec, d_w, R, d_dC, d_out, handled);
+    case 3: return launch_eval_records_err<3>(c, N, Q, d_Y, d_rec, d_w, R, d_dC, d_out, handled);
+    case 4: return launch_eval_records_err<4>(c, N, Q, d_Y, d_rec, d_w, R, d_dC, d_out, handled);
+    case 5: return launch_eval_records_err<5>(c, N, Q, d_Y, d_rec, d_w, R, d_dC, d_out, handled);
+    case 6: return launch_eval_records_err<6>(c, N, Q, d_Y, d_rec, d_w, R, d_dC, d_out, handled);
+    case 7: return launch_eval_records_err<7>(c, N, Q, d_Y, d_rec, d_w, R, d_dC, d_out, handled);
+    case 8: return launch_eval_records_err<8>(c, N, Q, d_Y, d_rec, d_w, R, d_dC, d_out, handled);
+    default: return launch_eval_records_err<9>(c, N, Q, d_Y, d_rec, d_w, R, d_dC, d_out, handled);
+    }
+}
 
 // out[t*Q + q] = sqrt(sum_ik Y[i*Q + q] dC[t*N*N + i*N + k] Y[k*Q + q]) by K2e; *handled = 0 when the shape is not the kernel's
 // (the caller then uses the library): N <= 144, Q even and Y / out 16-byte aligned (the 16-byte pieces of two points).

@@ -150,6 +150,24 @@ def select_records(time, t0, timetol=60., timeinterp=False, outside='raise'):
     return rec.astype(np.int32).reshape(shape), w
 
 
+def used_records(rec, w, R):
+    """(rows, rec_compact): the records a call of track_error / slant_error has to upload, and the (rec, w) of select_records
+    re-indexed into them.  rows: the sorted distinct records below R that the elements need - rec itself, with `w` given rec + 1
+    too.  rec_compact: int32 of the shape of rec, the position of rec in rows, -1 kept as -1; a pair (r, r + 1) stays adjacent,
+    r + 1 being in rows whenever r is and directly after it, and a needed row >= R keeps pointing at a row >= len(rows), which
+    the library answers with NaN as it does in the full stack."""
+    rec = np.asarray(rec)
+    r = rec.ravel().astype(np.int64)
+    ok = r >= 0
+    need = r[ok] if w is None else np.concatenate([r[ok], r[ok] + 1])
+    rows = np.unique(need[need < R])
+    compact = np.full(r.size, -1, dtype=np.int64)
+    pos = np.searchsorted(rows, r[ok])
+    pos[r[ok] >= R] = rows.size
+    compact[ok] = pos
+    return rows, compact.astype(np.int32).reshape(rec.shape)
+
+
 def hull_chords(eq, tol, a, b):
     """(s0, s1), each (P,): the part [s0, s1] of [0, 1] on which the segment a + s (b - a) lies inside the hull of
     hull_equations - inside <=> eq[:, :3] @ x + eq[:, 3] <= tol - for (P, 3) end points in ECEF metres.  The hull is convex, so
@@ -410,12 +428,15 @@ class Estimate(object):
         with np.errstate(invalid='ignore'):
             return np.sqrt(packed[:3].T).reshape(np.shape(gdlat) + (3,))
 
+    def _need_covariance(self):
+        if self.Covariance is None:
+            raise ValueError('this Estimate holds no covariance (Covariance is None): no standard error to evaluate')
+
     def _gradient_covariance(self, time, gdlat, gdlon, gdalt, check_hull, frame):
         """What gradient_covariance and gradient_error share: the packed (6, Q) result of vi_eval_grad_cov_f64."""
         if frame not in GRADIENT_FRAMES:
             raise ValueError("frame must be 'model' or 'enu', not %r" % (frame,))
-        if self.Covariance is None:
-            raise ValueError('this Estimate holds no covariance (Covariance is None): no standard error to evaluate')
+        self._need_covariance()
         C, dC = self.get_C(time)
         lat, lon, alt = ravel_points(gdlat, gdlon, gdalt)
         Q = lat.size
@@ -475,10 +496,23 @@ class Estimate(object):
         return self._along_track('vi_eval_track_grad_f64', (3,), (GRADIENT_FRAMES[frame],), times, gdlat, gdlon, gdalt, check_hull,
                                  outside, out)
 
-    def _along_track(self, entry, width, extra, times, gdlat, gdlon, gdalt, check_hull, outside, out):
-        """What track and track_gradient share: the record (rec, w) of every point's time, the points sorted by record (stable),
-        the library's `entry` - points, the arguments of _upload_records, `extra` arguments in, (Q,) + width out - on device
-        copies, the result back in the caller's order: an array of shape gdlat.shape + width."""
+    def track_error(self, times, gdlat, gdlon, gdalt, check_hull=True, outside='raise', out=None):
+        """Standard errors along a trajectory: element q is what self.error(times[q], gdlat[q], gdlon[q], gdalt[q], check_hull)
+        returns - sqrt(a^T dC a) with the covariance of get_C per point (with timeinterp the blend of the two neighbours'
+        covariances), NaN outside the hull, where a covariance the point needs holds a NaN and where the form is negative - in
+        ONE library call for all points (vi_eval_track_err_f64, kernel K2te) instead of one error call, and one upload of a
+        covariance, per record.  Only the covariances the points need go to the device (used_records).  times, outside and
+        `out` as in track; same shape as gdlat.  Raises ValueError when the Estimate holds no covariance."""
+        return self._along_track('vi_eval_track_err_f64', (), (), times, gdlat, gdlon, gdalt, check_hull, outside, out,
+                                 covariance=True)
+
+    def _along_track(self, entry, width, extra, times, gdlat, gdlon, gdalt, check_hull, outside, out, covariance=False):
+        """What track, track_gradient and track_error share: the record (rec, w) of every point's time, the points sorted by
+        record (stable), the library's `entry` - points, the arguments of _upload_records (`covariance`: of the covariances in
+        place of the coefficients), `extra` arguments in, (Q,) + width out - on device copies, the result back in the caller's
+        order: an array of shape gdlat.shape + width."""
+        if covariance:
+            self._need_covariance()
         lat, lon, alt = ravel_points(gdlat, gdlon, gdalt)
         shape, Q = np.shape(gdlat), lat.size
         t0 = self._times_for(times, shape, 'gdlat')
@@ -489,7 +523,7 @@ class Estimate(object):
         order = np.argsort(rec, kind='stable')          # the kernel's cost grows with the span of records in 64 points
         with self.model.ctx.scope() as dev:
             dlat, dlon, dalt = dev.up(lat[order]), dev.up(lon[order]), dev.up(alt[order])
-            records = self._upload_records(dev, rec[order], None if w is None else w[order], check_hull)
+            records = self._upload_records(dev, rec[order], None if w is None else w[order], check_hull, covariance)
             dO = dev.empty((Q,) + width)
             _lib.check(getattr(_lib.lib, entry)(self.model.handle(), Q, dlat.ptr, dlon.ptr, dalt.ptr, *records, *extra, dO.ptr),
                        entry)
@@ -503,15 +537,21 @@ class Estimate(object):
             raise ValueError('times must be one value or have the shape of ' + what)
         return np.broadcast_to(t0, shape).ravel()
 
-    def _upload_records(self, dev, rec, w, check_hull):
+    def _upload_records(self, dev, rec, w, check_hull, covariance=False):
         """The device half: the run of arguments vi_eval_track_f64 and vi_eval_slant_f64 share - (rec, w or None, R, Coeffs,
-        hull or None, F, tol) - of the (rec, w) of select_records in the caller's order, the device copies in the scope `dev`."""
+        hull or None, F, tol) - of the (rec, w) of select_records in the caller's order, the device copies in the scope `dev`.
+        `covariance`: the run of vi_eval_track_err_f64 and vi_eval_slant_err_f64 - the covariances used_records keeps in place
+        of the coefficients, their number for R and rec re-indexed into them."""
         eq, F, tol = self._hull_args(check_hull)
+        M = self.Coeffs
+        if covariance:
+            rows, rec = used_records(rec, w, self.Covariance.shape[0])
+            M = self.Covariance[rows]
         dr = dev.up(rec, np.int32)
         dw = None if w is None else dev.up(w)
-        dC = dev.up(np.ascontiguousarray(self.Coeffs, dtype=np.float64))
+        dM = dev.up(np.ascontiguousarray(M, dtype=np.float64))
         dh = None if eq is None else dev.up(eq)
-        return dr.ptr, _ptr(dw), self.Coeffs.shape[0], dC.ptr, _ptr(dh), F, tol
+        return dr.ptr, _ptr(dw), M.shape[0], dM.ptr, _ptr(dh), F, tol
 
     def slant(self, times, start, end, nodes=64, rule=None, coords='geodetic', check_hull=True, outside='raise', chord=False,
               out=None):
@@ -537,6 +577,29 @@ class Estimate(object):
         chord=True: returns (value, d0, d1), d0 = s0 |b - a| and d1 = s1 |b - a| the distances from `start` in metres between
         which the ray is inside the hull - geometry only, given for a ray without a record too; NaN for a miss.
         `out`: optional C-contiguous float64 array of the ray shape to write the values into."""
+        return self._along_rays('vi_eval_slant_f64', times, start, end, nodes, rule, coords, check_hull, outside, chord, out)
+
+    def slant_error(self, times, start, end, nodes=64, rule=None, coords='geodetic', check_hull=True, outside='raise',
+                    chord=False, out=None):
+        """Standard errors of the line integrals of slant, every ray at its own time: element p is what
+        resident_rays(ray p).error([times[p]]) gives - sqrt(b^T dC b) with b the ray-integrated basis of the ray (K1l: the
+        clip and the rule of slant) and dC the covariance of get_C for the ray's time (with timeinterp the blend of the two
+        neighbours' covariances), in the parameter's unit times metres - in ONE library call (vi_eval_slant_err_f64, kernels
+        K1l and K2te).  Arguments, broadcasting, `chord` and `out` exactly as in slant; NaN where slant gives NaN - a ray that
+        does not enter the hull, has no record (outside='nan') or a non-finite end point, a NaN in a covariance it needs - and
+        where the form is negative; 0 for a segment of length zero inside the hull.  The rays are sorted by record on the host
+        and only the covariances they need go to the device (used_records); results come back in the caller's order.  Raises
+        ValueError when the Estimate holds no covariance."""
+        return self._along_rays('vi_eval_slant_err_f64', times, start, end, nodes, rule, coords, check_hull, outside, chord, out,
+                                covariance=True)
+
+    def _along_rays(self, entry, times, start, end, nodes, rule, coords, check_hull, outside, chord, out, covariance=False):
+        """What slant and slant_error share: the rays and the rule of slant_rays, the record (rec, w) of every ray's time, the
+        library's `entry` - end points, the arguments of _upload_records, the rule in, values and chords out - on device copies.
+        `covariance`: the records are covariances, and the rays go sorted by record (stable; K2te's cost grows with the runs of
+        records, K2l's does not) and come back in the caller's order."""
+        if covariance:
+            self._need_covariance()
         x, wq, shape, a, b = slant_rays(start, end, nodes, rule, coords)
         t0 = self._times_for(times, shape, 'the rays')
         out = _check_out(out, shape)
@@ -544,18 +607,20 @@ class Estimate(object):
         if P == 0:
             return (out, np.empty(shape), np.empty(shape)) if chord else out
         rec, w = self.select_records(t0, outside)
+        order = np.argsort(rec, kind='stable') if covariance else slice(None)
         with self.model.ctx.scope() as dev:
-            da, db = dev.up(a), dev.up(b)
-            records = self._upload_records(dev, rec, w, check_hull)
+            da, db = dev.up(a[:, order]), dev.up(b[:, order])
+            records = self._upload_records(dev, rec[order], None if w is None else w[order], check_hull, covariance)
             dx, dq = dev.up(x), dev.up(wq)
             dO = dev.empty(P)
             dS = dev.empty((2, P)) if chord else None
-            _lib.check(_lib.lib.vi_eval_slant_f64(self.model.handle(), P, da.ptr, db.ptr, *records, x.size, dx.ptr, dq.ptr, dO.ptr,
-                                                  _ptr(dS)), 'vi_eval_slant_f64')
-            out.reshape(-1)[:] = dO.download()
+            _lib.check(getattr(_lib.lib, entry)(self.model.handle(), P, da.ptr, db.ptr, *records, x.size, dx.ptr, dq.ptr, dO.ptr,
+                                                _ptr(dS)), entry)
+            out.reshape(-1)[order] = dO.download()
             if chord:
                 length = np.linalg.norm(b - a, axis=0)
-                s = dS.download()
+                s = np.empty((2, P))
+                s[:, order] = dS.download()
                 return out, (s[0] * length).reshape(shape), (s[1] * length).reshape(shape)
         return out
 
