@@ -542,6 +542,20 @@ int  vi_eigvals_f64(vi_ctx* ctx, int64_t B, int32_t N, double* d_X, double* d_la
 int  vi_qr_similarity_f64(vi_ctx* ctx, int64_t B, int32_t N, const double* d_X, const double* d_y, double* d_X1,
                           double* d_y1, double* d_Q);
 
+/* Stage-test entry of the forming step of vi_basis_solve_f64 (csrc/vi_walk.hip, or the library chain with
+ * VINTERP_WALK_FORM=blas; the routine vi_basis_solve_f64 itself calls before its eigen-solve).  For B (record, basis,
+ * alpha) triples, with A = AWA[rec[i]], V = V[basis[i]] stored "row k = basis vector k" and D2 = D2[basis[i]]:
+ *   X[i] = f (V A V^T + alpha[i] D2), f the power of two that brings max|X[i]| into [1, 2) (1 for a zero or non-finite
+ *   system), scl[i] = 1 / f, yt[i] = V y[rec[i]].
+ * A system with a NaN or an infinite element (a bad record) comes out as NaN all over the lower block triangle, scl = 1.
+ * Of d_X (B x N x N, row-major) only the lower block triangle is defined: element (row, column) with
+ * column < 16 (row / 16 + 1).  What lies above it may be written or left as it was.  Same argument checks and the same
+ * refusal of an N outside the in-LDS Jacobi range (VI_ERR_UNSUPPORTED, nothing launched) as vi_basis_solve_f64; B = 0
+ * is a no-op. */
+int  vi_walk_form_f64(vi_ctx* ctx, int64_t B, int32_t N, const double* d_AWA, const int32_t* d_rec, const double* d_V,
+                      const double* d_D2, const int32_t* d_basis, const double* d_y, const double* d_alpha, double* d_X,
+                      double* d_scl, double* d_yt);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,8 @@
 """The stage entries of the fit (csrc/vi_fit.hip, csrc/vi_gemm_device.h) at every launch shape, against answers known by
 construction and against error-free references: vi_normal_eq_f64, vi_form_system_f64, vi_chi2_f64, vi_cov_f64,
 vi_warm_solve_f64, vi_warm_prepare_f64 / vi_warm_finish_f64, vi_warm_rebase_f64, vi_warm_chi2_one_f64, vi_gcv_terms_f64.
-(The two entries of the root finder, vi_brent_warm_f64 and vi_brent_host_one_f64, live in tests/test_gpu_brent_geometry.py.)
+(The two entries of the root finder, vi_brent_warm_f64 and vi_brent_host_one_f64, live in tests/test_gpu_brent_geometry.py,
+the forming step of vi_basis_solve_f64, vi_walk_form_f64, in tests/test_gpu_walk_geometry.py.)
 
 The launches are chosen from the sizes alone; the *_geometry functions below restate them:
 

@@ -10,8 +10,8 @@ of two batched rocBLAS products and two element-wise kernels - through vi_basis_
 The switch is read once per process, so the other setting runs in a child process: this file is also that child's script
 (`python test_gpu_walk_rotate.py <what> <out.npz>`).
 
-Forming on its own (X scl against NumPy's V AWA V^T + alpha D2, element by element) is NOT tested here: the kernel is not
-reachable without a new symbol of the C ABI, and none was added."""
+Forming on its own (X scl against V AWA V^T + alpha D2 element by element, at every instantiation of the kernel, through the
+stage-test entry vi_walk_form_f64) is tested in tests/test_gpu_walk_geometry.py."""
 import io
 import os
 import subprocess

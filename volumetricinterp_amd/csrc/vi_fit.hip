@@ -180,9 +180,12 @@ __global__ __launch_bounds__(BS) void k_scale_system(int NN, double* __restrict_
     double f = 1.0;
     if (mx > 0.0 && mx < 1.7e308) {
         (void)frexp(mx, &ex);            // mx = m * 2^ex, m in [0.5, 1)
-        f = ldexp(1.0, 1 - ex);          // mx * f in [1, 2)
+        f = ldexp(1.0, ex > -1022 ? 1 - ex : 1023);     // mx * f in [1, 2); below 2^-1023 the largest power of two, not Inf
     }
-    for (int e = tid; e < NN; e += BS) Xi[e] *= f;
+    // A system with an infinite element (a record with an Inf, an overflow) is useless; it comes out as NaN all over, like a
+    // system with a NaN record, instead of a pattern of Inf and NaN that depends on who formed it.  scl stays 1.
+    const double fx = isinf(mx) ? NAN : f;
+    for (int e = tid; e < NN; e += BS) Xi[e] *= fx;
     if (tid == 0) scl[i] = 1.0 / f;      // exact (power of two)
 }
 
@@ -221,12 +224,13 @@ __global__ __launch_bounds__(BS) void k_form_pair_scaled(int NN, const double* D
     double f = 1.0;
     if (mx > 0.0 && mx < 1.7e308) {
         (void)frexp(mx, &ex);            // mx = m * 2^ex, m in [0.5, 1)
-        f = ldexp(1.0, 1 - ex);          // mx * f in [1, 2)
+        f = ldexp(1.0, ex > -1022 ? 1 - ex : 1023);     // mx * f in [1, 2); below 2^-1023 the largest power of two, not Inf
     }
+    const double fx = isinf(mx) ? NAN : f;       // an infinite element: NaN all over (k_scale_system)
 #pragma unroll
     for (int u = 0; u < EPT; ++u) {
         const int e = tid + u * BS;
-        if (e < NN) X[i * NN + e] = v[u] * f;
+        if (e < NN) X[i * NN + e] = v[u] * fx;
     }
     if (tid == 0) scl[i] = 1.0 / f;      // exact (power of two)
 }
@@ -1148,6 +1152,46 @@ int walk_chunk_cap()
     static const int v = vi_env_int("VINTERP_WALK_CHUNK", 0);
     return v;
 }
+
+// What the library chain keeps in the workspace beside X: T1 = AWA V^T per system and the pointer arrays of the two batched
+// products.  K_walk needs none of it.
+struct walk_form_ws {
+    double* T1 = nullptr;
+    const double **pA = nullptr, **pV = nullptr;
+    double **pT = nullptr, **pD = nullptr;
+    static size_t per_system(bool blas, int NN) { return blas ? (size_t)NN * sizeof(double) + 4 * sizeof(void*) : 0; }
+    void take(ws_carver& w, bool blas, int64_t Bc, int NN)
+    {
+        if (!blas) return;
+        T1 = w.take<double>((size_t)Bc * NN);
+        pA = w.take<const double*>(Bc);
+        pV = w.take<const double*>(Bc);
+        pT = w.take<double*>(Bc);
+        pD = w.take<double*>(Bc);
+    }
+};
+
+// The forming step of one chunk of walk systems, either way: X = f (V AWA V^T + alpha D2), scl = 1 / f, yt = V y for the bc
+// triples at rec, basis, alpha (vi_basis_solve_f64 and its stage-test entry vi_walk_form_f64 both call this).
+int walk_form(vi_ctx* c, bool blas, const walk_form_ws& ws, int64_t bc, int N, const double* d_AWA, const int* rec,
+              const double* d_V, const double* d_D2, const int* basis, const double* d_y, const double* alpha, double* X,
+              double* scl, double* yt)
+{
+    if (!blas) return vi_walk_rotate(c, bc, N, d_AWA, rec, d_V, d_D2, basis, d_y, alpha, X, scl, yt);
+    const int NN = N * N;
+    const double one = 1.0, zero = 0.0;
+    hipLaunchKernelGGL(k_basis_ptrs, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, c->stream, bc, NN, d_AWA, rec, d_V, basis,
+                       ws.T1, X, ws.pA, ws.pV, ws.pT, ws.pD);
+    VI_HIP(hipGetLastError());
+    VI_ROCBLAS(rocblas_dgemm_batched(c->blas, rocblas_operation_none, rocblas_operation_none, N, N, N, &one, ws.pA, N, ws.pV, N,
+                                     &zero, ws.pT, N, (rocblas_int)bc));
+    VI_ROCBLAS(rocblas_dgemm_batched(c->blas, rocblas_operation_transpose, rocblas_operation_none, N, N, N, &one, ws.pV, N,
+                                     (const double* const*)ws.pT, N, &zero, ws.pD, N, (rocblas_int)bc));
+    hipLaunchKernelGGL(k_vt_vec, dim3((unsigned)bc), dim3(256), 0, c->stream, N, d_V, basis, d_y, rec, yt);
+    form_pair_scaled(c, bc, NN, X, d_D2, nullptr, basis, alpha, X, scl);
+    VI_HIP(hipGetLastError());
+    return VI_OK;
+}
 }  // namespace
 
 // The bracket walk in SHARED bases.  The records of one geometry differ in their weights, not in their basis functions
@@ -1175,46 +1219,25 @@ extern "C" int vi_basis_solve_f64(vi_ctx* c, int64_t B, int32_t N, const double*
     const int NN = N * N;
     const bool blas = walk_form_blas();
     const size_t logb = vi_jacobi_log_bytes(N, JACOBI_MAX_SWEEPS);
-    size_t per = logb + sizeof(double) + (size_t)NN * sizeof(double) + (size_t)2 * N * sizeof(double);
-    if (blas) per += (size_t)NN * sizeof(double) + 4 * sizeof(void*);
+    const size_t per = logb + sizeof(double) + (size_t)NN * sizeof(double) + (size_t)2 * N * sizeof(double) +
+                       walk_form_ws::per_system(blas, NN);
     int64_t Bc = chunk_size((size_t)8 << 30, per, B, 256);            // whole rounds of the 256 CUs
     if (walk_chunk_cap() > 0 && Bc > walk_chunk_cap()) Bc = walk_chunk_cap();
     void* log;
-    double *scl, *T1 = nullptr, *X, *yt, *cp;
-    const double **pA = nullptr, **pV = nullptr;
-    double **pT = nullptr, **pD = nullptr;
+    double *scl, *X, *yt, *cp;
+    walk_form_ws fw;
     int rc = ws_carve(c, [&](ws_carver& w) {
         log = w.take<char>((size_t)Bc * logb);
         scl = w.take<double>(Bc);
         X = w.take<double>((size_t)Bc * NN);             // the scaled system (blas: D1 first, scaled in place)
         yt = w.take<double>((size_t)Bc * N);
         cp = w.take<double>((size_t)Bc * N);
-        if (blas) {
-            T1 = w.take<double>((size_t)Bc * NN);
-            pA = w.take<const double*>(Bc);
-            pV = w.take<const double*>(Bc);
-            pT = w.take<double*>(Bc);
-            pD = w.take<double*>(Bc);
-        }
+        fw.take(w, blas, Bc, NN);
     });
     if (rc != VI_OK) return rc;
-    const double one = 1.0, zero = 0.0;
     return for_chunks(B, Bc, [&](int64_t i0, int64_t bc) -> int {
-        if (blas) {
-            hipLaunchKernelGGL(k_basis_ptrs, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, c->stream, bc, NN, d_AWA,
-                               d_rec + i0, d_V, d_basis + i0, T1, X, pA, pV, pT, pD);
-            VI_HIP(hipGetLastError());
-            VI_ROCBLAS(rocblas_dgemm_batched(c->blas, rocblas_operation_none, rocblas_operation_none, N, N, N, &one, pA, N,
-                                             pV, N, &zero, pT, N, (rocblas_int)bc));
-            VI_ROCBLAS(rocblas_dgemm_batched(c->blas, rocblas_operation_transpose, rocblas_operation_none, N, N, N, &one, pV,
-                                             N, (const double* const*)pT, N, &zero, pD, N, (rocblas_int)bc));
-            hipLaunchKernelGGL(k_vt_vec, dim3((unsigned)bc), dim3(256), 0, c->stream, N, d_V, d_basis + i0, d_y, d_rec + i0, yt);
-            form_pair_scaled(c, bc, NN, X, d_D2, nullptr, d_basis + i0, d_alpha + i0, X, scl);
-            VI_HIP(hipGetLastError());
-        } else {
-            const int r = vi_walk_rotate(c, bc, N, d_AWA, d_rec + i0, d_V, d_D2, d_basis + i0, d_y, d_alpha + i0, X, scl, yt);
-            if (r != VI_OK) return r;
-        }
+        const int rf = walk_form(c, blas, fw, bc, N, d_AWA, d_rec + i0, d_V, d_D2, d_basis + i0, d_y, d_alpha + i0, X, scl, yt);
+        if (rf != VI_OK) return rf;
         const int r = vi_jacobi_solve(c, bc, N, X, scl, yt, nullptr, rcond, cp, d_rank ? d_rank + i0 : nullptr, log,
                                       JACOBI_MAX_SWEEPS, d_sweeps ? d_sweeps + i0 : nullptr, nullptr, 0, nullptr,
                                       JACOBI_FLOOR_WARM, 0, walk_tolerance());
@@ -1223,6 +1246,32 @@ extern "C" int vi_basis_solve_f64(vi_ctx* c, int64_t B, int32_t N, const double*
                            d_basis + i0, cp, d_C + i0 * N);
         VI_HIP(hipGetLastError());
         return VI_OK;
+    });
+}
+
+// Stage-test entry: the forming step of vi_basis_solve_f64 on its own (walk_form above, with the setting of
+// VINTERP_WALK_FORM), into the caller's arrays.  Of d_X the lower block triangle is defined (see include/vinterp.h).
+extern "C" int vi_walk_form_f64(vi_ctx* c, int64_t B, int32_t N, const double* d_AWA, const int32_t* d_rec, const double* d_V,
+                                const double* d_D2, const int32_t* d_basis, const double* d_y, const double* d_alpha,
+                                double* d_X, double* d_scl, double* d_yt)
+{
+    VI_REQUIRE(c && d_AWA && d_y && d_rec && d_basis && d_alpha && d_V && d_D2 && d_X && d_scl && d_yt, "null argument");
+    VI_REQUIRE(B >= 0 && N > 0, "bad size");
+    if (B == 0) return VI_OK;
+    if (!vi_jacobi_supported(N)) {
+        vi_set_error("vi_walk_form_f64: N=%d outside the in-LDS Jacobi range", N);
+        return VI_ERR_UNSUPPORTED;
+    }
+    VI_HIP(hipSetDevice(c->device));
+    const int NN = N * N;
+    const bool blas = walk_form_blas();
+    const int64_t Bc = blas ? chunk_size((size_t)8 << 30, walk_form_ws::per_system(blas, NN), B, 256) : B;
+    walk_form_ws fw;
+    int rc = ws_carve(c, [&](ws_carver& w) { fw.take(w, blas, Bc, NN); });
+    if (rc != VI_OK) return rc;
+    return for_chunks(B, Bc, [&](int64_t i0, int64_t bc) -> int {
+        return walk_form(c, blas, fw, bc, N, d_AWA, d_rec + i0, d_V, d_D2, d_basis + i0, d_y, d_alpha + i0,
+                         d_X + i0 * NN, d_scl + i0, d_yt + i0 * N);
     });
 }
 

@@ -164,11 +164,14 @@ __global__ __launch_bounds__(NT * 64) void k_walk_rotate(int N, const double* __
     double f = 1.0;
     if (mx > 0.0 && mx < 1.7e308) {
         (void)frexp(mx, &ex);            // mx = m * 2^ex, m in [0.5, 1)
-        f = ldexp(1.0, 1 - ex);          // mx * f in [1, 2)
+        f = ldexp(1.0, ex > -1022 ? 1 - ex : 1023);     // mx * f in [1, 2); below 2^-1023 the largest power of two, not Inf
     }
     // The second pass, L2-hot, after the barrier above (every wave's stores of X are visible to the workgroup): a wave per
     // row, eight rows' loads in flight together.  Loads are unconditional, to clamped addresses inside the row's written
     // part; only the stores are predicated.
+    // A system with an infinite element comes out as NaN all over (k_scale_system, vi_fit.hip): without this an Inf in A gave
+    // +-Inf in the exact variants and NaN in a padded one whose clamped loads met it.  scl stays 1.
+    const double fx = isinf(mx) ? NAN : f;
     constexpr int RB = 8, CG = (16 * NT + 63) / 64;
     for (int r0 = w; r0 < N; r0 += RB * NT) {
         double xv[RB][CG];
@@ -189,7 +192,7 @@ __global__ __launch_bounds__(NT * 64) void k_walk_rotate(int N, const double* __
 #pragma unroll
             for (int m = 0; m < CG; ++m) {
                 const int col = lane + 64 * m;
-                if (row < N && col < lim) Xi[(int64_t)row * N + col] = xv[q][m] * f;
+                if (row < N && col < lim) Xi[(int64_t)row * N + col] = xv[q][m] * fx;
             }
         }
     }
