@@ -317,6 +317,38 @@ int  vi_eval_slant_err_f64(vi_model* model, int64_t P, const double* d_a, const 
 int  vi_eval_resident_gradcov_f64(vi_model* model, int64_t Q, int64_t T, const double* d_G, const double* d_dC, double* d_out);
 int  vi_eval_grad_cov_f64(vi_model* model, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt,
                           const double* d_dC, const double* d_hull_eq, int32_t F, double hull_tol, int32_t frame, double* d_out);
+/* The gradient covariance where every point has its OWN record (the points of a track): the covariance is chosen per column
+ * triple of d_G instead of per map, as vi_eval_records_err_f64 does for the scalar form.  d_G: any planar N x 3 x Q gradient
+ * basis laid out as vi_eval_grad_basis_f64 makes it; d_dC: the R row-major N x N covariances as stored, never assumed
+ * symmetric; d_rec[q], d_w select and blend the records as in vi_eval_track_f64.  With U(r, q)[k] the k-th packed entry of
+ * g_c^T 1/2 (dC_r + dC_r^T) g_d at point q (order as above), d_out[k*Q + q], (6, Q):
+ *   nearest mode (d_w == NULL):   d_out[k*Q + q] = U(d_rec[q], q)[k]
+ *   interpolation (d_w != NULL):  d_out[k*Q + q] = (1 - d_w[q]) * U(d_rec[q], q)[k] + d_w[q] * U(d_rec[q] + 1, q)[k], computed
+ *                                 as written, no shortcut at d_w = 0 or 1: get_C's blend of the two covariances pushed through
+ *                                 the form, which is linear in dC
+ * All six entries are NaN where the column is a NaN column of d_G, where d_rec[q] < 0, where a row the point needs is >= R
+ * (R = 0: every point) and where a covariance the point needs holds a NaN anywhere; a negative diagonal entry is returned as it
+ * is.  A NaN covariance reaches only the points that select it; d_dC is never read outside its R matrices.
+ * Kernel K2tc (csrc/vi_eval_resident.hip) takes N <= 144, any Q, any alignment: a workgroup owns blocks of 256 consecutive
+ * points, walks the runs of equal d_rec inside them as K2te does and stages one covariance per run (two in interpolation mode)
+ * for K2c's matrix-core body.  Correct for ANY order of d_rec, but the cost grows with the number of runs: SORT the points by
+ * d_rec.  A point's bits depend on its three columns of d_G, its record(s) and d_w[q], not on Q, the other points or their
+ * order; in nearest mode they are the bits vi_eval_resident_gradcov_f64's K2c gives for that point with that covariance.
+ * N > 144 and VINTERP_EVAL_RESIDENT=blas go run by run through the library's product and row dots, as
+ * vi_eval_resident_gradcov_f64 does map by map; that route reads d_rec back and waits for the stream.  Otherwise asynchronous on
+ * the context's stream.
+ *   vi_eval_track_grad_cov_f64  the same at points that each carry their own time: the hull pass once for all points, then chunk
+ *                         by chunk the gradient basis in the context workspace as vi_eval_grad_cov_f64 builds it (the same bits;
+ *                         hull, F, hull_tol and frame as there; at most 256 MB of it, VINTERP_TRACK_GRADCOV_CHUNK: fewer points
+ *                         per chunk, for tests) and the routes above on it.  What vi_eval_grad_cov_f64 gives record by record.
+ *                         A chunk border inside a run of records changes no bits.  Models and orders as
+ *                         vi_eval_grad_basis_f64, others return VI_ERR_UNSUPPORTED.
+ * Both are timed for vi_eval_kernel_ms like their siblings (tests/test_gpu_track_gradcov.py). */
+int  vi_eval_records_gradcov_f64(vi_model* model, int64_t Q, const double* d_G, const int32_t* d_rec, const double* d_w, int64_t R,
+                                 const double* d_dC, double* d_out);
+int  vi_eval_track_grad_cov_f64(vi_model* model, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt,
+                                const int32_t* d_rec, const double* d_w, int64_t R, const double* d_dC,
+                                const double* d_hull_eq, int32_t F, double hull_tol, int32_t frame, double* d_out);
 /* Column maps of many timesteps on the same resident grid, without the volume.  The grid is seen as (outer, L, inner), point
  * q = (o*L + l)*inner + i, column m = o*inner + i: any axis of a C-ordered grid, the last one with inner = 1.  What a user of
  * Estimate.__call__ (estimate.py:110-123) takes from a (lat, lon, alt) volume per column: the peak of the parameter along
@@ -352,7 +384,7 @@ int    vi_reduce_basis_f64(vi_model* model, int64_t outer, int64_t L, int64_t in
  * others return VI_ERR_UNSUPPORTED from vi_eval_f64 while the flag is set. */
 int  vi_model_set_eval_precision(vi_model* model, int32_t chain_f32);
 /* device time (ms) of the evaluation kernel launches of the last vi_eval_f64 / vi_eval_track_f64 / vi_eval_track_grad_f64 / vi_eval_slant_f64 / vi_eval_slant_basis_f64 / vi_eval_resident_f64 /
- * vi_eval_resident_err_f64 / vi_eval_resident_gradcov_f64 / vi_eval_grad_cov_f64 (its last chunk) / vi_eval_resident_peak_f64 call on this context, from HIP events recorded on the context's stream around them (the preparation kernels are excluded).
+ * vi_eval_resident_err_f64 / vi_eval_resident_gradcov_f64 / vi_eval_grad_cov_f64 (its last chunk) / vi_eval_records_gradcov_f64 / vi_eval_track_grad_cov_f64 /vi_eval_resident_peak_f64 call on this context, from HIP events recorded on the context's stream around them (the preparation kernels are excluded).
  * The events are recorded only while vi_ctx_set_eval_timing(ctx, 1) is in force (default: off - the pair costs a 0.2 ms call about 7 us);
  * vi_eval_kernel_ms fails with VI_ERR_ARG while it is off or before a call has been timed. */
 int  vi_ctx_set_eval_timing(vi_ctx* ctx, int32_t on);

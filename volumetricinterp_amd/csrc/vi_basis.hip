@@ -2622,30 +2622,21 @@ __global__ void k_rowdot_gradcov(int64_t P, int N, const double* __restrict__ A,
 // points per chunk of the library path: a workspace of at most 512 MB for A and B (77 000 points at N = 144)
 int64_t gradcov_chunk(int N) { return std::max<int64_t>(1, ((int64_t)1 << 25) / (3 * (int64_t)N)); }
 
-// The maps of T covariances on the Q points of the gradient basis d_G (N x 3 x Q) into d_out with plane stride ldo.  AB: 6 min(Q, gradcov_chunk(N)) N doubles for the library path, or nullptr: taken from the
-// context workspace when that path runs.
-int eval_resident_gradcov(vi_model* m, int64_t Q, int64_t T, const double* d_G, const double* d_dC, double* d_out, int64_t ldo,
-                          double* AB)
+// The library path: the maps of T covariances on Q points of a gradient basis d_G with row stride ldg (Q of its columns) into
+// d_out with plane stride ldo.  AB: 6 min(Q, gradcov_chunk(N)) N doubles.
+int gradcov_library(vi_model* m, int64_t Q, int64_t T, const double* d_G, int64_t ldg, const double* d_dC, double* d_out,
+                    int64_t ldo, double* AB)
 {
     vi_ctx* c = m->ctx;
     const int N = m->N;
-    int handled = 0;
-    int rc = vi_eval_resident_gradcov_mfma(c, N, Q, T, d_G, d_dC, d_out, ldo, &handled);      // K2c
-    if (rc != VI_OK || handled) return rc;
     int64_t chunk = gradcov_chunk(N);
     if (chunk > Q) chunk = Q;
-    if (!AB) {
-        void* ws = nullptr;
-        rc = vi_ctx_workspace(c, (size_t)6 * chunk * N * sizeof(double), &ws);
-        if (rc != VI_OK) return rc;
-        AB = (double*)ws;
-    }
     double* A = AB;
     double* B = A + 3 * chunk * N;
     const double one = 1.0, zero = 0.0;
     for (int64_t q0 = 0; q0 < Q; q0 += chunk) {
         const int64_t qc = (Q - q0) < chunk ? (Q - q0) : chunk;
-        hipLaunchKernelGGL(k_points_major3, dim3(nblocks(3 * qc * N, 256)), dim3(256), 0, c->stream, qc, N, d_G + q0, Q, A);
+        hipLaunchKernelGGL(k_points_major3, dim3(nblocks(3 * qc * N, 256)), dim3(256), 0, c->stream, qc, N, d_G + q0, ldg, A);
         VI_HIP(hipGetLastError());
         for (int64_t t = 0; t < T; ++t) {
             // row-major B (3 qc x N) = A (3 qc x N) dC_t^T, B[d*qc + q][i] = sum_k dC_t[i][k] g_d,k (as in vi_eval_resident_err_f64)
@@ -2658,7 +2649,106 @@ int eval_resident_gradcov(vi_model* m, int64_t Q, int64_t T, const double* d_G, 
     }
     return VI_OK;
 }
+
+// The maps of T covariances on the Q points of the gradient basis d_G (N x 3 x Q) into d_out with plane stride ldo.  AB: 6 min(Q, gradcov_chunk(N)) N doubles for the library path, or nullptr: taken from the
+// context workspace when that path runs.
+int eval_resident_gradcov(vi_model* m, int64_t Q, int64_t T, const double* d_G, const double* d_dC, double* d_out, int64_t ldo,
+                          double* AB)
+{
+    vi_ctx* c = m->ctx;
+    const int N = m->N;
+    int handled = 0;
+    int rc = vi_eval_resident_gradcov_mfma(c, N, Q, T, d_G, d_dC, d_out, ldo, &handled);      // K2c
+    if (rc != VI_OK || handled) return rc;
+    if (!AB) {
+        void* ws = nullptr;
+        rc = vi_ctx_workspace(c, (size_t)6 * std::min(Q, gradcov_chunk(N)) * N * sizeof(double), &ws);
+        if (rc != VI_OK) return rc;
+        AB = (double*)ws;
+    }
+    return gradcov_library(m, Q, T, d_G, Q, d_dC, d_out, ldo, AB);
+}
+
+// Gradient covariances with the covariance chosen per column (include/vinterp.h): K2tc (vi_eval_resident.hip) for N <= 144.
+// Other orders, and VINTERP_EVAL_RESIDENT=blas, go RUN BY RUN of equal d_rec through the library path above with T = 1 - the
+// six entries raw into a work space of two (6, chunk) planes per point (in blend mode again with dC_(r+1)) - and
+// k_records_gradcov_finish blends them and writes the NaN of a missing record, as records_err / k_records_finish do for the
+// scalar case.  This route reads d_rec back to find the runs, so it waits for the stream.
+//
+// out[k*ldo + q] from the entries F0[k*ldf + q] of record rec[q] and - in blend mode, w != nullptr - F1[k*ldf + q] of the next one
+__global__ void k_records_gradcov_finish(int64_t P, const int* __restrict__ rec, const double* __restrict__ w, int R,
+                                         const double* __restrict__ F0, const double* __restrict__ F1, int64_t ldf,
+                                         double* __restrict__ out, int64_t ldo)
+{
+    const int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (q >= P) return;
+    const int r = rec[q];
+    const bool none = r < 0 || (int64_t)r + (w ? 1 : 0) >= R;
+    for (int k = 0; k < 6; ++k) {
+        double v = __builtin_nan("");
+        if (!none) v = w ? vi_err_blend(w[q], F0[k * ldf + q], F1[k * ldf + q]) : F0[k * ldf + q];
+        out[k * ldo + q] = v;
+    }
+}
+
+// the doubles of the work space of the library route for chunks of `chunk` points: A and B of gradcov_library, two planes of
+// six entries per point
+size_t records_gradcov_work_doubles(int N, int64_t chunk) { return (size_t)6 * chunk * N + (size_t)12 * chunk; }
+
+// vi_eval_records_gradcov_f64 without its checks and its timer: the Q points of the gradient basis d_G (N x 3 x Q) into d_out
+// with plane stride ldo.  work: records_gradcov_work_doubles(N, min(Q, gradcov_chunk(N))) doubles for the library route, or
+// nullptr: taken from the context workspace when that route runs.
+int records_gradcov(vi_model* m, int64_t Q, const double* d_G, const int32_t* d_rec, const double* d_w, int64_t R,
+                    const double* d_dC, double* d_out, int64_t ldo, double* work)
+{
+    vi_ctx* c = m->ctx;
+    const int N = m->N;
+    int handled = 0;
+    int rc = vi_eval_records_gradcov_mfma(c, N, Q, d_G, d_rec, d_w, R, d_dC, d_out, ldo, &handled);      // K2tc
+    if (rc != VI_OK || handled) return rc;
+    std::vector<int32_t> rec((size_t)Q);
+    VI_HIP(hipMemcpyAsync(rec.data(), d_rec, (size_t)Q * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    VI_HIP(hipStreamSynchronize(c->stream));
+    const int64_t chunk = std::min(Q, gradcov_chunk(N));
+    if (!work) {
+        void* ws = nullptr;
+        rc = vi_ctx_workspace(c, records_gradcov_work_doubles(N, chunk) * sizeof(double), &ws);
+        if (rc != VI_OK) return rc;
+        work = (double*)ws;
+    }
+    double* AB = work;
+    double* F[2] = {AB + 6 * chunk * N, AB + 6 * chunk * N + 6 * chunk};
+    const int npass = d_w ? 2 : 1;
+    for (int64_t q0 = 0; q0 < Q; q0 += chunk) {
+        const int64_t qc = (Q - q0) < chunk ? (Q - q0) : chunk;
+        for (int64_t a = 0, b; a < qc; a = b) {              // the run [a, b) of record r
+            const int64_t r = rec[q0 + a];
+            for (b = a + 1; b < qc && rec[q0 + b] == r; ++b) {}
+            if (r < 0 || r + npass - 1 >= R) continue;       // no record: k_records_gradcov_finish reads no entry
+            for (int pass = 0; pass < npass; ++pass)
+                if ((rc = gradcov_library(m, b - a, 1, d_G + q0 + a, Q, d_dC + (r + pass) * N * N, F[pass] + a, chunk, AB)) != VI_OK)
+                    return rc;
+        }
+        hipLaunchKernelGGL(k_records_gradcov_finish, dim3(nblocks(qc, 256)), dim3(256), 0, c->stream, qc, d_rec + q0,
+                           d_w ? d_w + q0 : nullptr, (int)R, F[0], F[1], chunk, d_out + q0, ldo);
+        VI_HIP(hipGetLastError());
+    }
+    return VI_OK;
+}
 }  // namespace
+
+extern "C" int vi_eval_records_gradcov_f64(vi_model* m, int64_t Q, const double* d_G, const int32_t* d_rec, const double* d_w,
+                                           int64_t R, const double* d_dC, double* d_out)
+{
+    VI_REQUIRE(m && d_G && d_rec && d_out, "null argument");
+    VI_REQUIRE(Q >= 0 && R >= 0, "negative size");
+    VI_REQUIRE(R == 0 || d_dC, "record count given without covariances");
+    VI_REQUIRE(R <= 0x7fffffffLL, "more records than a 32-bit record index");
+    if (Q == 0) return VI_OK;
+    VI_HIP(hipSetDevice(m->ctx->device));
+    EvalTimer timer(m->ctx);
+    return records_gradcov(m, Q, d_G, d_rec, d_w, R, d_dC, d_out, Q, nullptr);
+}
 
 extern "C" int vi_eval_resident_gradcov_f64(vi_model* m, int64_t Q, int64_t T, const double* d_G, const double* d_dC,
                                             double* d_out)
@@ -2895,6 +2985,50 @@ extern "C" int vi_eval_track_err_f64(vi_model* m, int64_t Q, const double* d_lat
         if (rc == VI_OK && F > 0) rc = mask_basis(m, qc, m->d_mask + q0, Y);
         if (rc != VI_OK) return rc;
         return records_err(m, qc, Y, d_rec + q0, d_w ? d_w + q0 : nullptr, R, d_dC, d_out + q0, work);
+    });
+}
+
+// Gradient covariances along a trajectory (include/vinterp.h).  The hull pass of vi_eval_track_f64 for all points, then per
+// chunk: the planar gradient basis of the chunk into the context workspace by the launcher of vi_eval_grad_basis_f64, as
+// vi_eval_grad_cov_f64 builds it - the same bits per point, the hull's NaN columns and the frame folded in -, and
+// vi_eval_records_gradcov_f64's routes on it.  At most 256 MB of gradient basis per chunk (gradcov_chunk);
+// VINTERP_TRACK_GRADCOV_CHUNK: a smaller chunk (tests: several chunks at a small Q).  A chunk border inside a run of records
+// changes no bits: a point's bits do not depend on the other points.
+extern "C" int vi_eval_track_grad_cov_f64(vi_model* m, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt,
+                                          const int32_t* d_rec, const double* d_w, int64_t R, const double* d_dC,
+                                          const double* d_hull_eq, int32_t F, double hull_tol, int32_t frame, double* d_out)
+{
+    VI_REQUIRE(m && d_lat && d_lon && d_alt && d_rec && d_out, "null argument");
+    VI_REQUIRE(Q >= 0 && R >= 0 && F >= 0, "negative size");
+    VI_REQUIRE(R == 0 || d_dC, "record count given without covariances");
+    VI_REQUIRE(R <= 0x7fffffffLL, "more records than a 32-bit record index");
+    VI_REQUIRE(F == 0 || d_hull_eq, "hull facet count given without facet equations");
+    VI_REQUIRE(frame == VI_FRAME_MODEL || frame == VI_FRAME_ENU, "frame must be VI_FRAME_MODEL or VI_FRAME_ENU");
+    int rc = grad_model_check(m, "vi_eval_track_grad_cov_f64");
+    if (rc != VI_OK || Q == 0) return rc;
+    vi_ctx* c = m->ctx;
+    VI_HIP(hipSetDevice(c->device));
+    const int N = m->N;
+    if (F > 0 && (rc = prepare_call(m, Q, d_lat, d_lon, d_alt, d_hull_eq, F, hull_tol, 0, nullptr)) != VI_OK) return rc;
+    int64_t chunk = gradcov_chunk(N);
+    if (const char* e = getenv("VINTERP_TRACK_GRADCOV_CHUNK")) { const long long v = atoll(e); if (v >= 1 && v < chunk) chunk = v; }
+    if (chunk > Q) chunk = Q;
+    const bool own = vi_eval_resident_gradcov_shape(N);
+    void* ws = nullptr;
+    rc = vi_ctx_workspace(c, ((size_t)3 * chunk * N + (own ? 0 : records_gradcov_work_doubles(N, chunk))) * sizeof(double), &ws);
+    if (rc != VI_OK) return rc;
+    double* G = (double*)ws;
+    double* work = own ? nullptr : G + 3 * chunk * N;
+    EvalTimer timer(c);
+    return for_chunks(Q, chunk, [&](int64_t q0, int64_t qc) -> int {
+        const unsigned char* d_mask = F > 0 ? m->d_mask + q0 : nullptr;
+        int rc = frame == VI_FRAME_ENU
+                     ? launch_grad_sph<GRAD_RESIDENT, true>(m, "vi_eval_track_grad_cov_f64", qc, d_lat + q0, d_lon + q0, d_alt + q0,
+                                                            nullptr, d_mask, G, 1, qc, 3 * qc)
+                     : launch_grad_sph<GRAD_RESIDENT, false>(m, "vi_eval_track_grad_cov_f64", qc, d_lat + q0, d_lon + q0, d_alt + q0,
+                                                             nullptr, d_mask, G, 1, qc, 3 * qc);
+        if (rc != VI_OK) return rc;
+        return records_gradcov(m, qc, G, d_rec + q0, d_w ? d_w + q0 : nullptr, R, d_dC, d_out + q0, Q, work);
     });
 }
 

@@ -170,7 +170,10 @@ int with_flag(bool b, F&& f)
 // The standard error of a point between two records from its two forms f0 = y^T dC_r y, f1 = y^T dC_(r+1) y: get_C's blend
 // of the covariances pushed through the form, as written - a NaN in either form gives NaN at any w, a negative blend NaN as
 // np.sqrt gives it.  One definition for K2te and the library route of vi_eval_records_err_f64.
-__device__ __forceinline__ double vi_err_blend_sqrt(double w, double f0, double f1) { return sqrt((1.0 - w) * f0 + w * f1); }
+__device__ __forceinline__ double vi_err_blend(double w, double f0, double f1) { return (1.0 - w) * f0 + w * f1; }
+__device__ __forceinline__ double vi_err_blend_sqrt(double w, double f0, double f1) { return sqrt(vi_err_blend(w, f0, f1)); }
+// (vi_err_blend alone: an entry of the gradient covariance of a point between two records, K2tc and the library route of
+// vi_eval_records_gradcov_f64 - no root, a negative diagonal entry is returned as it is)
 
 // The VINTERP_* switches.  A switch is read once per process into a function-local `static const` where it is used: the
 // language initialises such a variable once and thread-safely, and FitEngine calls in from several host threads.

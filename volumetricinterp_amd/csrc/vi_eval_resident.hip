@@ -730,16 +730,16 @@ namespace {
 typedef double v2f64 __attribute__((ext_vector_type(2)));
 
 constexpr int ERR_WAVES = 8;                              // waves per workgroup
-constexpr int ERR_PTS = ERR_WAVES * 32;                   // points per workgroup and group
+constexpr int ERR_PTS = ERR_WAVES * 32;                   // points per workgroup and group (= RUN_PTS, the block of K2te's walk)
 constexpr int ERR_NBMAX = 9;                              // N <= 144
 
-// K2e's staging, shared with K2te: S of the covariance D in operand order,
-// shS[(blk * 4 + u) * 64 + (g * 16 + p)] = S_IJ[16 I + p][16 J + 4 u + g], by the 8 waves of the workgroup
-template <int NB>
+// The staging K2e, K2te, K2c and K2tc share: S of the covariance D in operand order,
+// shS[(blk * 4 + u) * 64 + (g * 16 + p)] = S_IJ[16 I + p][16 J + 4 u + g], by the WAVES waves of the workgroup
+template <int NB, int WAVES>
 __device__ __forceinline__ void err_stage(int N, const double* __restrict__ D, double* shS, int tid)
 {
     constexpr int NBLK = NB * (NB + 1) / 2;
-    for (int e = tid; e < NBLK * 256; e += ERR_WAVES * 64) {
+    for (int e = tid; e < NBLK * 256; e += WAVES * 64) {
         const int l = e & 63, u = (e >> 6) & 3, blk = e >> 8;
         int J = 0;
         while ((J + 1) * (J + 2) / 2 <= blk) ++J;
@@ -825,7 +825,7 @@ __global__ __launch_bounds__(ERR_WAVES * 64) void k_eval_resident_err(int N, int
     const int64_t t = r % T;
     const int64_t pg = (r / T) * 8 + xcd;
     if (pg >= npg) return;
-    err_stage<NB>(N, dC + t * N * N, shS, tid);
+    err_stage<NB, ERR_WAVES>(N, dC + t * N * N, shS, tid);
     __syncthreads();
     for (int grp = 0; grp < groups; ++grp) {
         const int64_t qa = (pg * groups + grp) * ERR_PTS + wave * 32 + 2 * (lane & 15);   // this lane's two points
@@ -859,6 +859,46 @@ int launch_eval_resident_err(vi_ctx* c, int N, int64_t Q, int64_t T, const doubl
     return VI_OK;
 }
 
+// The run walk K2te and K2tc share.  A workgroup owns RUN_PTS consecutive columns and walks the RUNS of equal rec inside them:
+// the block's rec and a bit mask of its run starts (four ballots) sit in LDS, every wave holds the mask in scalar registers
+// and finds the next run with a count of trailing zeros - the walk is uniform, costs no vector register and needs no table
+// from the host.
+constexpr int RUN_PTS = 256;
+static_assert(ERR_PTS == RUN_PTS, "K2te's block is the block of the walk");
+
+// by the threads 0 ... RUN_PTS - 1 (whole waves), a column each: bit c of the mask <=> a run starts at column c of the block
+__device__ __forceinline__ void runs_setup(const int* __restrict__ rec, int64_t q0, int nq, int tid, int* shRec, uint64_t* shStart)
+{
+    const int mine = tid < nq ? rec[q0 + tid] : 0;
+    const bool start = tid < nq && (tid == 0 || rec[q0 + tid - 1] != mine);
+    const uint64_t mask = __ballot(start);
+    shRec[tid] = mine;
+    if ((tid & 63) == 0) shStart[tid >> 6] = mask;
+}
+
+__device__ __forceinline__ void runs_masks(const uint64_t* shStart, uint64_t (&starts)[RUN_PTS / 64])
+{
+#pragma unroll
+    for (int k = 0; k < RUN_PTS / 64; ++k) {
+        const uint64_t v = shStart[k];
+        starts[k] = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)v) |
+                    (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32;
+    }
+}
+
+// the next run start after column p, or the end nq of the block
+__device__ __forceinline__ int runs_end(const uint64_t (&starts)[RUN_PTS / 64], int p, int nq)
+{
+    int e = nq;
+#pragma unroll
+    for (int k = RUN_PTS / 64 - 1; k >= 0; --k) {
+        const int from = p + 1 - 64 * k;              // the bits of word k from this one on
+        const uint64_t x = from >= 64 ? 0 : from > 0 ? starts[k] & (~(uint64_t)0 << from) : starts[k];
+        if (x) e = 64 * k + __builtin_ctzll(x);
+    }
+    return e;
+}
+
 // K2te: K2e with the covariance chosen per COLUMN (vi_eval_records_err_f64: every point of a track, every ray, has its own
 // record), F(r, q) = sum_ik Y[i][q] dC[r][i][k] Y[k][q]:
 //
@@ -866,9 +906,8 @@ int launch_eval_resident_err(vi_ctx* c, int N, int64_t Q, int64_t T, const doubl
 //
 // K2t's rule: correct for any order of rec, the cost grows with the disorder, callers sort.
 //  * A workgroup owns the 256 consecutive columns 256 b ... - 8 waves x 32 points, a lane's two points one 16-byte load, every
-//    column at its natural place as in K2e - and walks the RUNS of equal rec inside them: the block's rec and a bit mask of its
-//    run starts (four ballots) sit in LDS, every wave holds the mask in scalar registers and finds the next run with a
-//    count of trailing zeros - the walk is uniform, costs no vector register and needs no table from the host.
+//    column at its natural place as in K2e - and walks the RUNS of equal rec inside them (runs_setup, runs_masks, runs_end
+//    above).
 //  * Per run: S of the run's record is staged as in K2e (err_stage; 90 KB at N = 144: one record fits the LDS, two do not),
 //    the waves whose 32 columns meet the run compute their tile with K2e's body (err_forms; the others skip it, a
 //    wave-uniform branch), and a lane keeps the result only for those of its two columns that lie in the run.  Sorted input
@@ -895,31 +934,14 @@ __global__ __launch_bounds__(ERR_WAVES * 64) void k_eval_records_err(int N, int6
     const int tid = threadIdx.x;
     const int64_t q0 = (int64_t)blockIdx.x * ERR_PTS;
     const int nq = (int)((Q - q0) < ERR_PTS ? (Q - q0) : ERR_PTS);       // the block's columns
-    if (tid < ERR_PTS) {                                  // waves 0 ... 3, a column each: bit c of the mask <=> a run starts at c
-        const int mine = tid < nq ? rec[q0 + tid] : 0;
-        const bool start = tid < nq && (tid == 0 || rec[q0 + tid - 1] != mine);
-        const uint64_t mask = __ballot(start);
-        shRec[tid] = mine;
-        if ((tid & 63) == 0) shStart[tid >> 6] = mask;
-    }
+    if (tid < ERR_PTS) runs_setup(rec, q0, nq, tid, shRec, shStart);     // waves 0 ... 3, a column each
     __syncthreads();
     // the walk is scalar: the masks, the run [p, e) and its record r are the same in every lane and held as such
-    uint64_t starts[ERR_PTS / 64];
-#pragma unroll
-    for (int k = 0; k < ERR_PTS / 64; ++k) {
-        const uint64_t v = shStart[k];
-        starts[k] = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)v) |
-                    (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32;
-    }
+    uint64_t starts[RUN_PTS / 64];
+    runs_masks(shStart, starts);
     for (int p = 0, e; p < nq; p = e) {
         const int r = __builtin_amdgcn_readfirstlane(shRec[p]);
-        e = nq;                                           // the next run start after p, or the end of the block
-#pragma unroll
-        for (int k = ERR_PTS / 64 - 1; k >= 0; --k) {
-            const int from = p + 1 - 64 * k;              // the bits of word k from this one on
-            const uint64_t x = from >= 64 ? 0 : from > 0 ? starts[k] & (~(uint64_t)0 << from) : starts[k];
-            if (x) e = 64 * k + __builtin_ctzll(x);
-        }
+        e = runs_end(starts, p, nq);
         if (r < 0 || (int64_t)r + (INTERP ? 1 : 0) >= R) {               // no record: NaN for the run's columns
             if (tid >= p && tid < e) out[q0 + tid] = __builtin_nan("");
             continue;
@@ -935,7 +957,7 @@ __global__ __launch_bounds__(ERR_WAVES * 64) void k_eval_records_err(int N, int6
             const int ca = wave * 32 + 2 * (lane & 15);
             auto keep = [&](int c) { return (lane >> 4) == 0 && c >= p && c < e; };
             __syncthreads();                              // the tiles of the previous staging are done with S
-            err_stage<NB>(N, dC + (int64_t)(r + pass) * N * N, shS, t);
+            err_stage<NB, ERR_WAVES>(N, dC + (int64_t)(r + pass) * N * N, shS, t);
             __syncthreads();
             if (wave * 32 >= e || wave * 32 + 32 <= p) continue;          // the wave's columns do not meet the run
             double f0, f1;
@@ -1049,12 +1071,87 @@ namespace {
 constexpr int COV_WAVES = 4;                              // waves per workgroup: one per SIMD
 constexpr int COV_PTS = COV_WAVES * 16;                   // points per workgroup and group
 
+// K2c's per-tile body, shared with K2tc: the nine forms M[c][d] = sum_{I <= J} g_c,I^T S_IJ g_d,J of the wave's 16 points with
+// the staged S - gq: row 0, component 0 of the lane's point (G[(n*3 + c)*Q + q]) -, complete in every lane after the two
+// cross-lane adds
+template <int NB>
+__device__ __forceinline__ void cov_forms(int N, int64_t Q, const double* __restrict__ gq, const double* shS, int lane,
+                                          double (&M)[3][3])
+{
+    const int g = lane >> 4;
+    const double* gp = gq + (int64_t)g * 3 * Q;        // row g, component 0; row 16 J + 4 u + g is a uniform offset away
+    v4f64 Z[NB][3];
+#pragma unroll
+    for (int I = 0; I < NB; ++I) Z[I][0] = Z[I][1] = Z[I][2] = (v4f64){0.0, 0.0, 0.0, 0.0};
+    double y[2][3][4];                                 // B of block column J (y[J & 1][c][u]) and of the next one, in flight
+    auto load = [&](double (&b)[3][4], int J) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const double* src = gp + (int64_t)(16 * J + 4 * u) * 3 * Q;
+            // the last block column: rows from N on are zero padding, never loaded (a loaded infinity times a zero of S
+            // would be NaN)
+            const bool in = J < NB - 1 || 16 * J + 4 * u + g < N;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                double v = 0.0;
+                if (in) v = src[c * Q];
+                b[c][u] = v;
+            }
+        }
+    };
+#pragma unroll
+    for (int c = 0; c < 3; ++c) M[c][0] = M[c][1] = M[c][2] = 0.0;
+    load(y[(NB - 1) & 1], NB - 1);
+#pragma unroll
+    for (int J = NB - 1; J >= 0; --J) {
+        if (J > 0) load(y[(J - 1) & 1], J - 1);
+        __builtin_amdgcn_sched_barrier(0);            // the next block column's loads in flight before this one's products
+        const double(&b)[3][4] = y[J & 1];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+#pragma unroll
+            for (int I = 0; I <= J; ++I) {
+                const double a = shS[((J * (J + 1) / 2 + I) * 4 + u) * 64 + lane];
+                Z[I][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b[0][u], Z[I][0], 0, 0, 0);
+                Z[I][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b[1][u], Z[I][1], 0, 0, 0);
+                Z[I][2] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b[2][u], Z[I][2], 0, 0, 0);
+            }
+            // the LDS reads of one k-step at a time; reading them a k-step ahead measured 0.7 % faster: not worth its code
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        // Z_J[d] is complete; its row g + 4 v is basis row 16 J + 4 v + g, the one b[c][v] holds
+#pragma unroll
+        for (int v = 0; v < 4; ++v)
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+#pragma unroll
+                for (int d = 0; d < 3; ++d) M[c][d] = fma(b[c][v], Z[J][d][v], M[c][d]);
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            M[c][d] += __shfl_xor(M[c][d], 16);
+            M[c][d] += __shfl_xor(M[c][d], 32);
+        }
+}
+
+// the six entries of the symmetric part 1/2 (M + M^T), in the order of GRADCOV_PAIRS: (0,0) (1,1) (2,2) (0,1) (0,2) (1,2)
+__device__ __forceinline__ void cov_pack(const double (&M)[3][3], double (&U)[6])
+{
+    U[0] = M[0][0];
+    U[1] = M[1][1];
+    U[2] = M[2][2];
+    U[3] = 0.5 * (M[0][1] + M[1][0]);
+    U[4] = 0.5 * (M[0][2] + M[2][0]);
+    U[5] = 0.5 * (M[1][2] + M[2][1]);
+}
+
 template <int NB>
 __global__ __launch_bounds__(COV_WAVES * 64) void k_eval_resident_gradcov(int N, int64_t Q, int64_t T, int groups, int64_t npg,
                                                                           int64_t ldo, const double* __restrict__ G,
                                                                           const double* __restrict__ dC, double* __restrict__ out)
 {
-    constexpr int NBLK = NB * (NB + 1) / 2;
     extern __shared__ __align__(16) double shS[];         // [block J (J + 1) / 2 + I][k-step u][lane]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 4;
@@ -1064,90 +1161,20 @@ __global__ __launch_bounds__(COV_WAVES * 64) void k_eval_resident_gradcov(int N,
     const int64_t t = r % T;
     const int64_t pg = (r / T) * 8 + xcd;
     if (pg >= npg) return;
-    // ---- S of timestep t in operand order (as K2e): shS[(blk * 4 + u) * 64 + (g * 16 + p)] = S_IJ[16 I + p][16 J + 4 u + g]
-    const double* D = dC + t * N * N;
-    for (int e = tid; e < NBLK * 256; e += COV_WAVES * 64) {
-        const int l = e & 63, u = (e >> 6) & 3, blk = e >> 8;
-        int J = 0;
-        while ((J + 1) * (J + 2) / 2 <= blk) ++J;
-        const int I = blk - J * (J + 1) / 2;
-        const int i = 16 * I + (l & 15), k = 16 * J + 4 * u + (l >> 4);
-        double v = 0.0;
-        if (i < N && k < N) {
-            v = D[(int64_t)i * N + k];
-            if (I != J) v += D[(int64_t)k * N + i];
-        }
-        shS[e] = v;
-    }
+    err_stage<NB, COV_WAVES>(N, dC + t * N * N, shS, tid);   // S of timestep t in operand order, as K2e
     __syncthreads();
     double* const ot = out + t * 6 * ldo;
     for (int grp = 0; grp < groups; ++grp) {
         const int64_t q = (pg * groups + grp) * COV_PTS + wave * 16 + (lane & 15);         // this lane's point
         const bool valid = q < Q;
         if (__ballot(valid) == 0) break;
-        const double* gp = G + (valid ? q : 0) + (int64_t)g * 3 * Q;   // row g, component 0; row 16 J + 4 u + g is a uniform offset away
-        v4f64 Z[NB][3];
-#pragma unroll
-        for (int I = 0; I < NB; ++I) Z[I][0] = Z[I][1] = Z[I][2] = (v4f64){0.0, 0.0, 0.0, 0.0};
-        double y[2][3][4];                                 // B of block column J (y[J & 1][c][u]) and of the next one, in flight
-        auto load = [&](double (&b)[3][4], int J) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const double* src = gp + (int64_t)(16 * J + 4 * u) * 3 * Q;
-                // the last block column: rows from N on are zero padding, never loaded (a loaded infinity times a zero of S
-                // would be NaN)
-                const bool in = J < NB - 1 || 16 * J + 4 * u + g < N;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    double v = 0.0;
-                    if (in) v = src[c * Q];
-                    b[c][u] = v;
-                }
-            }
-        };
         double M[3][3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) M[c][0] = M[c][1] = M[c][2] = 0.0;
-        load(y[(NB - 1) & 1], NB - 1);
-#pragma unroll
-        for (int J = NB - 1; J >= 0; --J) {
-            if (J > 0) load(y[(J - 1) & 1], J - 1);
-            __builtin_amdgcn_sched_barrier(0);            // the next block column's loads in flight before this one's products
-            const double(&b)[3][4] = y[J & 1];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-#pragma unroll
-                for (int I = 0; I <= J; ++I) {
-                    const double a = shS[((J * (J + 1) / 2 + I) * 4 + u) * 64 + lane];
-                    Z[I][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b[0][u], Z[I][0], 0, 0, 0);
-                    Z[I][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b[1][u], Z[I][1], 0, 0, 0);
-                    Z[I][2] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b[2][u], Z[I][2], 0, 0, 0);
-                }
-                // the LDS reads of one k-step at a time; reading them a k-step ahead measured 0.7 % faster: not worth its code
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            // Z_J[d] is complete; its row g + 4 v is basis row 16 J + 4 v + g, the one b[c][v] holds
-#pragma unroll
-            for (int v = 0; v < 4; ++v)
-#pragma unroll
-                for (int c = 0; c < 3; ++c)
-#pragma unroll
-                    for (int d = 0; d < 3; ++d) M[c][d] = fma(b[c][v], Z[J][d][v], M[c][d]);
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-#pragma unroll
-            for (int d = 0; d < 3; ++d) {
-                M[c][d] += __shfl_xor(M[c][d], 16);
-                M[c][d] += __shfl_xor(M[c][d], 32);
-            }
+        cov_forms<NB>(N, Q, G + (valid ? q : 0), shS, lane, M);
         if (valid && g == 0) {                              // a negative diagonal entry (indefinite dC) is stored as it is
-            ot[0 * ldo + q] = M[0][0];
-            ot[1 * ldo + q] = M[1][1];
-            ot[2 * ldo + q] = M[2][2];
-            ot[3 * ldo + q] = 0.5 * (M[0][1] + M[1][0]);
-            ot[4 * ldo + q] = 0.5 * (M[0][2] + M[2][0]);
-            ot[5 * ldo + q] = 0.5 * (M[1][2] + M[2][1]);
+            double U[6];
+            cov_pack(M, U);
+#pragma unroll
+            for (int k = 0; k < 6; ++k) ot[k * ldo + q] = U[k];
         }
     }
 }
@@ -1173,7 +1200,154 @@ int launch_eval_resident_gradcov(vi_ctx* c, int N, int64_t Q, int64_t T, const d
     return VI_OK;
 }
 
+// K2tc: K2c with the covariance chosen per COLUMN (vi_eval_records_gradcov_f64: every point of a track has its own record), as
+// K2te is to K2e.  With U_r(q)[k] the six packed entries of g_c^T 1/2 (dC_r + dC_r^T) g_d at point q:
+//
+//   nearest mode:   out[k*ldo + q] = U_rec[q](q)[k]      blend: out[k*ldo + q] = (1 - w[q]) U_rec[q](q)[k] + w[q] U_(rec[q]+1)(q)[k]
+//
+// K2t's rule: correct for any order of rec, the cost grows with the number of runs, callers sort.
+//  * A workgroup of COV_WAVES waves takes `groups` blocks of RUN_PTS = 256 consecutive points, one after the other; a block is
+//    16 tiles of 16 points, tile t goes to wave t & 3 - a run of 64 columns occupies all four SIMDs - and the runs of equal rec
+//    inside the block are walked as in K2te (runs_setup, runs_masks, runs_end).
+//  * Per run: S of the run's record is staged as in K2c (err_stage), every tile that meets the run is computed by its wave with
+//    K2c's body (cov_forms, cov_pack), and a lane keeps the result only if its point lies in the run.  A tile that two runs
+//    share is computed once for each.  The record whose S sits in LDS is remembered: a run that goes on across a block border
+//    of the same workgroup is not staged again.
+//  * Blend mode: two stagings per run, records r and r + 1; the six values of the first wait in LDS (6 x 256 doubles; a lane
+//    reads back what it wrote itself) - no register lives across the second staging.  The pass whose record is already staged
+//    goes first, so sorted input alternates r, r + 1 | r + 1, r | ... across block borders: the blend takes its two values
+//    by record, not by pass, (1 - w) U_r + w U_(r+1) as written - a NaN in either covariance gives NaN at any w.
+//  * A run without a record (rec < 0, or a row it needs >= R) stages nothing and stores six NaN; dC is never read outside its R
+//    matrices.  A NaN anywhere in a staged S reaches every column of the tile, of which only the run's own are kept.
+// A point's bits depend on its three columns of G, its record(s) and its weight alone, and in nearest mode they are K2c's bits
+// for that point with that covariance.  No condition on Q or on the alignment of G.
+template <int NB, bool INTERP>
+__global__ __launch_bounds__(COV_WAVES * 64) void k_eval_records_gradcov(int N, int64_t Q, int groups, int64_t ldo,
+                                                                         const double* __restrict__ G, const int* __restrict__ rec,
+                                                                         const double* __restrict__ w, int R,
+                                                                         const double* __restrict__ dC, double* __restrict__ out)
+{
+    static_assert(COV_WAVES * 64 == RUN_PTS, "a thread per column of the block");
+    constexpr int NBLK = NB * (NB + 1) / 2;
+    extern __shared__ __align__(16) double shS[];         // S as in K2c | 6 x RUN_PTS first values | RUN_PTS records | run starts
+    double* const shF = shS + NBLK * 256;
+    int* const shRec = reinterpret_cast<int*>(shF + 6 * RUN_PTS);
+    uint64_t* const shStart = reinterpret_cast<uint64_t*>(shRec + RUN_PTS);
+    const int tid = threadIdx.x;
+    int staged = -1;                                      // the record whose S sits in LDS (uniform)
+    for (int grp = 0; grp < groups; ++grp) {
+        const int64_t q0 = ((int64_t)blockIdx.x * groups + grp) * RUN_PTS;
+        if (q0 >= Q) break;
+        const int nq = (int)((Q - q0) < RUN_PTS ? (Q - q0) : RUN_PTS);   // the block's columns
+        if (grp > 0) __syncthreads();                     // the walk of the previous block is done with its records
+        runs_setup(rec, q0, nq, tid, shRec, shStart);
+        __syncthreads();
+        uint64_t starts[RUN_PTS / 64];
+        runs_masks(shStart, starts);
+        for (int p = 0, e; p < nq; p = e) {
+            const int r = __builtin_amdgcn_readfirstlane(shRec[p]);
+            e = runs_end(starts, p, nq);
+            if (r < 0 || (int64_t)r + (INTERP ? 1 : 0) >= R) {           // no record: NaN for the run's columns
+                if (tid >= p && tid < e) {
+#pragma unroll
+                    for (int k = 0; k < 6; ++k) out[k * ldo + q0 + tid] = __builtin_nan("");
+                }
+                continue;
+            }
+            const int first = INTERP && staged == r + 1 ? 1 : 0;         // the pass that finds its S staged goes first
+#pragma unroll 1
+            for (int it = 0; it <= (INTERP ? 1 : 0); ++it) {
+                const int pass = it ^ first;                              // S of record r + pass
+                // the lane's view of the run, from an opaque copy of its index: what derives from it is made again for every
+                // staging, not kept in registers over the tiles
+                int t = tid;
+                asm volatile("" : "+v"(t));
+                const int lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
+                if (staged != r + pass) {
+                    __syncthreads();                      // the tiles of the previous staging are done with S
+                    err_stage<NB, COV_WAVES>(N, dC + (int64_t)(r + pass) * N * N, shS, t);
+                    __syncthreads();
+                    staged = r + pass;
+                }
+#pragma unroll 1
+                for (int tile = (p >> 4) + ((wave - (p >> 4)) & 3); 16 * tile < e; tile += COV_WAVES) {   // this wave's tiles of the run
+                    const int c = 16 * tile + (lane & 15);                // this lane's column of the block
+                    double M[3][3];
+                    cov_forms<NB>(N, Q, G + (c < nq ? q0 + c : 0), shS, lane, M);
+                    const bool keep = (lane >> 4) == 0 && c >= p && c < e;   // the point lies in the run (e <= nq)
+                    if (!keep) continue;                  // (after the cross-lane adds of cov_forms; the tile loop is uniform)
+                    double U[6];
+                    cov_pack(M, U);
+                    if (INTERP && it == 0) {              // the first values wait in LDS for the lane that wrote them
+#pragma unroll
+                        for (int k = 0; k < 6; ++k) shF[k * RUN_PTS + c] = U[k];
+                    } else if (INTERP) {
+                        const double wq = w[q0 + c];
+#pragma unroll
+                        for (int k = 0; k < 6; ++k) {
+                            const double a = shF[k * RUN_PTS + c], b = U[k];
+                            out[k * ldo + q0 + c] = pass == 1 ? vi_err_blend(wq, a, b) : vi_err_blend(wq, b, a);
+                        }
+                    } else {                              // a negative diagonal entry is stored as it is (K2c's rule)
+#pragma unroll
+                        for (int k = 0; k < 6; ++k) out[k * ldo + q0 + c] = U[k];
+                    }
+                }
+            }
+        }
+    }
+}
+
+// blocks of 256 points per workgroup of K2tc: S stays staged across the block borders of a workgroup where the record does not
+// change.  VINTERP_K2TC_GROUPS: tests, experiments.
+int records_gradcov_groups(int64_t Q)
+{
+    int groups = (int)((Q >> 16) < 1 ? 1 : ((Q >> 16) > 8 ? 8 : (Q >> 16)));
+    if (const char* e = getenv("VINTERP_K2TC_GROUPS")) { const int gr = atoi(e); if (gr >= 1 && gr <= 256) groups = gr; }
+    return groups;
+}
+
+template <int NB>
+int launch_eval_records_gradcov(vi_ctx* c, int N, int64_t Q, const double* d_G, const int32_t* d_rec, const double* d_w, int64_t R,
+                                const double* d_dC, double* d_out, int64_t ldo, int* handled)
+{
+    const size_t shm = ((size_t)(NB * (NB + 1) / 2) * 4 * 64 + 6 * RUN_PTS) * sizeof(double) + RUN_PTS * sizeof(int) + RUN_PTS / 8;
+    const int groups = records_gradcov_groups(Q);
+    const int64_t nblk = (Q + (int64_t)RUN_PTS * groups - 1) / ((int64_t)RUN_PTS * groups);
+    if (nblk > 0x7fffffffLL) return VI_OK;
+    const int rc = with_flag(d_w != nullptr, [&](auto interp) -> int {
+        VI_HIP(hipFuncSetAttribute((const void*)k_eval_records_gradcov<NB, interp>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)shm));
+        hipLaunchKernelGGL((k_eval_records_gradcov<NB, interp>), dim3((unsigned)nblk), dim3(COV_WAVES * 64), shm, c->stream, N, Q,
+                           groups, ldo, d_G, d_rec, d_w, (int)R, d_dC, d_out);
+        VI_HIP(hipGetLastError());
+        return VI_OK;
+    });
+    if (rc == VI_OK) *handled = 1;
+    return rc;
+}
+
 }  // namespace
+
+// out[k*ldo + q] of vi_eval_records_gradcov_f64 by K2tc; *handled = 0 when the shape is not the kernel's - N > 144,
+// VINTERP_EVAL_RESIDENT=blas - (the caller then goes run by run through the library)
+int vi_eval_records_gradcov_mfma(vi_ctx* c, int N, int64_t Q, const double* d_G, const int32_t* d_rec, const double* d_w, int64_t R,
+                                 const double* d_dC, double* d_out, int64_t ldo, int* handled)
+{
+    *handled = 0;
+    if (!vi_eval_resident_gradcov_shape(N)) return VI_OK;
+    switch ((N + 15) / 16) {
+    case 1: return launch_eval_records_gradcov<1>(c, N, Q, d_G, d_rec, d_w, R, d_dC, d_out, ldo, handled);
+    case 2: return launch_eval_records_gradcov<2>(c, N, Q, d_G, d_rec, d_w, R, d_dC, d_out, ldo, handled);
+    case 3: return launch_eval_records_gradcov<3>(c, N, Q, d_G, d_rec, d_w, R, d_dC, d_out, ldo, handled);
+    case 4: return launch_eval_records_gradcov<4>(c, N, Q, d_G, d_rec, d_w, R, d_dC, d_out, ldo, handled);
+    case 5: return launch_eval_records_gradcov<5>(c, N, Q, d_G, d_rec, d_w, R, d_dC, d_out, ldo, handled);
+    case 6: return launch_eval_records_gradcov<6>(c, N, Q, d_G, d_rec, d_w, R, d_dC, d_out, ldo, handled);
+    case 7: return launch_eval_records_gradcov<7>(c, N, Q, d_G, d_rec, d_w, R, d_dC, d_out, ldo, handled);
+    case 8: return launch_eval_records_gradcov<8>(c, N, Q, d_G, d_rec, d_w, R, d_dC, d_out, ldo, handled);
+    default: return launch_eval_records_gradcov<9>(c, N, Q, d_G, d_rec, d_w, R, d_dC, d_out, ldo, handled);
+    }
+}
 
 // whether K2c takes gradient bases of N rows at all (what a caller that carves a workspace for the library path asks first)
 bool vi_eval_resident_gradcov_shape(int N) { return use_own_kernel() && N >= 1 && N <= 16 * ERR_NBMAX; }

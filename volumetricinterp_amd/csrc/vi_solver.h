@@ -46,6 +46,8 @@ int vi_eval_records_err_mfma(vi_ctx* c, int N, int64_t Q, const double* d_Y, con
 bool vi_eval_resident_gradcov_shape(int N);
 int vi_eval_resident_gradcov_mfma(vi_ctx* c, int N, int64_t Q, int64_t T, const double* d_G, const double* d_dC, double* d_out,
                                   int64_t ldo, int* handled);
+int vi_eval_records_gradcov_mfma(vi_ctx* c, int N, int64_t Q, const double* d_G, const int32_t* d_rec, const double* d_w, int64_t R,
+                                 const double* d_dC, double* d_out, int64_t ldo, int* handled);
 // peak maps and reduced bases of a resident grid seen as (outer, L, inner) (vi_eval_resident.hip)
 bool vi_peak_fused_shape(int N, int64_t outer, int64_t L, int64_t inner);
 size_t vi_peak_fused_work_bytes(int64_t outer, int64_t L, int64_t T);

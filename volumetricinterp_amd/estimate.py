@@ -506,11 +506,42 @@ class Estimate(object):
         return self._along_track('vi_eval_track_err_f64', (), (), times, gdlat, gdlon, gdalt, check_hull, outside, out,
                                  covariance=True)
 
-    def _along_track(self, entry, width, extra, times, gdlat, gdlon, gdalt, check_hull, outside, out, covariance=False):
-        """What track, track_gradient and track_error share: the record (rec, w) of every point's time, the points sorted by
-        record (stable), the library's `entry` - points, the arguments of _upload_records (`covariance`: of the covariances in
-        place of the coefficients), `extra` arguments in, (Q,) + width out - on device copies, the result back in the caller's
-        order: an array of shape gdlat.shape + width."""
+    def track_gradient_covariance(self, times, gdlat, gdlon, gdalt, check_hull=True, outside='raise', frame='model', out=None):
+        """Gradient covariances along a trajectory: element q is what self.gradient_covariance(times[q], gdlat[q], gdlon[q],
+        gdalt[q], check_hull, frame) returns - the symmetric 3 x 3 covariance of the gradient with the covariance of get_C per
+        point, NaN outside the hull and where a covariance the point needs holds a NaN - in ONE library call for all points
+        (vi_eval_track_grad_cov_f64, kernel K2tc) instead of one call, one upload of a covariance and one host hull test per
+        record.  With timeinterp the two neighbours' forms are blended, (1 - w) U_r + w U_(r+1), where gradient_covariance
+        blends the covariances before the form: the same quantity, the form being linear in dC, to rounding.  Only the
+        covariances the points need go to the device (used_records).  times, outside as in track, frame as in gradient.
+        Shape gdlat.shape + (3, 3); `out`: optional C-contiguous float64 array of that shape to write into.  Raises ValueError
+        when the Estimate holds no covariance."""
+        return self._track_gradient_covariance((3, 3), gradcov_matrix, times, gdlat, gdlon, gdalt, check_hull, outside, frame, out)
+
+    def track_gradient_error(self, times, gdlat, gdlon, gdalt, check_hull=True, outside='raise', frame='model', out=None):
+        """Standard errors of the three gradient components along a trajectory, shape gdlat.shape + (3,): the square root of
+        the diagonal of track_gradient_covariance (NaN where it is negative, as gradient_error gives it); element q is what
+        self.gradient_error(times[q], gdlat[q], gdlon[q], gdalt[q], check_hull, frame) returns.  Arguments as there."""
+        def root(packed):
+            with np.errstate(invalid='ignore'):
+                return np.sqrt(packed[:3].T)
+        return self._track_gradient_covariance((3,), root, times, gdlat, gdlon, gdalt, check_hull, outside, frame, out)
+
+    def _track_gradient_covariance(self, width, unpack, times, gdlat, gdlon, gdalt, check_hull, outside, frame, out):
+        """What track_gradient_covariance and track_gradient_error share: the packed (6, Q) result of
+        vi_eval_track_grad_cov_f64 through _along_track, unpacked to (Q,) + width by `unpack`."""
+        if frame not in GRADIENT_FRAMES:
+            raise ValueError("frame must be 'model' or 'enu', not %r" % (frame,))
+        return self._along_track('vi_eval_track_grad_cov_f64', width, (GRADIENT_FRAMES[frame],), times, gdlat, gdlon, gdalt,
+                                 check_hull, outside, out, covariance=True, planar=(6, unpack))
+
+    def _along_track(self, entry, width, extra, times, gdlat, gdlon, gdalt, check_hull, outside, out, covariance=False,
+                     planar=None):
+        """What track, track_gradient, track_error and the track_gradient_covariance pair share: the record (rec, w) of every
+        point's time, the points sorted by record (stable), the library's `entry` - points, the arguments of _upload_records
+        (`covariance`: of the covariances in place of the coefficients), `extra` arguments in, (Q,) + width out - on device
+        copies, the result back in the caller's order: an array of shape gdlat.shape + width.  `planar` = (K, unpack): the
+        entry writes K planes, (K, Q), which unpack turns into (Q,) + width on the host."""
         if covariance:
             self._need_covariance()
         lat, lon, alt = ravel_points(gdlat, gdlon, gdalt)
@@ -524,10 +555,11 @@ class Estimate(object):
         with self.model.ctx.scope() as dev:
             dlat, dlon, dalt = dev.up(lat[order]), dev.up(lon[order]), dev.up(alt[order])
             records = self._upload_records(dev, rec[order], None if w is None else w[order], check_hull, covariance)
-            dO = dev.empty((Q,) + width)
+            dO = dev.empty((Q,) + width if planar is None else (planar[0], Q))
             _lib.check(getattr(_lib.lib, entry)(self.model.handle(), Q, dlat.ptr, dlon.ptr, dalt.ptr, *records, *extra, dO.ptr),
                        entry)
-            out.reshape((Q,) + width)[order] = dO.download()
+            res = dO.download()
+        out.reshape((Q,) + width)[order] = res if planar is None else planar[1](res)
         return out
 
     def _times_for(self, times, shape, what):
