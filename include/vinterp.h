@@ -259,6 +259,21 @@ int  vi_eval_grad_basis_f64(vi_model* model, int64_t Q, const double* d_lat, con
  * K2e takes N <= 144 with Q even and d_Y / d_out 16-byte aligned; other shapes, and VINTERP_EVAL_RESIDENT=blas, go through
  * the library's product and a row dot, as vi_eval_err_f64 (tests/test_gpu_resident_error.py). */
 int  vi_eval_resident_err_f64(vi_model* model, int64_t Q, int64_t T, const double* d_Y, const double* d_dC, double* d_out);
+/* The same form at ONE chosen point per column and timestep, without the map: the standard error of a peak at the position
+ * vi_eval_resident_peak_f64 (below) found, from its index map as it lies on the device.  The grid is seen as (outer, L, inner)
+ * as there, column m = o*inner + i, M = outer*inner columns, and d_idx[t*M + m] = l selects point q = (o*L + l)*inner + i:
+ *   vi_eval_resident_err_at_f64  d_out[t*M + m] = sqrt( sum_i sum_k d_Y[i*Q + q] * d_dC[t*N*N + i*N + k] * d_Y[k*Q + q] )
+ * First-order, the position taken as given.  NaN where l is outside [0, L) - the -1 of a column without a peak -, and
+ * vi_eval_resident_err_f64's NaN cases: a NaN column of d_Y, a NaN anywhere in d_dC[t], a negative form.  An index outside
+ * [0, L) is never turned into an address.  T = 0 or M = 0: nothing is written.
+ * Kernel K2eg (csrc/vi_eval_resident.hip) takes N <= 144 with any M and any alignment: K2e's launch and arithmetic on M columns,
+ * the two points of a lane gathered independently (two 8-byte loads per basis row, 64-bit offsets).  A result has the bits
+ * vi_eval_resident_err_f64's K2e gives at that point with that covariance.  Other orders, and VINTERP_EVAL_RESIDENT=blas, gather
+ * the chosen columns into the context workspace timestep by timestep and go through the library's product and a row dot.
+ * VINTERP_K2E_GROUPS sets the groups of 256 columns per workgroup as for K2e.  Asynchronous on the context's stream; timed for
+ * vi_eval_kernel_ms like its siblings (tests/test_gpu_resident_column_error.py). */
+int  vi_eval_resident_err_at_f64(vi_model* model, int64_t outer, int64_t L, int64_t inner, int64_t T, const double* d_Y,
+                                 const double* d_dC, const int32_t* d_idx, double* d_out);
 /* Standard errors where every column has its OWN record (the points of a track, rays at their own times): the covariance is
  * chosen per column of d_Y instead of per map.  d_Y: any N x Q matrix laid out as vi_eval_basis_f64 / vi_eval_slant_basis_f64
  * make it; d_dC: the R row-major N x N covariances as stored, the full matrix, never assumed symmetric; d_rec[q], d_w select and
@@ -384,7 +399,7 @@ int    vi_reduce_basis_f64(vi_model* model, int64_t outer, int64_t L, int64_t in
  * others return VI_ERR_UNSUPPORTED from vi_eval_f64 while the flag is set. */
 int  vi_model_set_eval_precision(vi_model* model, int32_t chain_f32);
 /* device time (ms) of the evaluation kernel launches of the last vi_eval_f64 / vi_eval_track_f64 / vi_eval_track_grad_f64 / vi_eval_slant_f64 / vi_eval_slant_basis_f64 / vi_eval_resident_f64 /
- * vi_eval_resident_err_f64 / vi_eval_resident_gradcov_f64 / vi_eval_grad_cov_f64 (its last chunk) / vi_eval_records_gradcov_f64 / vi_eval_track_grad_cov_f64 /vi_eval_resident_peak_f64 call on this context, from HIP events recorded on the context's stream around them (the preparation kernels are excluded).
+ * vi_eval_resident_err_f64 / vi_eval_resident_err_at_f64 / vi_eval_resident_gradcov_f64 / vi_eval_grad_cov_f64 (its last chunk) / vi_eval_records_gradcov_f64 / vi_eval_track_grad_cov_f64 /vi_eval_resident_peak_f64 call on this context, from HIP events recorded on the context's stream around them (the preparation kernels are excluded).
  * The events are recorded only while vi_ctx_set_eval_timing(ctx, 1) is in force (default: off - the pair costs a 0.2 ms call about 7 us);
  * vi_eval_kernel_ms fails with VI_ERR_ARG while it is off or before a call has been timed. */
 int  vi_ctx_set_eval_timing(vi_ctx* ctx, int32_t on);

@@ -2475,6 +2475,69 @@ extern "C" int vi_eval_resident_err_f64(vi_model* m, int64_t Q, int64_t T, const
     return VI_OK;
 }
 
+// The form of vi_eval_resident_err_f64 at one chosen point per column and timestep (include/vinterp.h): K2eg
+// (vi_eval_resident.hip) for N <= 144.  Other orders, and VINTERP_EVAL_RESIDENT=blas: timestep by timestep the chosen columns
+// of a chunk are gathered point-major into the context workspace - k_points_major through the index, a row of NaN for an index
+// outside [0, L), which is never turned into an address - then the product and the row dot of vi_eval_resident_err_f64's
+// library route; the NaN row gives the NaN of the column.
+namespace {
+__global__ void k_points_major_at(int64_t P, int N, const double* __restrict__ Y, int64_t Q, int64_t L, int64_t inner, int64_t m0,
+                                  const int* __restrict__ idx, double* __restrict__ A)
+{
+    const int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;     // e = n * P + p, as k_points_major
+    if (e >= P * N) return;
+    const int64_t n = e / P, p = e - n * P;
+    const int64_t m = m0 + p, l = idx[m], o = m / inner;
+    A[p * N + n] = (l >= 0 && l < L) ? Y[n * Q + (o * L + l) * inner + (m - o * inner)] : __builtin_nan("");
+}
+}  // namespace
+
+extern "C" int vi_eval_resident_err_at_f64(vi_model* m, int64_t outer, int64_t L, int64_t inner, int64_t T, const double* d_Y,
+                                           const double* d_dC, const int32_t* d_idx, double* d_out)
+{
+    VI_REQUIRE(m && d_Y && d_dC && d_idx && d_out, "null argument");
+    VI_REQUIRE(outer >= 0 && L >= 0 && inner >= 0 && T >= 0, "negative size");
+    VI_REQUIRE(L <= 0x7fffffffLL, "the indexed axis is longer than a 32-bit index");
+    const int64_t M = outer * inner, Q = M * L;
+    if (M == 0 || T == 0) return VI_OK;
+    vi_ctx* c = m->ctx;
+    VI_HIP(hipSetDevice(c->device));
+    const int N = m->N;
+    if (L == 0) {                            // columns of length zero: no index is inside, d_Y holds nothing to read - all NaN
+        VI_HIP(hipMemsetAsync(d_out, 0xFF, (size_t)(T * M) * sizeof(double), c->stream));
+        return VI_OK;
+    }
+    {
+        EvalTimer timer(c);
+        int handled = 0;
+        const int rc = vi_eval_resident_err_at_mfma(c, N, outer, L, inner, T, d_Y, d_dC, d_idx, d_out, &handled);   // K2eg
+        if (rc != VI_OK || handled) return rc;
+    }
+    // columns per chunk: a workspace of at most 512 MB, as vi_eval_resident_err_f64
+    int64_t chunk = ((int64_t)1 << 25) / N;
+    if (chunk > M) chunk = M;
+    void* ws = nullptr;
+    int rc = vi_ctx_workspace(c, (size_t)2 * chunk * N * sizeof(double), &ws);
+    if (rc != VI_OK) return rc;
+    double* A = (double*)ws;
+    double* B = A + chunk * N;
+    const double one = 1.0, zero = 0.0;
+    EvalTimer timer(c);
+    for (int64_t t = 0; t < T; ++t)
+        for (int64_t m0 = 0; m0 < M; m0 += chunk) {
+            const int64_t mc = (M - m0) < chunk ? (M - m0) : chunk;
+            hipLaunchKernelGGL(k_points_major_at, dim3(nblocks(mc * N, 256)), dim3(256), 0, c->stream, mc, N, d_Y, Q, L, inner, m0,
+                               d_idx + t * M, A);
+            VI_HIP(hipGetLastError());
+            // row-major B (mc x N) = A (mc x N) dC_t^T, as in vi_eval_resident_err_f64
+            VI_ROCBLAS(rocblas_dgemm(c->blas, rocblas_operation_transpose, rocblas_operation_none, N, (rocblas_int)mc, N, &one,
+                                     d_dC + t * N * N, N, A, N, &zero, B, N));
+            hipLaunchKernelGGL(k_rowdot_sqrt, dim3(nblocks(mc, 4)), dim3(256), 0, c->stream, mc, N, A, B, d_out + t * M + m0);
+            VI_HIP(hipGetLastError());
+        }
+    return VI_OK;
+}
+
 // Standard errors with the covariance chosen per column (include/vinterp.h): K2te (vi_eval_resident.hip) for the shapes K2e
 // takes.  Other shapes and orders, and VINTERP_EVAL_RESIDENT=blas, go RUN BY RUN of equal d_rec through the library route of
 // vi_eval_resident_err_f64 - the columns of a chunk point-major once, per run B = A dC_r^T by the library and the row dot, raw,

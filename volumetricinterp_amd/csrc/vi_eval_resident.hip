@@ -754,11 +754,15 @@ __device__ __forceinline__ void err_stage(int N, const double* __restrict__ D, d
     }
 }
 
-// K2e's per-tile body, shared with K2te: the forms y^T S y of the wave's 32 points with the staged S - acc0, acc1 those of the
-// lane's two points yp[0], yp[1] (columns of Y, row stride Q), complete in every lane after the two cross-lane adds
-template <int NB>
+// K2e's per-tile body, shared with K2te and K2eg: the forms y^T S y of the wave's 32 points with the staged S - acc0, acc1
+// those of the lane's two points (columns of Y, row stride Q), complete in every lane after the two cross-lane adds.
+// How the two points are fetched is the one thing that varies: yp[0], yp[1], neighbours, one 16-byte load per basis row (K2e,
+// K2te), or with GATHER yp[0], yp[dq], two columns chosen independently, two 8-byte loads `dq` doubles apart, nothing asked of
+// the alignment of Y (K2eg).  An MFMA output column depends on its own B column alone: a point's bits do not depend on the tile
+// or the lane half that carries it, nor on how it was fetched.
+template <int NB, bool GATHER = false>
 __device__ __forceinline__ void err_forms(int N, int64_t Q, const double* __restrict__ yp, const double* shS, int lane,
-                                          double& acc0, double& acc1)
+                                          double& acc0, double& acc1, int64_t dq = 0)
 {
     const int g = lane >> 4;
     const double* yg = yp + (int64_t)g * Q;             // basis row g; row 16 J + 4 u + g is a uniform offset away
@@ -770,10 +774,14 @@ __device__ __forceinline__ void err_forms(int N, int64_t Q, const double* __rest
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const double* src = yg + (int64_t)(16 * J + 4 * u) * Q;
-            if (J < NB - 1) {
+            // the last block column: rows from N on are zero padding - such a lane reads row 0 of its columns and takes zero
+            const bool in = J < NB - 1 || 16 * J + 4 * u + g < N;
+            if constexpr (GATHER) {
+                const double* s = in ? src : yp;
+                b[u] = in ? (v2f64){s[0], s[dq]} : (v2f64){0.0, 0.0};
+            } else if (J < NB - 1) {
                 b[u] = *reinterpret_cast<const v2f64*>(src);
-            } else {                                    // the last block column: rows from N on are zero padding
-                const bool in = 16 * J + 4 * u + g < N;
+            } else {
                 const v2f64 v = *reinterpret_cast<const v2f64*>(in ? src : yp);
                 b[u] = in ? v : (v2f64){0.0, 0.0};
             }
@@ -839,21 +847,112 @@ __global__ __launch_bounds__(ERR_WAVES * 64) void k_eval_resident_err(int N, int
     }
 }
 
+// points per workgroup of K2e and K2eg on `cols` columns: 256 x groups - S (up to 166 KB of covariance through L2) is staged
+// once per workgroup, against 22 us of matrix-core work per group of 256 points at N = 144.  VINTERP_K2E_GROUPS, read at every
+// launch: tests, experiments.
+int err_groups(int64_t cols)
+{
+    int groups = (int)((cols >> 16) < 1 ? 1 : ((cols >> 16) > 8 ? 8 : (cols >> 16)));
+    if (const char* e = getenv("VINTERP_K2E_GROUPS")) { const int gr = atoi(e); if (gr >= 1 && gr <= 256) groups = gr; }
+    return groups;
+}
+
 template <int NB>
 int launch_eval_resident_err(vi_ctx* c, int N, int64_t Q, int64_t T, const double* d_Y, const double* d_dC, double* d_out,
                              int* handled)
 {
     const size_t shm = (size_t)(NB * (NB + 1) / 2) * 4 * 64 * sizeof(double);
-    // points per workgroup: 256 x groups - S (up to 166 KB of covariance through L2) is staged once per workgroup, against
-    // 22 us of matrix-core work per group of 256 points at N = 144
-    int groups = (int)((Q >> 16) < 1 ? 1 : ((Q >> 16) > 8 ? 8 : (Q >> 16)));
-    if (const char* e = getenv("VINTERP_K2E_GROUPS")) { const int gr = atoi(e); if (gr >= 1 && gr <= 256) groups = gr; }  // experiments
+    const int groups = err_groups(Q);
     const int64_t npg = (Q + (int64_t)ERR_PTS * groups - 1) / ((int64_t)ERR_PTS * groups);
     const int64_t nblk = ((npg + 7) / 8) * 8 * T;
     if (nblk > 0x7fffffffLL) return VI_OK;
     VI_HIP(hipFuncSetAttribute((const void*)k_eval_resident_err<NB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
     hipLaunchKernelGGL(k_eval_resident_err<NB>, dim3((unsigned)nblk), dim3(ERR_WAVES * 64), shm, c->stream, N, Q, T, groups, npg,
                        d_Y, d_dC, d_out);
+    VI_HIP(hipGetLastError());
+    *handled = 1;
+    return VI_OK;
+}
+
+// K2eg: K2e's form at ONE chosen point per column and timestep (vi_eval_resident_err_at_f64: the standard error at the peak
+// that K2p found).  The grid is (outer, L, inner), column m = o inner + i, and idx[t][m] = l selects point
+// q = (o L + l) inner + i:
+//
+//   out[t][m] = sqrt( sum_i sum_k Y[i][q] * dC[t][i][k] * Y[k][q] ),   NaN where l is outside [0, L)
+//
+//  * K2e's launch: one timestep per workgroup in the XCD-aware order, S staged once by err_stage and reused for `groups` x 256
+//    COLUMNS, a wave 32 of them as two 16-column tiles, lane (p, g) the columns 2p, 2p + 1 of its wave's 32.
+//  * The lane's two points are two columns of Y gathered independently (err_forms<NB, true>): L or L inner doubles apart, not
+//    neighbours, so two 8-byte loads per basis row from 64-bit offsets - a cache line per value.  Everything after the load is
+//    err_forms: the bits at a point are K2e's bits at that point with that covariance.
+//  * An index outside [0, L) never becomes an address: the lane half reads column 0, as a lane past the end does, and stores
+//    NaN.  Validity is per lane half, any M >= 1; the two results go out as one 16-byte store where that is aligned, else as two
+//    8-byte stores.
+template <int NB>
+__global__ __launch_bounds__(ERR_WAVES * 64) void k_eval_resident_err_at(int N, int64_t Q, int64_t L, int64_t inner, int64_t M,
+                                                                         int64_t T, int groups, int64_t npg,
+                                                                         const double* __restrict__ Y,
+                                                                         const double* __restrict__ dC,
+                                                                         const int* __restrict__ idx, double* __restrict__ out)
+{
+    extern __shared__ __align__(16) double shS[];         // [block J (J + 1) / 2 + I][k-step u][lane]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t bid = blockIdx.x;
+    const int xcd = (int)(bid & 7);
+    const int64_t r = bid >> 3;
+    const int64_t t = r % T;
+    const int64_t pg = (r / T) * 8 + xcd;
+    if (pg >= npg) return;
+    err_stage<NB, ERR_WAVES>(N, dC + t * N * N, shS, tid);
+    __syncthreads();
+    const int* const it = idx + t * M;
+    double* const ot = out + t * M;
+    for (int grp = 0; grp < groups; ++grp) {
+        const int64_t m0 = (pg * groups + grp) * ERR_PTS + wave * 32;                       // the wave's first column
+        if (m0 >= M) break;                                                                 // (uniform in the wave)
+        // the lane's two points: the flat index of (column, idx[column]), or point 0 for a lane half without one
+        int64_t q[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int64_t m = m0 + 2 * (lane & 15) + j;
+            const int64_t l = m < M ? it[m] : -1;
+            const int64_t o = m / inner;
+            q[j] = (l >= 0 && l < L) ? (o * L + l) * inner + (m - o * inner) : 0;
+        }
+        double acc0, acc1;
+        err_forms<NB, true>(N, Q, Y + q[0], shS, lane, acc0, acc1, q[1] - q[0]);
+        // what the store needs is made again from an opaque copy of the lane index: nothing but the two forms lives across
+        // err_forms (K2e's body leaves two registers free at N = 144)
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
+        const int64_t m = m0 + 2 * (ln & 15);
+        if ((ln >> 4) == 0 && m < M) {
+            const int64_t la = it[m], lb = m + 1 < M ? it[m + 1] : -1;
+            const double nan = __builtin_nan("");         // a negative form gives NaN, as np.sqrt does
+            const double ea = (la >= 0 && la < L) ? sqrt(acc0) : nan, eb = (lb >= 0 && lb < L) ? sqrt(acc1) : nan;
+            if (m + 1 < M && ((uintptr_t)(ot + m) & 15) == 0) {
+                *reinterpret_cast<v2f64*>(ot + m) = (v2f64){ea, eb};
+            } else {
+                ot[m] = ea;
+                if (m + 1 < M) ot[m + 1] = eb;
+            }
+        }
+    }
+}
+
+template <int NB>
+int launch_eval_resident_err_at(vi_ctx* c, int N, int64_t outer, int64_t L, int64_t inner, int64_t T, const double* d_Y,
+                                const double* d_dC, const int32_t* d_idx, double* d_out, int* handled)
+{
+    const size_t shm = (size_t)(NB * (NB + 1) / 2) * 4 * 64 * sizeof(double);
+    const int64_t M = outer * inner;
+    const int groups = err_groups(M);
+    const int64_t npg = (M + (int64_t)ERR_PTS * groups - 1) / ((int64_t)ERR_PTS * groups);
+    const int64_t nblk = ((npg + 7) / 8) * 8 * T;
+    if (nblk > 0x7fffffffLL) return VI_OK;
+    VI_HIP(hipFuncSetAttribute((const void*)k_eval_resident_err_at<NB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+    hipLaunchKernelGGL(k_eval_resident_err_at<NB>, dim3((unsigned)nblk), dim3(ERR_WAVES * 64), shm, c->stream, N, M * L, L, inner,
+                       M, T, groups, npg, d_Y, d_dC, d_idx, d_out);
     VI_HIP(hipGetLastError());
     *handled = 1;
     return VI_OK;
@@ -1041,6 +1140,26 @@ int vi_eval_resident_err_mfma(vi_ctx* c, int N, int64_t Q, int64_t T, const doub
     case 7: return launch_eval_resident_err<7>(c, N, Q, T, d_Y, d_dC, d_out, handled);
     case 8: return launch_eval_resident_err<8>(c, N, Q, T, d_Y, d_dC, d_out, handled);
     default: return launch_eval_resident_err<9>(c, N, Q, T, d_Y, d_dC, d_out, handled);
+    }
+}
+
+// out[t*M + m] of vi_eval_resident_err_at_f64 by K2eg; *handled = 0 when the order is not the kernel's (N > 144) or with
+// VINTERP_EVAL_RESIDENT=blas (the caller then gathers the columns and uses the library).  Any M, any alignment.
+int vi_eval_resident_err_at_mfma(vi_ctx* c, int N, int64_t outer, int64_t L, int64_t inner, int64_t T, const double* d_Y,
+                                 const double* d_dC, const int32_t* d_idx, double* d_out, int* handled)
+{
+    *handled = 0;
+    if (!use_own_kernel() || N < 1 || N > 16 * ERR_NBMAX) return VI_OK;
+    switch ((N + 15) / 16) {
+    case 1: return launch_eval_resident_err_at<1>(c, N, outer, L, inner, T, d_Y, d_dC, d_idx, d_out, handled);
+    case 2: return launch_eval_resident_err_at<2>(c, N, outer, L, inner, T, d_Y, d_dC, d_idx, d_out, handled);
+    case 3: return launch_eval_resident_err_at<3>(c, N, outer, L, inner, T, d_Y, d_dC, d_idx, d_out, handled);
+    case 4: return launch_eval_resident_err_at<4>(c, N, outer, L, inner, T, d_Y, d_dC, d_idx, d_out, handled);
+    case 5: return launch_eval_resident_err_at<5>(c, N, outer, L, inner, T, d_Y, d_dC, d_idx, d_out, handled);
+    case 6: return launch_eval_resident_err_at<6>(c, N, outer, L, inner, T, d_Y, d_dC, d_idx, d_out, handled);
+    case 7: return launch_eval_resident_err_at<7>(c, N, outer, L, inner, T, d_Y, d_dC, d_idx, d_out, handled);
+    case 8: return launch_eval_resident_err_at<8>(c, N, outer, L, inner, T, d_Y, d_dC, d_idx, d_out, handled);
+    default: return launch_eval_resident_err_at<9>(c, N, outer, L, inner, T, d_Y, d_dC, d_idx, d_out, handled);
     }
 }
 

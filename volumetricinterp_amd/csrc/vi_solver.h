@@ -40,6 +40,8 @@ int vi_eval_sph_split(vi_model* m, int64_t Q, const double* lat, const double* l
 int vi_eval_resident_mfma(vi_ctx* c, int N, int64_t Q, int64_t T, const double* d_Y, const double* d_C, double* d_out, int* handled);
 int vi_eval_resident_err_mfma(vi_ctx* c, int N, int64_t Q, int64_t T, const double* d_Y, const double* d_dC, double* d_out,
                               int* handled);
+int vi_eval_resident_err_at_mfma(vi_ctx* c, int N, int64_t outer, int64_t L, int64_t inner, int64_t T, const double* d_Y,
+                                 const double* d_dC, const int32_t* d_idx, double* d_out, int* handled);
 bool vi_eval_records_err_shape(int N, int64_t Q, const double* d_Y, const double* d_out);
 int vi_eval_records_err_mfma(vi_ctx* c, int N, int64_t Q, const double* d_Y, const int32_t* d_rec, const double* d_w, int64_t R,
                              const double* d_dC, double* d_out, int* handled);

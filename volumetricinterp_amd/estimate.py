@@ -282,6 +282,40 @@ def gradcov_matrix(packed):
     return cov
 
 
+def _grid_columns(shape, axis):
+    """A C-ordered grid of `shape` as (outer, L, inner) about `axis`: point q = (o * L + l) * inner + i, column
+    m = o * inner + i.  Returns (axis, outer, L, inner), the axis counted from the front."""
+    nd = len(shape)
+    if nd == 0:
+        raise ValueError('a 0-d grid has no axis to reduce')
+    if not isinstance(axis, (int, np.integer)) or isinstance(axis, bool) or not -nd <= axis < nd:
+        raise ValueError('axis must be an integer in [%d, %d), not %r' % (-nd, nd, axis))
+    axis = int(axis) % nd
+    outer = int(np.prod(shape[:axis], dtype=np.int64))
+    inner = int(np.prod(shape[axis + 1:], dtype=np.int64))
+    return axis, outer, int(shape[axis]), inner
+
+
+def column_points(shape, axis, index):
+    """The flat index (C order) of the point at position index[t, m] along `axis` in column m of a grid of `shape`, the
+    columns in C order of the remaining axes as ResidentGrid.peak numbers them: (T, M) int64, -1 where index is -1 (a column
+    without a peak).  index: (T, M) integers in [-1, L), L the length of the axis; anything else raises ValueError.  On the
+    host; np.take_along_axis(volume.reshape(T, -1), column_points(...), 1) picks the selected values where index >= 0."""
+    shape = tuple(int(n) for n in shape)
+    axis, outer, L, inner = _grid_columns(shape, axis)
+    index = np.asarray(index)
+    if index.dtype.kind not in 'iu':
+        raise ValueError('index must be an integer array, not %s' % index.dtype)
+    M = outer * inner
+    if index.ndim != 2 or index.shape[1] != M:
+        raise ValueError('index must have shape (T, %d), not %r' % (M, index.shape))
+    index = index.astype(np.int64)
+    if index.size and (index.min() < -1 or index.max() >= L):
+        raise ValueError('index must lie in [-1, %d)' % L)
+    o, i = np.divmod(np.arange(M, dtype=np.int64), max(inner, 1))
+    return np.where(index < 0, -1, (o * L + index) * inner + i)
+
+
 class Estimate(object):
     def __init__(self, coeff_filename, timetol=60., timeinterp=False, ctx=None):
         self.timetol = timetol
@@ -767,22 +801,26 @@ class ResidentGrid(object):
             return C, out, 0
         return C, out, self._slab(T, int(np.prod(width)) * 8)
 
-    def _run(self, slab, X, outs, call, work=None, once=True):
+    def _run(self, slab, X, outs, call, work=None, once=True, also=()):
         """The slab loop of every map on the grid.  X holds the inputs of the T timesteps row by row: uploaded once, or (once
-        False) slab by slab.  Per slab of tc timesteps from t0: call(tc, pointer to row t0 of X on the device, device
-        outputs..., work buffer of `work` bytes unless None), then the device outputs to outs[k][t0:t0 + tc].  Every device
-        buffer is freed whatever happens."""
+        False) slab by slab.  `also`: further inputs with a row per timestep, uploaded slab by slab.  Per slab of tc timesteps
+        from t0: call(tc, pointer to row t0 of X on the device, device outputs..., work buffer of `work` bytes unless None,
+        device copies of the rows of `also`...), then the device outputs to outs[k][t0:t0 + tc].  Every device buffer is freed
+        whatever happens."""
         ctx = self.est.model.ctx
         T = X.shape[0]
         with ctx.scope() as dev:
             dX = dev.up(X) if once else dev.empty((slab,) + X.shape[1:])
             dOs = [dev.empty((slab,) + o.shape[1:], o.dtype) for o in outs]
             dW = [] if work is None else [dev.empty(work, np.uint8)]
+            dAs = [dev.empty((slab,) + a.shape[1:], a.dtype) for a in also]
             for t0 in range(0, T, slab):
                 tc = min(slab, T - t0)
                 if not once:
                     dX.upload(X[t0:t0 + tc])
-                call(tc, dX.offset_ptr(t0 * X[0].size if once else 0), *dOs, *dW)
+                for a, dA in zip(also, dAs):
+                    dA.upload(a[t0:t0 + tc])
+                call(tc, dX.offset_ptr(t0 * X[0].size if once else 0), *dOs, *dW, *dAs)
                 for o, dO in zip(outs, dOs):
                     part = o[t0:t0 + tc]
                     _lib.check(_lib.lib.vi_d2h(ctx.handle, part.ctypes.data_as(_lib.VOIDP), dO.ptr, part.nbytes), 'd2h')
@@ -876,6 +914,49 @@ class ResidentGrid(object):
         selects the coefficients): array (len(times),) + grid shape."""
         return self.evaluate_errors(self._covariances_at(times)).reshape((len(times),) + tuple(self.shape))
 
+    def _index_at(self, index, T, axis):
+        """`index` of evaluate_errors_at, checked on the host (column_points' rules, a row per covariance): C-contiguous
+        int32 (T, M)."""
+        index = np.asarray(index)
+        column_points(self.shape, axis, index)
+        if index.shape[0] != T:
+            raise ValueError('index must have a row per covariance (%d), not %d' % (T, index.shape[0]))
+        return np.ascontiguousarray(index, dtype=np.int32)
+
+    def evaluate_errors_at(self, dC, index, axis=-1, out=None):
+        """out[t, m] = standard error sqrt(a^T dC[t] a) of the fitted parameter at ONE point per column and covariance: the
+        point at position index[t, m] along `axis` in column m (columns as in evaluate_peaks; column_points gives its flat
+        index).  index: (T, M) integers in [-1, L), checked before anything goes to the device; (T, M) host array, NaN
+        where index is -1 and where evaluate_errors gives NaN.  What np.take_along_axis picks from evaluate_errors(dC), bit
+        for bit where both run on the matrix cores, without the (T, Q) map (vi_eval_resident_err_at_f64, kernel K2eg)."""
+        axis, outer, L, inner = self._columns(axis)
+        M = outer * inner
+        dC = self._covariances(dC)
+        T, N = dC.shape[0], dC.shape[1]
+        index = self._index_at(index, T, axis)
+        out = _check_out(out, (T, M))
+        if T == 0 or self.Q == 0:
+            out.fill(np.nan)                # (columns of length zero: no point to select)
+            return out
+        h, dY = self.est.model.handle(), self._open(self.dY)
+
+        def call(tc, dD, dO, dI):
+            _lib.check(_lib.lib.vi_eval_resident_err_at_f64(h, outer, L, inner, tc, dY.ptr, dD, dI.ptr, dO.ptr),
+                       'vi_eval_resident_err_at_f64')
+        return self._run(self._slab(T, M * 12 + N * N * 8), dC, (out,), call, once=False, also=(index,))[0]
+
+    def errors_at(self, times, index, axis=-1):
+        """Standard errors at one point per column for a list of datetimes (covariances as error takes them): index of shape
+        (len(times),) + the grid shape without `axis`, positions along `axis` in [-1, L) - what peak returns -; the result has
+        the same shape.  See evaluate_errors_at."""
+        axis, rest = self._rest(times, axis)
+        dC = self._covariances_at(times)
+        index = np.asarray(index)
+        if index.shape != rest:
+            raise ValueError('index must have shape %r, not %r' % (rest, index.shape))
+        M = int(np.prod(rest[1:], dtype=np.int64))
+        return self.evaluate_errors_at(dC, index.reshape(len(times), M), axis=axis).reshape(rest)
+
     def evaluate_gradient_errors(self, dC, out=None):
         """out[t, c] = standard error sqrt(g_c^T dC[t] g_c) of component c of the gradient on the grid for each covariance
         dC[t]; (T, 3, Q) host array, c in the grid's frame, NaN as in evaluate_errors.  The same form as evaluate_errors on the
@@ -910,15 +991,7 @@ class ResidentGrid(object):
 
     def _columns(self, axis):
         """The grid as (outer, L, inner) about `axis`: point q = (o * L + l) * inner + i, column m = o * inner + i."""
-        nd = len(self.shape)
-        if nd == 0:
-            raise ValueError('a 0-d grid has no axis to reduce')
-        if not isinstance(axis, (int, np.integer)) or isinstance(axis, bool) or not -nd <= axis < nd:
-            raise ValueError('axis must be an integer in [%d, %d), not %r' % (-nd, nd, axis))
-        axis = int(axis) % nd
-        outer = int(np.prod(self.shape[:axis], dtype=np.int64))
-        inner = int(np.prod(self.shape[axis + 1:], dtype=np.int64))
-        return axis, outer, int(self.shape[axis]), inner
+        return _grid_columns(self.shape, axis)
 
     def _rest(self, times, axis):
         """(axis, shape) of the column maps of peak and integrate: `axis` as _columns checks it, (len(times),) + the grid
@@ -932,31 +1005,48 @@ class ResidentGrid(object):
         (kind='min': np.nanmin) of evaluate_coeffs(C) and the first position that attains it, (NaN, -1) for a column without
         a number (outside the hull, or NaN coefficients).  Computed on the device from the resident basis; the volume is
         not copied to the host and, with the reduced axis last, not formed.  `out`: a pair of preallocated arrays."""
+        return self._peaks(C, None, axis, kind, out)
+
+    def _peaks(self, C, dC, axis, kind, out):
+        """What evaluate_peaks and evaluate_peak_errors share: (value, index) of the peaks of C and - with covariances dC, a
+        matrix per row of C - the standard error at each peak; `out`: None or preallocated arrays, one per result.  Slab by slab
+        the peak call, then the form at the index map it left on the device (vi_eval_resident_err_at_f64)."""
         axis, outer, L, inner = self._columns(axis)
         if kind not in PEAK_KINDS:
             raise ValueError("kind must be 'max' or 'min', not %r" % (kind,))
         M = outer * inner
         C = self._coeffs(C)
-        T = C.shape[0]
+        T, N = C.shape
+        names = ('value', 'index') if dC is None else ('value', 'index', 'error')
+        if dC is not None:
+            dC = self._covariances(dC)
+            if dC.shape[0] != T:
+                raise ValueError('covariances must have shape (%d, %d, %d): one per coefficient row' % (T, N, N))
         try:
-            val, idx = (None, None) if out is None else out
-            if out is not None and (val is None or idx is None):
+            outs = (None,) * len(names) if out is None else tuple(out)
+            if len(outs) != len(names) or (out is not None and any(o is None for o in outs)):
                 raise TypeError
         except (TypeError, ValueError):
-            raise ValueError('out must be a pair (value, index) of arrays')
-        val, idx = _check_out(val, (T, M)), _check_out(idx, (T, M), np.int32)
+            raise ValueError('out must be a %s (%s) of arrays' % ('pair' if dC is None else 'triple', ', '.join(names)))
+        outs = tuple(_check_out(o, (T, M), np.int32 if name == 'index' else np.float64) for o, name in zip(outs, names))
         if T == 0 or self.Q == 0:
-            val.fill(np.nan)                # (columns of length zero: nothing to select)
-            idx.fill(-1)
-            return val, idx
+            for o, name in zip(outs, names):
+                o.fill(-1 if name == 'index' else np.nan)       # (columns of length zero: nothing to select)
+            return outs
         h, dY = self.est.model.handle(), self._open(self.dY)
         work = lambda tc: int(_lib.lib.vi_eval_resident_peak_work_bytes(h, outer, L, inner, tc))
-        slab = self._slab(T, work(1) + M * 12)          # the work space and the two maps
+        # the work space and the maps; with covariances their slab too
+        slab = self._slab(T, work(1) + M * 12 + (0 if dC is None else M * 8 + N * N * 8))
 
-        def call(tc, dC, dV, dI, dW):
-            _lib.check(_lib.lib.vi_eval_resident_peak_f64(h, outer, L, inner, tc, dY.ptr, dC, PEAK_KINDS[kind], dV.ptr, dI.ptr,
+        def call(tc, dCo, dV, dI, *rest):
+            dW = rest[-1] if dC is None else rest[1]
+            _lib.check(_lib.lib.vi_eval_resident_peak_f64(h, outer, L, inner, tc, dY.ptr, dCo, PEAK_KINDS[kind], dV.ptr, dI.ptr,
                                                           dW.ptr, dW.nbytes), 'vi_eval_resident_peak_f64')
-        return self._run(slab, C, (val, idx), call, work=work(slab))
+            if dC is not None:
+                dE, _, dD = rest
+                _lib.check(_lib.lib.vi_eval_resident_err_at_f64(h, outer, L, inner, tc, dY.ptr, dD.ptr, dI.ptr, dE.ptr),
+                           'vi_eval_resident_err_at_f64')
+        return self._run(slab, C, outs, call, work=work(slab), also=() if dC is None else (dC,))
 
     def peak(self, times, axis=-1, kind='max'):
         """Peak maps for a list of datetimes (coefficients of Estimate.get_C per time, as __call__ takes them): (value, index),
@@ -965,6 +1055,24 @@ class ResidentGrid(object):
         axis, rest = self._rest(times, axis)
         val, idx = self.evaluate_peaks(self._coeffs_at(times), axis=axis, kind=kind)
         return val.reshape(rest), idx.reshape(rest)
+
+    def evaluate_peak_errors(self, C, dC, axis=-1, kind='max', out=None):
+        """(value, index, error): value and index as evaluate_peaks(C, axis, kind) gives them, bit for bit, and error (T, M)
+        float64, the standard error sqrt(a^T dC[t] a) of the parameter at the peak of column m - first-order, the position
+        taken as given; the uncertainty of the position itself is not part of it.  NaN where index is -1 and where
+        evaluate_errors gives NaN at that point.  dC: (T, N, N), a covariance per row of C.  The index map goes from the peak
+        call to the form call on the device; neither the density nor the error volume is formed (with the reduced axis last)
+        or copied to the host.  `out`: a triple of preallocated arrays."""
+        return self._peaks(C, dC, axis, kind, out)
+
+    def peak_error(self, times, axis=-1, kind='max'):
+        """Peak maps with their standard errors for a list of datetimes (coefficients and covariances of Estimate.get_C per
+        time): (value, index, error), each (len(times),) + the grid shape without `axis`; value and index are those of peak.
+        On a (lat, lon, alt) grid: NmF2, the altitude index of hmF2 and the standard error of NmF2."""
+        axis, rest = self._rest(times, axis)
+        dC = self._covariances_at(times)
+        val, idx, err = self.evaluate_peak_errors(self._coeffs_at(times), dC, axis=axis, kind=kind)
+        return val.reshape(rest), idx.reshape(rest), err.reshape(rest)
 
     @staticmethod
     def _weights(L, weights):
@@ -1021,6 +1129,29 @@ class ResidentGrid(object):
         axis, rest = self._rest(times, axis)
         return self.evaluate_integrals(self._coeffs_at(times), weights=weights, axis=axis).reshape(rest)
 
+    def evaluate_integral_errors(self, dC, weights=None, axis=-1, out=None):
+        """out[t, m] = standard error of evaluate_integrals' weighted column sum for each covariance dC[t]: sqrt(b^T dC[t] b)
+        with b column m of the reduced basis of (axis, weights) - the matrix evaluate_integrals multiplies, built once and kept
+        with it - by the form of evaluate_errors on M columns (vi_eval_resident_err_f64).  (T, M) host array in the
+        parameter's unit times the weights' unit; NaN for a column without a point inside the hull, for a covariance holding
+        a NaN and where the form is negative.  weights, axis as in evaluate_integrals, `out` as in evaluate_coeffs."""
+        axis, outer, L, inner = self._columns(axis)
+        w = self._weights(L, weights)
+        M = outer * inner
+        dC = self._covariances(dC)
+        out = _check_out(out, (dC.shape[0], M))
+        if dC.shape[0] == 0 or self.Q == 0:
+            out.fill(np.nan)                # (columns of length zero: no point inside)
+            return out
+        self._open(self.dY)
+        return self._forms('vi_eval_resident_err_f64', self._reduced_basis(axis, outer, L, inner, w), M, dC, out, (M,))
+
+    def integrate_error(self, times, weights=None, axis=-1):
+        """Standard errors of integrate's weighted column sums for a list of datetimes (covariances as error takes them):
+        (len(times),) + the grid shape without `axis`; see evaluate_integral_errors."""
+        axis, rest = self._rest(times, axis)
+        return self.evaluate_integral_errors(self._covariances_at(times), weights=weights, axis=axis).reshape(rest)
+
     def close(self):
         """Give the basis matrix (the gradient basis, the reduced bases of evaluate_integrals) back to the device (idempotent).  Also runs
         on `with est.resident_grid(...) as g:` exit and when the object is collected."""
@@ -1059,6 +1190,7 @@ class ResidentRays(ResidentGrid):
       peak, evaluate_peaks            the largest (smallest) integral along an axis of the ray shape and where it sits;
       integrate, evaluate_integrals   weighted sums of the integrals along an axis, over the rays that enter the hull.
     NaN for a ray that does not enter the hull or has a non-finite end point, 0 for a segment of length zero inside it.
+    peak_error, errors_at and integrate_error give the standard errors of those maxima and weighted sums in the same way.
     It holds no gradient basis: gradient and evaluate_gradients raise."""
 
     def __init__(self, est, start, end, nodes=64, rule=None, coords='geodetic', check_hull=True):
