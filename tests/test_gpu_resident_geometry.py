@@ -1,7 +1,7 @@
 """Resident-grid evaluation (vi_eval_resident_f64) and standard-error maps (vi_eval_resident_err_f64) at every launch geometry,
 against answers known by construction and against a high-precision reference.
 
-The launch of both calls is chosen from (N, Q, T, alignment) alone (csrc/vi_eval_resident.hip, csrc/vi_basis.hip);
+The launch of both calls is chosen from (N, Q, T, alignment) alone (csrc/vi_eval_resident.hip, csrc/vi_resident.hip);
 k2r_geometry and k2e_geometry below restate it:
 
   K2r  k_eval_resident       KS = ceil(N / 4) k-steps, padded to KSp (a multiple of PF = 4); coefficient tile KSp x 2 KB of

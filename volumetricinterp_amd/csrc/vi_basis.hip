@@ -11,6 +11,7 @@
 #include "vi_solver.h"
 #include "vi_sph_device.h"
 
+#include <algorithm>
 #include <cstdlib>
 
 namespace {
@@ -2000,19 +2001,6 @@ int launch_slant_sph(vi_model* m, const SlantArgs& s, const double* Cp)
     });
 }
 
-// records HIP events around the evaluation kernel launches of one vi_eval_f64 call (see vi_eval_kernel_ms)
-struct EvalTimer {
-    vi_ctx* c;
-    explicit EvalTimer(vi_ctx* ctx) : c(ctx)
-    {
-        c->evk_valid = c->evk_enabled && hipEventRecord(c->evk0, c->stream) == hipSuccess;
-    }
-    ~EvalTimer()
-    {
-        if (c->evk_valid) c->evk_valid = hipEventRecord(c->evk1, c->stream) == hipSuccess;
-    }
-};
-
 bool use_fast_eval()
 {
     static const bool generic = vi_env_is("VINTERP_EVAL", "generic");
@@ -2108,6 +2096,27 @@ int launch_grad_sph(vi_model* m, const char* who, int64_t P, const double* d_lat
     });
 }
 
+// The planar gradient basis of Q points, G[(n*3 + c)*Q + q], in the frame asked for - vi_eval_grad_basis_f64's matrix, and that
+// of a chunk of vi_eval_grad_cov_f64 and vi_eval_track_grad_cov_f64.  mask: the hull's bytes for these points, or nullptr.
+int launch_grad_resident(vi_model* m, const char* who, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt,
+                         const unsigned char* d_mask, int32_t frame, double* d_G)
+{
+    return with_flag(frame == VI_FRAME_ENU, [&](auto enu) -> int {
+        return launch_grad_sph<GRAD_RESIDENT, enu>(m, who, Q, d_lat, d_lon, d_alt, nullptr, d_mask, d_G, 1, Q, 3 * Q);
+    });
+}
+
+// A smaller chunk for a call from the switch `name` (tests: several chunks at a small point count), read at every call: its
+// value rounded down to a multiple of `multiple`, taken where it is at least that and below `chunk`
+int64_t test_chunk(const char* name, int64_t chunk, int multiple)
+{
+    if (const char* e = getenv(name)) {
+        const long long v = atoll(e) / multiple * multiple;
+        if (v >= multiple && v < chunk) chunk = v;
+    }
+    return chunk;
+}
+
 // K2tg launch (vi_eval_track_grad_f64): w == nullptr is nearest mode.  C: the R raw rows.
 template <int LCAP, int KCAP>
 int launch_track_grad_sph(vi_model* m, int64_t Q, const double* lat, const double* lon, const double* alt, const int* rec,
@@ -2148,22 +2157,8 @@ extern "C" int vi_eval_grad_f64(vi_model* m, int64_t Q, const double* d_lat, con
 
 // Standard error of the fitted parameter from the coefficient covariance: err[q] = sqrt(a_q^T dC a_q), a_q = basis row
 // of point q (first-order error propagation; the `calcerr` output the reference's Estimate.__call__ advertises but never
-// computes, estimate.py:139-145).  Chunks of points: basis tile A (K1) -> B = A dC (rocBLAS fp64 GEMM, MFMA) ->
-// row-wise dot.  2 N^2 flop per point: MFMA-bound.
-namespace {
-__global__ void k_rowdot_sqrt(int64_t P, int N, const double* __restrict__ A, const double* __restrict__ B,
-                              double* __restrict__ out)
-{
-    const int64_t p = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (p >= P) return;
-    double acc = 0.0;
-    for (int n = lane; n < N; n += 64) acc = fma(A[p * N + n], B[p * N + n], acc);
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o);
-    if (lane == 0) out[p] = sqrt(acc);          // a negative variance (indefinite dC) gives NaN, as np.sqrt would
-}
-}  // namespace
-
+// computes, estimate.py:139-145).  Chunks of points: basis tile A (K1), row-major, then the product and the row dot of the
+// forms' library route (vi_forms_tile, vi_resident.hip).  2 N^2 flop per point: MFMA-bound.
 extern "C" int vi_eval_err_f64(vi_model* m, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt,
                                const double* d_dC, double* d_out)
 {
@@ -2178,18 +2173,11 @@ extern "C" int vi_eval_err_f64(vi_model* m, int64_t Q, const double* d_lat, cons
     if (rc != VI_OK) return rc;
     double* A = (double*)ws;
     double* B = A + chunk * N;
-    const double one = 1.0, zero = 0.0;
-    for (int64_t q0 = 0; q0 < Q; q0 += chunk) {
-        const int64_t qc = (Q - q0) < chunk ? (Q - q0) : chunk;
-        rc = vi_basis_f64(m, qc, d_lat + q0, d_lon + q0, d_alt + q0, A, N, 1);            // row-major (qc, N)
+    return for_chunks(Q, chunk, [&](int64_t q0, int64_t qc) -> int {
+        const int rc = vi_basis_f64(m, qc, d_lat + q0, d_lon + q0, d_alt + q0, A, N, 1);            // row-major (qc, N)
         if (rc != VI_OK) return rc;
-        // row-major B (qc x N) = A (qc x N) dC (N x N)  <=>  column-major B^T (N x qc) = dC^T (N x N) A^T (N x qc)
-        VI_ROCBLAS(rocblas_dgemm(m->ctx->blas, rocblas_operation_transpose, rocblas_operation_none, N, (rocblas_int)qc, N, &one,
-                                 d_dC, N, A, N, &zero, B, N));
-        hipLaunchKernelGGL(k_rowdot_sqrt, dim3(nblocks(qc, 4)), dim3(256), 0, m->ctx->stream, qc, N, A, B, d_out + q0);
-        VI_HIP(hipGetLastError());
-    }
-    return VI_OK;
+        return vi_forms_tile(m->ctx, N, qc, A, d_dC, B, d_out + q0);
+    });
 }
 
 // Arithmetic of the Legendre degree recurrences of the fused evaluation: 0 = fp64 (default), 1 = fp32 chains (seeds,
@@ -2222,14 +2210,10 @@ extern "C" int vi_transform_f64(vi_model* m, int64_t P, const double* d_lat, con
     return VI_OK;
 }
 
-// ---- evaluation of many timesteps on one grid from a RESIDENT basis (BASELINE configs[3]: a GPU's share of 10 000 timesteps on
-// one 256^3 grid).  vi_eval_f64 recomputes the basis of a point for every tile of 32 timesteps - right for one timestep or a
-// few, and it keeps the matrix cores waiting for the recurrences half of the time.  With hundreds of
-// timesteps on the same grid the basis matrix is worth keeping: N x Q doubles - 19 GB at the default order on 256^3, a
-// fifteenth of this GPU's HBM - assembled once by K1 (vi_basis_f64, basis-major so that every access is a contiguous run of
-// points), the rows of points outside the hull set to NaN, so that the mask costs nothing afterwards: NaN times anything is
-// NaN.  The evaluation is then a plain product out(Q x T) = Y(Q x N) C(N x T) - the library's GEMM, in tiles of 128 timesteps
-// (tools/microbench/dgemm_eval_shape.hip: 59 TFLOP/s at 128, 32 at 64, 56 at 256; Y is read once per tile: 0.15 B/flop).
+// ---- the RESIDENT basis of a grid that many timesteps are evaluated on (vi_eval_resident_f64 and the other entries of
+// vi_resident.hip, which has the why): N x Q doubles assembled once by K1 (vi_basis_f64, basis-major so that every access is a
+// contiguous run of points), the rows of points outside the hull set to NaN, so that the mask costs nothing afterwards: NaN
+// times anything is NaN.
 namespace {
 __global__ void k_mask_basis(int64_t Q, int N, const unsigned char* __restrict__ mask, double* __restrict__ Y)
 {
@@ -2324,505 +2308,7 @@ extern "C" int vi_eval_grad_basis_f64(vi_model* m, int64_t Q, const double* d_la
         const int rc = prepare_call(m, Q, d_lat, d_lon, d_alt, d_hull_eq, F, hull_tol, 0, nullptr);
         if (rc != VI_OK) return rc;
     }
-    const unsigned char* d_mask = F > 0 ? m->d_mask : nullptr;
-    if (frame == VI_FRAME_ENU)
-        return launch_grad_sph<GRAD_RESIDENT, true>(m, "vi_eval_grad_basis_f64", Q, d_lat, d_lon, d_alt, nullptr, d_mask, d_G, 1,
-                                                    Q, 3 * Q);
-    return launch_grad_sph<GRAD_RESIDENT, false>(m, "vi_eval_grad_basis_f64", Q, d_lat, d_lon, d_alt, nullptr, d_mask, d_G, 1, Q,
-                                                 3 * Q);
-}
-
-namespace {
-
-// the product of vi_eval_resident_f64 without its timer (vi_eval_resident_peak_f64 runs it per slab inside its own)
-int eval_resident(vi_model* m, int64_t Q, int64_t T, const double* d_Y, const double* d_C, double* d_out)
-{
-    vi_ctx* c = m->ctx;
-    const int N = m->N;
-    int handled = 0;
-    const int rc = vi_eval_resident_mfma(c, N, Q, T, d_Y, d_C, d_out, &handled);      // K2r (vi_eval_resident.hip)
-    if (rc != VI_OK || handled) return rc;
-    // shapes outside K2r's (Q not a multiple of 4, orders whose coefficient tile exceeds the LDS): the library's product
-    const double one = 1.0, zero = 0.0;
-    const int64_t TT = 128;                          // timesteps per product
-    const int64_t QQ = (int64_t)1 << 30;             // points per product (the library's dimensions are 32-bit)
-    for (int64_t t0 = 0; t0 < T; t0 += TT) {
-        const int64_t tc = (T - t0) < TT ? (T - t0) : TT;
-        for (int64_t q0 = 0; q0 < Q; q0 += QQ) {
-            const int64_t qc = (Q - q0) < QQ ? (Q - q0) : QQ;
-            // column-major: out(qc x tc, ld Q) = Y(qc x N, ld Q) * C(N x tc, ld N)
-            VI_ROCBLAS(rocblas_dgemm(c->blas, rocblas_operation_none, rocblas_operation_none, (rocblas_int)qc, (rocblas_int)tc, N,
-                                     &one, d_Y + q0, (rocblas_int)Q, d_C + t0 * N, N, &zero, d_out + t0 * Q + q0, (rocblas_int)Q));
-        }
-    }
-    return VI_OK;
-}
-
-}  // namespace
-
-extern "C" int vi_eval_resident_f64(vi_model* m, int64_t Q, int64_t T, const double* d_Y, const double* d_C, double* d_out)
-{
-    VI_REQUIRE(m && d_Y && d_C && d_out, "null argument");
-    VI_REQUIRE(Q >= 0 && T >= 0, "negative size");
-    if (Q == 0 || T == 0) return VI_OK;
-    VI_HIP(hipSetDevice(m->ctx->device));
-    EvalTimer timer(m->ctx);
-    return eval_resident(m, Q, T, d_Y, d_C, d_out);
-}
-
-// Peak maps along one axis of a resident grid (include/vinterp.h).  K2p where the shape is its own; else, and with
-// VINTERP_K2P=twopass or VINTERP_EVAL_RESIDENT=blas: the density product of vi_eval_resident_f64 into d_work, a slab of as many
-// timesteps as it holds, and k_peak_columns over the slab.
-extern "C" size_t vi_eval_resident_peak_work_bytes(vi_model* m, int64_t outer, int64_t L, int64_t inner, int64_t T)
-{
-    if (!m || outer <= 0 || L <= 0 || inner <= 0 || T <= 0) return 0;
-    if (vi_peak_fused_shape(m->N, outer, L, inner)) return vi_peak_fused_work_bytes(outer, L, T);
-    return (size_t)T * (size_t)(outer * L * inner) * sizeof(double);
-}
-
-extern "C" int vi_eval_resident_peak_f64(vi_model* m, int64_t outer, int64_t L, int64_t inner, int64_t T, const double* d_Y,
-                                         const double* d_C, int32_t kind, double* d_val, int32_t* d_idx, void* d_work,
-                                         size_t work_bytes)
-{
-    VI_REQUIRE(m && d_Y && d_C && d_val && d_idx, "null argument");
-    VI_REQUIRE(outer >= 0 && L >= 0 && inner >= 0 && T >= 0, "negative size");
-    VI_REQUIRE(kind == 0 || kind == 1, "kind must be 0 (max) or 1 (min)");
-    VI_REQUIRE(L <= 0x7fffffffLL, "the reduced axis is longer than a 32-bit index");
-    const int64_t M = outer * inner, Q = M * L;
-    if (Q == 0 || T == 0) return VI_OK;
-    VI_REQUIRE(d_work, "null work space");
-    vi_ctx* c = m->ctx;
-    VI_HIP(hipSetDevice(c->device));
-    EvalTimer timer(c);
-    if (inner == 1) {
-        int handled = 0;
-        const int rc = vi_eval_resident_peak_mfma(c, m->N, outer, L, T, d_Y, d_C, kind, d_val, d_idx, d_work, work_bytes, &handled);
-        if (rc != VI_OK || handled) return rc;
-    }
-    const int64_t slab = (int64_t)(work_bytes / ((size_t)Q * sizeof(double)));
-    VI_REQUIRE(slab >= 1, "work space smaller than the density map of one timestep");
-    for (int64_t t0 = 0; t0 < T; t0 += slab) {
-        const int64_t tc = (T - t0) < slab ? (T - t0) : slab;
-        int rc = eval_resident(m, Q, tc, d_Y, d_C + t0 * m->N, (double*)d_work);
-        if (rc != VI_OK) return rc;
-        rc = vi_peak_columns(c, outer, L, inner, tc, kind, (const double*)d_work, d_val + t0 * M, d_idx + t0 * M);
-        if (rc != VI_OK) return rc;
-    }
-    return VI_OK;
-}
-
-// The reduced basis of a resident grid along one axis (include/vinterp.h): k_reduce_basis (vi_eval_resident.hip)
-extern "C" int vi_reduce_basis_f64(vi_model* m, int64_t outer, int64_t L, int64_t inner, const double* d_Y, const double* d_w,
-                                   double* d_Yr)
-{
-    VI_REQUIRE(m && d_Y && d_w && d_Yr, "null argument");
-    VI_REQUIRE(outer >= 0 && L >= 0 && inner >= 0, "negative size");
-    if (outer * inner == 0) return VI_OK;
-    VI_HIP(hipSetDevice(m->ctx->device));
-    return vi_reduce_basis(m->ctx, m->N, outer, L, inner, d_Y, d_w, d_Yr);
-}
-
-// Standard-error maps of many timesteps on the resident grid: out[t*Q + q] = sqrt(sum_ik Y[i][q] dC[t][i][k] Y[k][q]).  K2e
-// (vi_eval_resident.hip) for N <= 144; other shapes and orders, and VINTERP_EVAL_RESIDENT=blas: per chunk of points the basis
-// columns are turned point-major once into the context workspace, then per timestep the product and the row dot of
-// vi_eval_err_f64 (B = A dC_t by the library, then k_rowdot_sqrt).
-namespace {
-__global__ void k_points_major(int64_t P, int N, const double* __restrict__ Y, int64_t ldy, double* __restrict__ A)
-{
-    const int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;     // e = n * P + q: the reads along the basis rows
-    if (e >= P * N) return;
-    const int64_t n = e / P, q = e - n * P;
-    A[q * N + n] = Y[n * ldy + q];
-}
-}  // namespace
-
-extern "C" int vi_eval_resident_err_f64(vi_model* m, int64_t Q, int64_t T, const double* d_Y, const double* d_dC, double* d_out)
-{
-    VI_REQUIRE(m && d_Y && d_dC && d_out, "null argument");
-    VI_REQUIRE(Q >= 0 && T >= 0, "negative size");
-    if (Q == 0 || T == 0) return VI_OK;
-    vi_ctx* c = m->ctx;
-    VI_HIP(hipSetDevice(c->device));
-    const int N = m->N;
-    {
-        EvalTimer timer(c);
-        int handled = 0;
-        const int rc = vi_eval_resident_err_mfma(c, N, Q, T, d_Y, d_dC, d_out, &handled);      // K2e
-        if (rc != VI_OK || handled) return rc;
-    }
-    // points per chunk: a workspace of at most 512 MB (233 000 points at N = 144)
-    int64_t chunk = ((int64_t)1 << 25) / N;
-    if (chunk > Q) chunk = Q;
-    void* ws = nullptr;
-    int rc = vi_ctx_workspace(c, (size_t)2 * chunk * N * sizeof(double), &ws);
-    if (rc != VI_OK) return rc;
-    double* A = (double*)ws;
-    double* B = A + chunk * N;
-    const double one = 1.0, zero = 0.0;
-    EvalTimer timer(c);
-    for (int64_t q0 = 0; q0 < Q; q0 += chunk) {
-        const int64_t qc = (Q - q0) < chunk ? (Q - q0) : chunk;
-        hipLaunchKernelGGL(k_points_major, dim3(nblocks(qc * N, 256)), dim3(256), 0, c->stream, qc, N, d_Y + q0, Q, A);
-        VI_HIP(hipGetLastError());
-        for (int64_t t = 0; t < T; ++t) {
-            // row-major B (qc x N) = A (qc x N) dC_t^T, B[q][i] = sum_k dC_t[i][k] Y[k][q0 + q] (as in vi_eval_err_f64)
-            VI_ROCBLAS(rocblas_dgemm(c->blas, rocblas_operation_transpose, rocblas_operation_none, N, (rocblas_int)qc, N, &one,
-                                     d_dC + t * N * N, N, A, N, &zero, B, N));
-            hipLaunchKernelGGL(k_rowdot_sqrt, dim3(nblocks(qc, 4)), dim3(256), 0, c->stream, qc, N, A, B, d_out + t * Q + q0);
-            VI_HIP(hipGetLastError());
-        }
-    }
-    return VI_OK;
-}
-
-// The form of vi_eval_resident_err_f64 at one chosen point per column and timestep (include/vinterp.h): K2eg
-// (vi_eval_resident.hip) for N <= 144.  Other orders, and VINTERP_EVAL_RESIDENT=blas: timestep by timestep the chosen columns
-// of a chunk are gathered point-major into the context workspace - k_points_major through the index, a row of NaN for an index
-// outside [0, L), which is never turned into an address - then the product and the row dot of vi_eval_resident_err_f64's
-// library route; the NaN row gives the NaN of the column.
-namespace {
-__global__ void k_points_major_at(int64_t P, int N, const double* __restrict__ Y, int64_t Q, int64_t L, int64_t inner, int64_t m0,
-                                  const int* __restrict__ idx, double* __restrict__ A)
-{
-    const int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;     // e = n * P + p, as k_points_major
-    if (e >= P * N) return;
-    const int64_t n = e / P, p = e - n * P;
-    const int64_t m = m0 + p, l = idx[m], o = m / inner;
-    A[p * N + n] = (l >= 0 && l < L) ? Y[n * Q + (o * L + l) * inner + (m - o * inner)] : __builtin_nan("");
-}
-}  // namespace
-
-extern "C" int vi_eval_resident_err_at_f64(vi_model* m, int64_t outer, int64_t L, int64_t inner, int64_t T, const double* d_Y,
-                                           const double* d_dC, const int32_t* d_idx, double* d_out)
-{
-    VI_REQUIRE(m && d_Y && d_dC && d_idx && d_out, "null argument");
-    VI_REQUIRE(outer >= 0 && L >= 0 && inner >= 0 && T >= 0, "negative size");
-    VI_REQUIRE(L <= 0x7fffffffLL, "the indexed axis is longer than a 32-bit index");
-    const int64_t M = outer * inner, Q = M * L;
-    if (M == 0 || T == 0) return VI_OK;
-    vi_ctx* c = m->ctx;
-    VI_HIP(hipSetDevice(c->device));
-    const int N = m->N;
-    if (L == 0) {                            // columns of length zero: no index is inside, d_Y holds nothing to read - all NaN
-        VI_HIP(hipMemsetAsync(d_out, 0xFF, (size_t)(T * M) * sizeof(double), c->stream));
-        return VI_OK;
-    }
-    {
-        EvalTimer timer(c);
-        int handled = 0;
-        const int rc = vi_eval_resident_err_at_mfma(c, N, outer, L, inner, T, d_Y, d_dC, d_idx, d_out, &handled);   // K2eg
-        if (rc != VI_OK || handled) return rc;
-    }
-    // columns per chunk: a workspace of at most 512 MB, as vi_eval_resident_err_f64
-    int64_t chunk = ((int64_t)1 << 25) / N;
-    if (chunk > M) chunk = M;
-    void* ws = nullptr;
-    int rc = vi_ctx_workspace(c, (size_t)2 * chunk * N * sizeof(double), &ws);
-    if (rc != VI_OK) return rc;
-    double* A = (double*)ws;
-    double* B = A + chunk * N;
-    const double one = 1.0, zero = 0.0;
-    EvalTimer timer(c);
-    for (int64_t t = 0; t < T; ++t)
-        for (int64_t m0 = 0; m0 < M; m0 += chunk) {
-            const int64_t mc = (M - m0) < chunk ? (M - m0) : chunk;
-            hipLaunchKernelGGL(k_points_major_at, dim3(nblocks(mc * N, 256)), dim3(256), 0, c->stream, mc, N, d_Y, Q, L, inner, m0,
-                               d_idx + t * M, A);
-            VI_HIP(hipGetLastError());
-            // row-major B (mc x N) = A (mc x N) dC_t^T, as in vi_eval_resident_err_f64
-            VI_ROCBLAS(rocblas_dgemm(c->blas, rocblas_operation_transpose, rocblas_operation_none, N, (rocblas_int)mc, N, &one,
-                                     d_dC + t * N * N, N, A, N, &zero, B, N));
-            hipLaunchKernelGGL(k_rowdot_sqrt, dim3(nblocks(mc, 4)), dim3(256), 0, c->stream, mc, N, A, B, d_out + t * M + m0);
-            VI_HIP(hipGetLastError());
-        }
-    return VI_OK;
-}
-
-// Standard errors with the covariance chosen per column (include/vinterp.h): K2te (vi_eval_resident.hip) for the shapes K2e
-// takes.  Other shapes and orders, and VINTERP_EVAL_RESIDENT=blas, go RUN BY RUN of equal d_rec through the library route of
-// vi_eval_resident_err_f64 - the columns of a chunk point-major once, per run B = A dC_r^T by the library and the row dot, raw,
-// into a work space of 2 forms per point (in blend mode again with dC_(r+1)) - and k_records_finish blends the forms and takes
-// the square root.  This route reads d_rec back to find the runs, so it waits for the stream.
-namespace {
-// the forms themselves: out[p] = A[p] . B[p], k_rowdot_sqrt without the square root
-__global__ void k_rowdot(int64_t P, int N, const double* __restrict__ A, const double* __restrict__ B, double* __restrict__ out)
-{
-    const int64_t p = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (p >= P) return;
-    double acc = 0.0;
-    for (int n = lane; n < N; n += 64) acc = fma(A[p * N + n], B[p * N + n], acc);
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o);
-    if (lane == 0) out[p] = acc;
-}
-
-// out[q] from the forms F0[q] of record rec[q] and - in blend mode, w != nullptr - F1[q] of the next one; NaN without a record
-__global__ void k_records_finish(int64_t P, const int* __restrict__ rec, const double* __restrict__ w, int R,
-                                 const double* __restrict__ F0, const double* __restrict__ F1, double* __restrict__ out)
-{
-    const int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (q >= P) return;
-    const int r = rec[q];
-    if (r < 0 || (int64_t)r + (w ? 1 : 0) >= R)
-        out[q] = __builtin_nan("");
-    else
-        out[q] = w ? vi_err_blend_sqrt(w[q], F0[q], F1[q]) : sqrt(F0[q]);
-}
-
-// points per chunk of the library route, as vi_eval_resident_err_f64 sizes it, and the doubles of its work space: A, B, forms
-int64_t records_err_chunk(int N, int64_t Q) { return std::min(Q, std::max<int64_t>(1, ((int64_t)1 << 25) / N)); }
-size_t records_err_work_doubles(int N, int64_t chunk) { return (size_t)2 * chunk * N + (size_t)2 * chunk; }
-
-// vi_eval_records_err_f64 without its checks and its timer.  work: records_err_work_doubles(N, records_err_chunk(N, Q)) doubles
-// for the library route, or nullptr: taken from the context workspace when that route runs.
-int records_err(vi_model* m, int64_t Q, const double* d_Y, const int32_t* d_rec, const double* d_w, int64_t R,
-                const double* d_dC, double* d_out, double* work)
-{
-    vi_ctx* c = m->ctx;
-    const int N = m->N;
-    int handled = 0;
-    int rc = vi_eval_records_err_mfma(c, N, Q, d_Y, d_rec, d_w, R, d_dC, d_out, &handled);     // K2te
-    if (rc != VI_OK || handled) return rc;
-    std::vector<int32_t> rec((size_t)Q);
-    VI_HIP(hipMemcpyAsync(rec.data(), d_rec, (size_t)Q * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    VI_HIP(hipStreamSynchronize(c->stream));
-    const int64_t chunk = records_err_chunk(N, Q);
-    if (!work) {
-        void* ws = nullptr;
-        rc = vi_ctx_workspace(c, records_err_work_doubles(N, chunk) * sizeof(double), &ws);
-        if (rc != VI_OK) return rc;
-        work = (double*)ws;
-    }
-    double* A = work;
-    double* B = A + chunk * N;
-    double* F[2] = {B + chunk * N, B + chunk * N + chunk};
-    const int npass = d_w ? 2 : 1;
-    const double one = 1.0, zero = 0.0;
-    for (int64_t q0 = 0; q0 < Q; q0 += chunk) {
-        const int64_t qc = (Q - q0) < chunk ? (Q - q0) : chunk;
-        hipLaunchKernelGGL(k_points_major, dim3(nblocks(qc * N, 256)), dim3(256), 0, c->stream, qc, N, d_Y + q0, Q, A);
-        VI_HIP(hipGetLastError());
-        for (int64_t a = 0, b; a < qc; a = b) {              // the run [a, b) of record r
-            const int64_t r = rec[q0 + a];
-            for (b = a + 1; b < qc && rec[q0 + b] == r; ++b) {}
-            if (r < 0 || r + npass - 1 >= R) continue;       // no record: k_records_finish reads no form
-            for (int pass = 0; pass < npass; ++pass) {
-                // row-major B (run x N) = A (run x N) dC^T, as in vi_eval_resident_err_f64
-                VI_ROCBLAS(rocblas_dgemm(c->blas, rocblas_operation_transpose, rocblas_operation_none, N, (rocblas_int)(b - a), N,
-                                         &one, d_dC + (r + pass) * N * N, N, A + a * N, N, &zero, B + a * N, N));
-                hipLaunchKernelGGL(k_rowdot, dim3(nblocks(b - a, 4)), dim3(256), 0, c->stream, b - a, N, A + a * N, B + a * N,
-                                   F[pass] + a);
-                VI_HIP(hipGetLastError());
-            }
-        }
-        hipLaunchKernelGGL(k_records_finish, dim3(nblocks(qc, 256)), dim3(256), 0, c->stream, qc, d_rec + q0,
-                           d_w ? d_w + q0 : nullptr, (int)R, F[0], F[1], d_out + q0);
-        VI_HIP(hipGetLastError());
-    }
-    return VI_OK;
-}
-}  // namespace
-
-extern "C" int vi_eval_records_err_f64(vi_model* m, int64_t Q, const double* d_Y, const int32_t* d_rec, const double* d_w,
-                                       int64_t R, const double* d_dC, double* d_out)
-{
-    VI_REQUIRE(m && d_Y && d_rec && d_out, "null argument");
-    VI_REQUIRE(Q >= 0 && R >= 0, "negative size");
-    VI_REQUIRE(R == 0 || d_dC, "record count given without covariances");
-    VI_REQUIRE(R <= 0x7fffffffLL, "more records than a 32-bit record index");
-    if (Q == 0) return VI_OK;
-    VI_HIP(hipSetDevice(m->ctx->device));
-    EvalTimer timer(m->ctx);
-    return records_err(m, Q, d_Y, d_rec, d_w, R, d_dC, d_out, nullptr);
-}
-
-// Gradient-covariance maps on a resident gradient basis: out[(t*6 + k)*ldo + q] = g_c^T 1/2 (dC_t + dC_t^T) g_d, (c, d) the
-// k-th of (0,0) (1,1) (2,2) (0,1) (0,2) (1,2), g_c = column (c, q) of d_G[(n*3 + c)*Q + q].  K2c (vi_eval_resident.hip) for
-// N <= 144; other orders, and VINTERP_EVAL_RESIDENT=blas: per chunk of points the three components are turned point-major
-// (row d * qc + q of A), then per timestep B = A dC_t^T by the library and the nine row dots M[c][d] = A_c[q] . B_d[q]
-// = g_c^T dC_t g_d, symmetrised as K2c does: 1/2 (M[c][d] + M[d][c]).
-namespace {
-// A[(d*P + q)*N + n] = G[(n*3 + d)*ldg + q]
-__global__ void k_points_major3(int64_t P, int N, const double* __restrict__ G, int64_t ldg, double* __restrict__ A)
-{
-    const int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;     // e = (n * 3 + d) * P + q: the reads along the rows
-    if (e >= 3 * P * N) return;
-    const int64_t nd = e / P, q = e - nd * P;
-    const int64_t n = nd / 3, d = nd - 3 * n;
-    A[(d * P + q) * N + n] = G[nd * ldg + q];
-}
-
-// a wave per point: the nine dots of its three rows of A with its three rows of B, the six entries of the symmetric part
-__global__ void k_rowdot_gradcov(int64_t P, int N, const double* __restrict__ A, const double* __restrict__ B,
-                                 double* __restrict__ out, int64_t ldo)
-{
-    const int64_t p = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (p >= P) return;
-    double M[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
-    for (int n = lane; n < N; n += 64) {
-        double a[3], b[3];
-        for (int c = 0; c < 3; ++c) {
-            a[c] = A[(c * P + p) * N + n];
-            b[c] = B[(c * P + p) * N + n];
-        }
-        for (int c = 0; c < 3; ++c)
-            for (int d = 0; d < 3; ++d) M[c][d] = fma(a[c], b[d], M[c][d]);
-    }
-    for (int c = 0; c < 3; ++c)
-        for (int d = 0; d < 3; ++d)
-            for (int o = 32; o > 0; o >>= 1) M[c][d] += __shfl_down(M[c][d], o);
-    if (lane == 0) {
-        out[0 * ldo + p] = M[0][0];
-        out[1 * ldo + p] = M[1][1];
-        out[2 * ldo + p] = M[2][2];
-        out[3 * ldo + p] = 0.5 * (M[0][1] + M[1][0]);
-        out[4 * ldo + p] = 0.5 * (M[0][2] + M[2][0]);
-        out[5 * ldo + p] = 0.5 * (M[1][2] + M[2][1]);
-    }
-}
-
-// points per chunk of the library path: a workspace of at most 512 MB for A and B (77 000 points at N = 144)
-int64_t gradcov_chunk(int N) { return std::max<int64_t>(1, ((int64_t)1 << 25) / (3 * (int64_t)N)); }
-
-// The library path: the maps of T covariances on Q points of a gradient basis d_G with row stride ldg (Q of its columns) into
-// d_out with plane stride ldo.  AB: 6 min(Q, gradcov_chunk(N)) N doubles.
-int gradcov_library(vi_model* m, int64_t Q, int64_t T, const double* d_G, int64_t ldg, const double* d_dC, double* d_out,
-                    int64_t ldo, double* AB)
-{
-    vi_ctx* c = m->ctx;
-    const int N = m->N;
-    int64_t chunk = gradcov_chunk(N);
-    if (chunk > Q) chunk = Q;
-    double* A = AB;
-    double* B = A + 3 * chunk * N;
-    const double one = 1.0, zero = 0.0;
-    for (int64_t q0 = 0; q0 < Q; q0 += chunk) {
-        const int64_t qc = (Q - q0) < chunk ? (Q - q0) : chunk;
-        hipLaunchKernelGGL(k_points_major3, dim3(nblocks(3 * qc * N, 256)), dim3(256), 0, c->stream, qc, N, d_G + q0, ldg, A);
-        VI_HIP(hipGetLastError());
-        for (int64_t t = 0; t < T; ++t) {
-            // row-major B (3 qc x N) = A (3 qc x N) dC_t^T, B[d*qc + q][i] = sum_k dC_t[i][k] g_d,k (as in vi_eval_resident_err_f64)
-            VI_ROCBLAS(rocblas_dgemm(c->blas, rocblas_operation_transpose, rocblas_operation_none, N, (rocblas_int)(3 * qc), N, &one,
-                                     d_dC + t * N * N, N, A, N, &zero, B, N));
-            hipLaunchKernelGGL(k_rowdot_gradcov, dim3(nblocks(qc, 4)), dim3(256), 0, c->stream, qc, N, A, B,
-                               d_out + t * 6 * ldo + q0, ldo);
-            VI_HIP(hipGetLastError());
-        }
-    }
-    return VI_OK;
-}
-
-// The maps of T covariances on the Q points of the gradient basis d_G (N x 3 x Q) into d_out with plane stride ldo.  AB: 6 min(Q, gradcov_chunk(N)) N doubles for the library path, or nullptr: taken from the
-// context workspace when that path runs.
-int eval_resident_gradcov(vi_model* m, int64_t Q, int64_t T, const double* d_G, const double* d_dC, double* d_out, int64_t ldo,
-                          double* AB)
-{
-    vi_ctx* c = m->ctx;
-    const int N = m->N;
-    int handled = 0;
-    int rc = vi_eval_resident_gradcov_mfma(c, N, Q, T, d_G, d_dC, d_out, ldo, &handled);      // K2c
-    if (rc != VI_OK || handled) return rc;
-    if (!AB) {
-        void* ws = nullptr;
-        rc = vi_ctx_workspace(c, (size_t)6 * std::min(Q, gradcov_chunk(N)) * N * sizeof(double), &ws);
-        if (rc != VI_OK) return rc;
-        AB = (double*)ws;
-    }
-    return gradcov_library(m, Q, T, d_G, Q, d_dC, d_out, ldo, AB);
-}
-
-// Gradient covariances with the covariance chosen per column (include/vinterp.h): K2tc (vi_eval_resident.hip) for N <= 144.
-// Other orders, and VINTERP_EVAL_RESIDENT=blas, go RUN BY RUN of equal d_rec through the library path above with T = 1 - the
-// six entries raw into a work space of two (6, chunk) planes per point (in blend mode again with dC_(r+1)) - and
-// k_records_gradcov_finish blends them and writes the NaN of a missing record, as records_err / k_records_finish do for the
-// scalar case.  This route reads d_rec back to find the runs, so it waits for the stream.
-//
-// out[k*ldo + q] from the entries F0[k*ldf + q] of record rec[q] and - in blend mode, w != nullptr - F1[k*ldf + q] of the next one
-__global__ void k_records_gradcov_finish(int64_t P, const int* __restrict__ rec, const double* __restrict__ w, int R,
-                                         const double* __restrict__ F0, const double* __restrict__ F1, int64_t ldf,
-                                         double* __restrict__ out, int64_t ldo)
-{
-    const int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (q >= P) return;
-    const int r = rec[q];
-    const bool none = r < 0 || (int64_t)r + (w ? 1 : 0) >= R;
-    for (int k = 0; k < 6; ++k) {
-        double v = __builtin_nan("");
-        if (!none) v = w ? vi_err_blend(w[q], F0[k * ldf + q], F1[k * ldf + q]) : F0[k * ldf + q];
-        out[k * ldo + q] = v;
-    }
-}
-
-// the doubles of the work space of the library route for chunks of `chunk` points: A and B of gradcov_library, two planes of
-// six entries per point
-size_t records_gradcov_work_doubles(int N, int64_t chunk) { return (size_t)6 * chunk * N + (size_t)12 * chunk; }
-
-// vi_eval_records_gradcov_f64 without its checks and its timer: the Q points of the gradient basis d_G (N x 3 x Q) into d_out
-// with plane stride ldo.  work: records_gradcov_work_doubles(N, min(Q, gradcov_chunk(N))) doubles for the library route, or
-// nullptr: taken from the context workspace when that route runs.
-int records_gradcov(vi_model* m, int64_t Q, const double* d_G, const int32_t* d_rec, const double* d_w, int64_t R,
-                    const double* d_dC, double* d_out, int64_t ldo, double* work)
-{
-    vi_ctx* c = m->ctx;
-    const int N = m->N;
-    int handled = 0;
-    int rc = vi_eval_records_gradcov_mfma(c, N, Q, d_G, d_rec, d_w, R, d_dC, d_out, ldo, &handled);      // K2tc
-    if (rc != VI_OK || handled) return rc;
-    std::vector<int32_t> rec((size_t)Q);
-    VI_HIP(hipMemcpyAsync(rec.data(), d_rec, (size_t)Q * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    VI_HIP(hipStreamSynchronize(c->stream));
-    const int64_t chunk = std::min(Q, gradcov_chunk(N));
-    if (!work) {
-        void* ws = nullptr;
-        rc = vi_ctx_workspace(c, records_gradcov_work_doubles(N, chunk) * sizeof(double), &ws);
-        if (rc != VI_OK) return rc;
-        work = (double*)ws;
-    }
-    double* AB = work;
-    double* F[2] = {AB + 6 * chunk * N, AB + 6 * chunk * N + 6 * chunk};
-    const int npass = d_w ? 2 : 1;
-    for (int64_t q0 = 0; q0 < Q; q0 += chunk) {
-        const int64_t qc = (Q - q0) < chunk ? (Q - q0) : chunk;
-        for (int64_t a = 0, b; a < qc; a = b) {              // the run [a, b) of record r
-            const int64_t r = rec[q0 + a];
-            for (b = a + 1; b < qc && rec[q0 + b] == r; ++b) {}
-            if (r < 0 || r + npass - 1 >= R) continue;       // no record: k_records_gradcov_finish reads no entry
-            for (int pass = 0; pass < npass; ++pass)
-                if ((rc = gradcov_library(m, b - a, 1, d_G + q0 + a, Q, d_dC + (r + pass) * N * N, F[pass] + a, chunk, AB)) != VI_OK)
-                    return rc;
-        }
-        hipLaunchKernelGGL(k_records_gradcov_finish, dim3(nblocks(qc, 256)), dim3(256), 0, c->stream, qc, d_rec + q0,
-                           d_w ? d_w + q0 : nullptr, (int)R, F[0], F[1], chunk, d_out + q0, ldo);
-        VI_HIP(hipGetLastError());
-    }
-    return VI_OK;
-}
-}  // namespace
-
-extern "C" int vi_eval_records_gradcov_f64(vi_model* m, int64_t Q, const double* d_G, const int32_t* d_rec, const double* d_w,
-                                           int64_t R, const double* d_dC, double* d_out)
-{
-    VI_REQUIRE(m && d_G && d_rec && d_out, "null argument");
-    VI_REQUIRE(Q >= 0 && R >= 0, "negative size");
-    VI_REQUIRE(R == 0 || d_dC, "record count given without covariances");
-    VI_REQUIRE(R <= 0x7fffffffLL, "more records than a 32-bit record index");
-    if (Q == 0) return VI_OK;
-    VI_HIP(hipSetDevice(m->ctx->device));
-    EvalTimer timer(m->ctx);
-    return records_gradcov(m, Q, d_G, d_rec, d_w, R, d_dC, d_out, Q, nullptr);
-}
-
-extern "C" int vi_eval_resident_gradcov_f64(vi_model* m, int64_t Q, int64_t T, const double* d_G, const double* d_dC,
-                                            double* d_out)
-{
-    VI_REQUIRE(m && d_G && d_dC && d_out, "null argument");
-    VI_REQUIRE(Q >= 0 && T >= 0, "negative size");
-    if (Q == 0 || T == 0) return VI_OK;
-    vi_ctx* c = m->ctx;
-    VI_HIP(hipSetDevice(c->device));
-    EvalTimer timer(c);
-    return eval_resident_gradcov(m, Q, T, d_G, d_dC, d_out, Q, nullptr);
+    return launch_grad_resident(m, "vi_eval_grad_basis_f64", Q, d_lat, d_lon, d_alt, F > 0 ? m->d_mask : nullptr, frame, d_G);
 }
 
 // The gradient covariance of ONE covariance at arbitrary points, d_out[k*Q + q]: in chunks of points the planar gradient basis
@@ -2843,29 +2329,22 @@ extern "C" int vi_eval_grad_cov_f64(vi_model* m, int64_t Q, const double* d_lat,
     VI_HIP(hipSetDevice(c->device));
     const int N = m->N;
     if (F > 0 && (rc = prepare_call(m, Q, d_lat, d_lon, d_alt, d_hull_eq, F, hull_tol, 0, nullptr)) != VI_OK) return rc;
-    int64_t chunk = gradcov_chunk(N);
-    if (const char* e = getenv("VINTERP_GRADCOV_CHUNK")) { const long long v = atoll(e); if (v >= 1 && v < chunk) chunk = v; }
-    if (chunk > Q) chunk = Q;
+    const int64_t chunk = std::min(Q, test_chunk("VINTERP_GRADCOV_CHUNK", vi_forms_chunk(N, 3), 1));
     const bool own = vi_eval_resident_gradcov_shape(N);
-    void* ws = nullptr;
-    rc = vi_ctx_workspace(c, (size_t)(own ? 3 : 9) * chunk * N * sizeof(double), &ws);
+    double *G, *AB;                                       // AB: A and B of the library route, behind G without a gap
+    rc = ws_carve(c, [&](ws_carver& w) {
+        G = w.take<double>((size_t)3 * chunk * N);
+        AB = w.take<double>(own ? 0 : (size_t)6 * chunk * N, 8);
+        if (own) AB = nullptr;
+    });
     if (rc != VI_OK) return rc;
-    double* G = (double*)ws;
-    double* AB = own ? nullptr : G + 3 * chunk * N;
-    for (int64_t q0 = 0; q0 < Q; q0 += chunk) {
-        const int64_t qc = (Q - q0) < chunk ? (Q - q0) : chunk;
-        const unsigned char* d_mask = F > 0 ? m->d_mask + q0 : nullptr;
-        rc = frame == VI_FRAME_ENU
-                 ? launch_grad_sph<GRAD_RESIDENT, true>(m, "vi_eval_grad_cov_f64", qc, d_lat + q0, d_lon + q0, d_alt + q0, nullptr,
-                                                        d_mask, G, 1, qc, 3 * qc)
-                 : launch_grad_sph<GRAD_RESIDENT, false>(m, "vi_eval_grad_cov_f64", qc, d_lat + q0, d_lon + q0, d_alt + q0, nullptr,
-                                                         d_mask, G, 1, qc, 3 * qc);
+    return for_chunks(Q, chunk, [&](int64_t q0, int64_t qc) -> int {
+        const int rc = launch_grad_resident(m, "vi_eval_grad_cov_f64", qc, d_lat + q0, d_lon + q0, d_alt + q0,
+                                            F > 0 ? m->d_mask + q0 : nullptr, frame, G);
         if (rc != VI_OK) return rc;
         EvalTimer timer(c);
-        rc = eval_resident_gradcov(m, qc, 1, G, d_dC, d_out + q0, Q, AB);
-        if (rc != VI_OK) return rc;
-    }
-    return VI_OK;
+        return vi_resident_gradcov(m, qc, 1, G, d_dC, d_out + q0, Q, AB);
+    });
 }
 
 extern "C" int vi_eval_f64(vi_model* m, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt,
@@ -2998,13 +2477,12 @@ extern "C" int vi_eval_track_grad_f64(vi_model* m, int64_t Q, const double* d_la
 namespace {
 // Points (rays) per chunk of vi_eval_track_err_f64 and vi_eval_slant_err_f64: the basis of a chunk takes at most 256 MB of the
 // context workspace, half of what the library route of vi_eval_resident_err_f64 asks for its two matrices - with which the
-// library route of a chunk (records_err) fits beside it.  Even, so that every chunk of an even call keeps K2te's shape.
+// library route of a chunk (vi_records_err) fits beside it.  Even, so that every chunk of an even call keeps K2te's shape.
 // VINTERP_TRACK_ERR_CHUNK: a smaller chunk (tests: several chunks at a small Q).
 int64_t track_err_chunk(int N, int64_t Q)
 {
-    int64_t chunk = std::max<int64_t>(2, (((int64_t)1 << 25) / N) & ~(int64_t)1);
-    if (const char* e = getenv("VINTERP_TRACK_ERR_CHUNK")) { const long long v = atoll(e) & ~1LL; if (v >= 2 && v < chunk) chunk = v; }
-    return std::min(chunk, Q);
+    const int64_t chunk = std::max<int64_t>(2, vi_forms_chunk(N, 1) & ~(int64_t)1);
+    return std::min(Q, test_chunk("VINTERP_TRACK_ERR_CHUNK", chunk, 2));
 }
 
 // The workspace of a chunked call: the basis Y (N x chunk), `extra` doubles for the caller, and - unless every chunk is K2te's -
@@ -3016,7 +2494,7 @@ int track_err_workspace(vi_model* m, int64_t Q, int64_t chunk, const double* d_o
     return ws_carve(m->ctx, [&](ws_carver& w) {
         *Y = w.take<double>((size_t)chunk * m->N, 256);
         *X = w.take<double>(extra, 256);
-        *work = w.take<double>(own ? 0 : records_err_work_doubles(m->N, chunk), 256);
+        *work = w.take<double>(own ? 0 : vi_forms_work_doubles(m->N, 1, chunk), 256);
         if (own) *work = nullptr;
     });
 }
@@ -3047,14 +2525,14 @@ extern "C" int vi_eval_track_err_f64(vi_model* m, int64_t Q, const double* d_lat
         int rc = vi_basis_f64(m, qc, d_lat + q0, d_lon + q0, d_alt + q0, Y, 1, qc);
         if (rc == VI_OK && F > 0) rc = mask_basis(m, qc, m->d_mask + q0, Y);
         if (rc != VI_OK) return rc;
-        return records_err(m, qc, Y, d_rec + q0, d_w ? d_w + q0 : nullptr, R, d_dC, d_out + q0, work);
+        return vi_records_err(m, qc, Y, d_rec + q0, d_w ? d_w + q0 : nullptr, R, d_dC, d_out + q0, work);
     });
 }
 
 // Gradient covariances along a trajectory (include/vinterp.h).  The hull pass of vi_eval_track_f64 for all points, then per
 // chunk: the planar gradient basis of the chunk into the context workspace by the launcher of vi_eval_grad_basis_f64, as
 // vi_eval_grad_cov_f64 builds it - the same bits per point, the hull's NaN columns and the frame folded in -, and
-// vi_eval_records_gradcov_f64's routes on it.  At most 256 MB of gradient basis per chunk (gradcov_chunk);
+// vi_eval_records_gradcov_f64's routes on it.  At most 256 MB of gradient basis per chunk (vi_forms_chunk);
 // VINTERP_TRACK_GRADCOV_CHUNK: a smaller chunk (tests: several chunks at a small Q).  A chunk border inside a run of records
 // changes no bits: a point's bits do not depend on the other points.
 extern "C" int vi_eval_track_grad_cov_f64(vi_model* m, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt,
@@ -3073,25 +2551,21 @@ extern "C" int vi_eval_track_grad_cov_f64(vi_model* m, int64_t Q, const double* 
     VI_HIP(hipSetDevice(c->device));
     const int N = m->N;
     if (F > 0 && (rc = prepare_call(m, Q, d_lat, d_lon, d_alt, d_hull_eq, F, hull_tol, 0, nullptr)) != VI_OK) return rc;
-    int64_t chunk = gradcov_chunk(N);
-    if (const char* e = getenv("VINTERP_TRACK_GRADCOV_CHUNK")) { const long long v = atoll(e); if (v >= 1 && v < chunk) chunk = v; }
-    if (chunk > Q) chunk = Q;
+    const int64_t chunk = std::min(Q, test_chunk("VINTERP_TRACK_GRADCOV_CHUNK", vi_forms_chunk(N, 3), 1));
     const bool own = vi_eval_resident_gradcov_shape(N);
-    void* ws = nullptr;
-    rc = vi_ctx_workspace(c, ((size_t)3 * chunk * N + (own ? 0 : records_gradcov_work_doubles(N, chunk))) * sizeof(double), &ws);
+    double *G, *work;                                     // work: that of the library route, behind G without a gap
+    rc = ws_carve(c, [&](ws_carver& w) {
+        G = w.take<double>((size_t)3 * chunk * N);
+        work = w.take<double>(own ? 0 : vi_forms_work_doubles(N, 3, chunk), 8);
+        if (own) work = nullptr;
+    });
     if (rc != VI_OK) return rc;
-    double* G = (double*)ws;
-    double* work = own ? nullptr : G + 3 * chunk * N;
     EvalTimer timer(c);
     return for_chunks(Q, chunk, [&](int64_t q0, int64_t qc) -> int {
-        const unsigned char* d_mask = F > 0 ? m->d_mask + q0 : nullptr;
-        int rc = frame == VI_FRAME_ENU
-                     ? launch_grad_sph<GRAD_RESIDENT, true>(m, "vi_eval_track_grad_cov_f64", qc, d_lat + q0, d_lon + q0, d_alt + q0,
-                                                            nullptr, d_mask, G, 1, qc, 3 * qc)
-                     : launch_grad_sph<GRAD_RESIDENT, false>(m, "vi_eval_track_grad_cov_f64", qc, d_lat + q0, d_lon + q0, d_alt + q0,
-                                                             nullptr, d_mask, G, 1, qc, 3 * qc);
+        const int rc = launch_grad_resident(m, "vi_eval_track_grad_cov_f64", qc, d_lat + q0, d_lon + q0, d_alt + q0,
+                                            F > 0 ? m->d_mask + q0 : nullptr, frame, G);
         if (rc != VI_OK) return rc;
-        return records_gradcov(m, qc, G, d_rec + q0, d_w ? d_w + q0 : nullptr, R, d_dC, d_out + q0, Q, work);
+        return vi_records_gradcov(m, qc, G, d_rec + q0, d_w ? d_w + q0 : nullptr, R, d_dC, d_out + q0, Q, work);
     });
 }
 
@@ -3219,6 +2693,6 @@ extern "C" int vi_eval_slant_err_f64(vi_model* m, int64_t P, const double* d_a, 
         if (rc != VI_OK) return rc;
         if (pc < P && d_chord)
             VI_HIP(hipMemcpy2DAsync(d_chord + p0, P * row, s.chord, pc * row, pc * row, 2, hipMemcpyDeviceToDevice, c->stream));
-        return records_err(m, pc, Y, d_rec + p0, d_w ? d_w + p0 : nullptr, R, d_dC, d_out + p0, work);
+        return vi_records_err(m, pc, Y, d_rec + p0, d_w ? d_w + p0 : nullptr, R, d_dC, d_out + p0, work);
     });
 }

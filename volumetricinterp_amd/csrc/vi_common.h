@@ -76,6 +76,19 @@ struct vi_ctx {
 
 int vi_ctx_workspace(vi_ctx* ctx, size_t bytes, void** out);
 
+// records HIP events around the evaluation kernel launches of one evaluation call (see vi_eval_kernel_ms)
+struct EvalTimer {
+    vi_ctx* c;
+    explicit EvalTimer(vi_ctx* ctx) : c(ctx)
+    {
+        c->evk_valid = c->evk_enabled && hipEventRecord(c->evk0, c->stream) == hipSuccess;
+    }
+    ~EvalTimer()
+    {
+        if (c->evk_valid) c->evk_valid = hipEventRecord(c->evk1, c->stream) == hipSuccess;
+    }
+};
+
 // A grow-only device buffer (p, *have bytes) made to hold `need` bytes.  Growing drains the context's stream before the old
 // block is freed: a kernel of an earlier call may still be reading it.
 template <class T>

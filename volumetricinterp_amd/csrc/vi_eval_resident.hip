@@ -847,32 +847,57 @@ __global__ __launch_bounds__(ERR_WAVES * 64) void k_eval_resident_err(int N, int
     }
 }
 
-// points per workgroup of K2e and K2eg on `cols` columns: 256 x groups - S (up to 166 KB of covariance through L2) is staged
-// once per workgroup, against 22 us of matrix-core work per group of 256 points at N = 144.  VINTERP_K2E_GROUPS, read at every
-// launch: tests, experiments.
-int err_groups(int64_t cols)
+// ---- what the launches of K2e, K2eg, K2te, K2c and K2tc share on the host ----
+
+// f(integral_constant NB) at the block count NB = N / 16 rounded up of an order N <= 16 ERR_NBMAX (the callers' shape tests):
+// every kernel of the family is compiled at each of the nine
+template <class F>
+int at_block_count(int N, F&& f)
 {
-    int groups = (int)((cols >> 16) < 1 ? 1 : ((cols >> 16) > 8 ? 8 : (cols >> 16)));
-    if (const char* e = getenv("VINTERP_K2E_GROUPS")) { const int gr = atoi(e); if (gr >= 1 && gr <= 256) groups = gr; }
+    switch ((N + 15) / 16) {
+#define VI_NB(NB) \
+    case NB: return f(std::integral_constant<int, NB>{});
+        VI_NB(1) VI_NB(2) VI_NB(3) VI_NB(4) VI_NB(5) VI_NB(6) VI_NB(7) VI_NB(8)
+#undef VI_NB
+    default: return f(std::integral_constant<int, ERR_NBMAX>{});
+    }
+}
+
+// the bytes of S as err_stage lays it out at block count NB: NB (NB + 1) / 2 blocks of 4 k-steps x 64 lanes
+constexpr size_t staged_bytes(int NB) { return (size_t)(NB * (NB + 1) / 2) * 4 * 64 * sizeof(double); }
+
+// blocks of points per workgroup: `cols` columns >> shift, within [1, cap], unless the switch `name` - read at every launch:
+// tests, experiments - gives a count in [1, 256]
+int groups_switch(int64_t cols, int shift, int cap, const char* name)
+{
+    int groups = (int)((cols >> shift) < 1 ? 1 : ((cols >> shift) > cap ? cap : (cols >> shift)));
+    if (const char* e = getenv(name)) { const int gr = atoi(e); if (gr >= 1 && gr <= 256) groups = gr; }
     return groups;
 }
 
-template <int NB>
-int launch_eval_resident_err(vi_ctx* c, int N, int64_t Q, int64_t T, const double* d_Y, const double* d_dC, double* d_out,
-                             int* handled)
+// The timestep-major launch of K2e, K2eg and K2c: *npg groups of pts x groups columns, and *nblk workgroups - the groups rounded
+// up to the 8 XCDs, times the T timesteps.  false: more workgroups than a launch takes (the caller leaves the call unhandled).
+bool timestep_blocks(int64_t cols, int pts, int groups, int64_t T, int64_t* npg, int64_t* nblk)
 {
-    const size_t shm = (size_t)(NB * (NB + 1) / 2) * 4 * 64 * sizeof(double);
-    const int groups = err_groups(Q);
-    const int64_t npg = (Q + (int64_t)ERR_PTS * groups - 1) / ((int64_t)ERR_PTS * groups);
-    const int64_t nblk = ((npg + 7) / 8) * 8 * T;
-    if (nblk > 0x7fffffffLL) return VI_OK;
-    VI_HIP(hipFuncSetAttribute((const void*)k_eval_resident_err<NB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    hipLaunchKernelGGL(k_eval_resident_err<NB>, dim3((unsigned)nblk), dim3(ERR_WAVES * 64), shm, c->stream, N, Q, T, groups, npg,
-                       d_Y, d_dC, d_out);
+    *npg = (cols + (int64_t)pts * groups - 1) / ((int64_t)pts * groups);
+    *nblk = ((*npg + 7) / 8) * 8 * T;
+    return *nblk <= 0x7fffffffLL;
+}
+
+// One launch of a kernel of the family with shm bytes of dynamic LDS; *handled = 1 once it is on the stream
+template <class K, class... A>
+int launch_forms(vi_ctx* c, K kernel, int64_t nblk, int waves, size_t shm, int* handled, A... args)
+{
+    VI_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)nblk), dim3(waves * 64), shm, c->stream, args...);
     VI_HIP(hipGetLastError());
     *handled = 1;
     return VI_OK;
 }
+
+// points per workgroup of K2e and K2eg on `cols` columns: 256 x groups - S (up to 166 KB of covariance through L2) is staged
+// once per workgroup, against 22 us of matrix-core work per group of 256 points at N = 144.
+int err_groups(int64_t cols) { return groups_switch(cols, 16, 8, "VINTERP_K2E_GROUPS"); }
 
 // K2eg: K2e's form at ONE chosen point per column and timestep (vi_eval_resident_err_at_f64: the standard error at the peak
 // that K2p found).  The grid is (outer, L, inner), column m = o inner + i, and idx[t][m] = l selects point
@@ -938,24 +963,6 @@ __global__ __launch_bounds__(ERR_WAVES * 64) void k_eval_resident_err_at(int N, 
             }
         }
     }
-}
-
-template <int NB>
-int launch_eval_resident_err_at(vi_ctx* c, int N, int64_t outer, int64_t L, int64_t inner, int64_t T, const double* d_Y,
-                                const double* d_dC, const int32_t* d_idx, double* d_out, int* handled)
-{
-    const size_t shm = (size_t)(NB * (NB + 1) / 2) * 4 * 64 * sizeof(double);
-    const int64_t M = outer * inner;
-    const int groups = err_groups(M);
-    const int64_t npg = (M + (int64_t)ERR_PTS * groups - 1) / ((int64_t)ERR_PTS * groups);
-    const int64_t nblk = ((npg + 7) / 8) * 8 * T;
-    if (nblk > 0x7fffffffLL) return VI_OK;
-    VI_HIP(hipFuncSetAttribute((const void*)k_eval_resident_err_at<NB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    hipLaunchKernelGGL(k_eval_resident_err_at<NB>, dim3((unsigned)nblk), dim3(ERR_WAVES * 64), shm, c->stream, N, M * L, L, inner,
-                       M, T, groups, npg, d_Y, d_dC, d_idx, d_out);
-    VI_HIP(hipGetLastError());
-    *handled = 1;
-    return VI_OK;
 }
 
 // The run walk K2te and K2tc share.  A workgroup owns RUN_PTS consecutive columns and walks the RUNS of equal rec inside them:
@@ -1075,25 +1082,6 @@ __global__ __launch_bounds__(ERR_WAVES * 64) void k_eval_records_err(int N, int6
     }
 }
 
-template <int NB>
-int launch_eval_records_err(vi_ctx* c, int N, int64_t Q, const double* d_Y, const int32_t* d_rec, const double* d_w, int64_t R,
-                            const double* d_dC, double* d_out, int* handled)
-{
-    const size_t shm = ((size_t)(NB * (NB + 1) / 2) * 4 * 64 + ERR_PTS) * sizeof(double) + ERR_PTS * sizeof(int) + ERR_PTS / 8;
-    const int64_t nblk = (Q + ERR_PTS - 1) / ERR_PTS;
-    if (nblk > 0x7fffffffLL) return VI_OK;
-    const int rc = with_flag(d_w != nullptr, [&](auto interp) -> int {
-        VI_HIP(hipFuncSetAttribute((const void*)k_eval_records_err<NB, interp>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)shm));
-        hipLaunchKernelGGL((k_eval_records_err<NB, interp>), dim3((unsigned)nblk), dim3(ERR_WAVES * 64), shm, c->stream, N, Q,
-                           d_Y, d_rec, d_w, (int)R, d_dC, d_out);
-        VI_HIP(hipGetLastError());
-        return VI_OK;
-    });
-    if (rc == VI_OK) *handled = 1;
-    return rc;
-}
-
 }  // namespace
 
 // whether K2te takes this call: K2e's shapes - N <= 144, Q even, Y / out 16-byte aligned - unless VINTERP_EVAL_RESIDENT=blas
@@ -1109,17 +1097,16 @@ int vi_eval_records_err_mfma(vi_ctx* c, int N, int64_t Q, const double* d_Y, con
 {
     *handled = 0;
     if (!vi_eval_records_err_shape(N, Q, d_Y, d_out)) return VI_OK;
-    switch ((N + 15) / 16) {
-    case 1: return launch_eval_records_err<1>(c, N, Q, d_Y, d_rec, d_w, R, d_dC, d_out, handled);
-    case 2: return launch_eval_records_err<2>(c, N, Q, d_Y, d_rec, d_w, R, d_dC, d_out, handled);
-    case 3: return launch_eval_records_err<3>(c, N, Q, d_Y, d_rec, d_w, R, d_dC, d_out, handled);
-    case 4: return launch_eval_records_err<4>(c, N, Q, d_Y, d_rec, d_w, R, d_dC, d_out, handled);
-    case 5: return launch_eval_records_err<5>(c, N, Q, d_Y, d_rec, d_w, R, d_dC, d_out, handled);
-    case 6: return launch_eval_records_err<6>(c, N, Q, d_Y, d_rec, d_w, R, d_dC, d_out, handled);
-    case 7: return launch_eval_records_err<7>(c, N, Q, d_Y, d_rec, d_w, R, d_dC, d_out, handled);
-    case 8: return launch_eval_records_err<8>(c, N, Q, d_Y, d_rec, d_w, R, d_dC, d_out, handled);
-    default: return launch_eval_records_err<9>(c, N, Q, d_Y, d_rec, d_w, R, d_dC, d_out, handled);
-    }
+    const int64_t nblk = (Q + ERR_PTS - 1) / ERR_PTS;
+    if (nblk > 0x7fffffffLL) return VI_OK;
+    return at_block_count(N, [&](auto nb) -> int {
+        // S, a first form per column, the block's rec and the mask of its run starts
+        const size_t shm = staged_bytes(nb) + ERR_PTS * sizeof(double) + ERR_PTS * sizeof(int) + ERR_PTS / 8;
+        return with_flag(d_w != nullptr, [&](auto interp) -> int {
+            return launch_forms(c, k_eval_records_err<nb, interp>, nblk, ERR_WAVES, shm, handled, N, Q, d_Y, d_rec, d_w, (int)R,
+                                d_dC, d_out);
+        });
+    });
 }
 
 // out[t*Q + q] = sqrt(sum_ik Y[i*Q + q] dC[t*N*N + i*N + k] Y[k*Q + q]) by K2e; *handled = 0 when the shape is not the kernel's
@@ -1128,19 +1115,14 @@ int vi_eval_resident_err_mfma(vi_ctx* c, int N, int64_t Q, int64_t T, const doub
                               int* handled)
 {
     *handled = 0;
-    if (!use_own_kernel()) return VI_OK;
-    if (N < 1 || N > 16 * ERR_NBMAX || (Q & 1) != 0 || (((uintptr_t)d_Y | (uintptr_t)d_out) & 15) != 0) return VI_OK;
-    switch ((N + 15) / 16) {
-    case 1: return launch_eval_resident_err<1>(c, N, Q, T, d_Y, d_dC, d_out, handled);
-    case 2: return launch_eval_resident_err<2>(c, N, Q, T, d_Y, d_dC, d_out, handled);
-    case 3: return launch_eval_resident_err<3>(c, N, Q, T, d_Y, d_dC, d_out, handled);
-    case 4: return launch_eval_resident_err<4>(c, N, Q, T, d_Y, d_dC, d_out, handled);
-    case 5: return launch_eval_resident_err<5>(c, N, Q, T, d_Y, d_dC, d_out, handled);
-    case 6: return launch_eval_resident_err<6>(c, N, Q, T, d_Y, d_dC, d_out, handled);
-    case 7: return launch_eval_resident_err<7>(c, N, Q, T, d_Y, d_dC, d_out, handled);
-    case 8: return launch_eval_resident_err<8>(c, N, Q, T, d_Y, d_dC, d_out, handled);
-    default: return launch_eval_resident_err<9>(c, N, Q, T, d_Y, d_dC, d_out, handled);
-    }
+    if (!vi_eval_records_err_shape(N, Q, d_Y, d_out)) return VI_OK;
+    const int groups = err_groups(Q);
+    int64_t npg, nblk;
+    if (!timestep_blocks(Q, ERR_PTS, groups, T, &npg, &nblk)) return VI_OK;
+    return at_block_count(N, [&](auto nb) -> int {
+        return launch_forms(c, k_eval_resident_err<nb>, nblk, ERR_WAVES, staged_bytes(nb), handled, N, Q, T, groups, npg, d_Y,
+                            d_dC, d_out);
+    });
 }
 
 // out[t*M + m] of vi_eval_resident_err_at_f64 by K2eg; *handled = 0 when the order is not the kernel's (N > 144) or with
@@ -1150,17 +1132,14 @@ int vi_eval_resident_err_at_mfma(vi_ctx* c, int N, int64_t outer, int64_t L, int
 {
     *handled = 0;
     if (!use_own_kernel() || N < 1 || N > 16 * ERR_NBMAX) return VI_OK;
-    switch ((N + 15) / 16) {
-    case 1: return launch_eval_resident_err_at<1>(c, N, outer, L, inner, T, d_Y, d_dC, d_idx, d_out, handled);
-    case 2: return launch_eval_resident_err_at<2>(c, N, outer, L, inner, T, d_Y, d_dC, d_idx, d_out, handled);
-    case 3: return launch_eval_resident_err_at<3>(c, N, outer, L, inner, T, d_Y, d_dC, d_idx, d_out, handled);
-    case 4: return launch_eval_resident_err_at<4>(c, N, outer, L, inner, T, d_Y, d_dC, d_idx, d_out, handled);
-    case 5: return launch_eval_resident_err_at<5>(c, N, outer, L, inner, T, d_Y, d_dC, d_idx, d_out, handled);
-    case 6: return launch_eval_resident_err_at<6>(c, N, outer, L, inner, T, d_Y, d_dC, d_idx, d_out, handled);
-    case 7: return launch_eval_resident_err_at<7>(c, N, outer, L, inner, T, d_Y, d_dC, d_idx, d_out, handled);
-    case 8: return launch_eval_resident_err_at<8>(c, N, outer, L, inner, T, d_Y, d_dC, d_idx, d_out, handled);
-    default: return launch_eval_resident_err_at<9>(c, N, outer, L, inner, T, d_Y, d_dC, d_idx, d_out, handled);
-    }
+    const int64_t M = outer * inner;
+    const int groups = err_groups(M);
+    int64_t npg, nblk;
+    if (!timestep_blocks(M, ERR_PTS, groups, T, &npg, &nblk)) return VI_OK;
+    return at_block_count(N, [&](auto nb) -> int {
+        return launch_forms(c, k_eval_resident_err_at<nb>, nblk, ERR_WAVES, staged_bytes(nb), handled, N, M * L, L, inner, M, T,
+                            groups, npg, d_Y, d_dC, d_idx, d_out);
+    });
 }
 
 // K2c: gradient-covariance maps of many timesteps on the resident GRADIENT basis of the grid (vi_eval_grad_basis_f64,
@@ -1298,26 +1277,10 @@ __global__ __launch_bounds__(COV_WAVES * 64) void k_eval_resident_gradcov(int N,
     }
 }
 
-template <int NB>
-int launch_eval_resident_gradcov(vi_ctx* c, int N, int64_t Q, int64_t T, const double* d_G, const double* d_dC, double* d_out,
-                                 int64_t ldo, int* handled)
-{
-    const size_t shm = (size_t)(NB * (NB + 1) / 2) * 4 * 64 * sizeof(double);
-    // points per workgroup: 64 x groups, by the size of Q as in K2e and up to K2e's 2048 - S (up to 166 KB of covariance through
-    // L2, by 4 waves) is staged once per workgroup, against 17 us of matrix-core work per group of 64 points at N = 144, and
-    // no second workgroup fits the CU to hide it: 42.1 ms at 8 groups, 36.8 at 32, 35.9 at 64 (128^3 x 16 timesteps)
-    int groups = (int)((Q >> 14) < 1 ? 1 : ((Q >> 14) > 32 ? 32 : (Q >> 14)));
-    if (const char* e = getenv("VINTERP_K2C_GROUPS")) { const int gr = atoi(e); if (gr >= 1 && gr <= 256) groups = gr; }  // tests, experiments
-    const int64_t npg = (Q + (int64_t)COV_PTS * groups - 1) / ((int64_t)COV_PTS * groups);
-    const int64_t nblk = ((npg + 7) / 8) * 8 * T;
-    if (nblk > 0x7fffffffLL) return VI_OK;
-    VI_HIP(hipFuncSetAttribute((const void*)k_eval_resident_gradcov<NB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    hipLaunchKernelGGL(k_eval_resident_gradcov<NB>, dim3((unsigned)nblk), dim3(COV_WAVES * 64), shm, c->stream, N, Q, T, groups,
-                       npg, ldo, d_G, d_dC, d_out);
-    VI_HIP(hipGetLastError());
-    *handled = 1;
-    return VI_OK;
-}
+// points per workgroup of K2c: 64 x groups, by the size of Q as in K2e and up to K2e's 2048 - S (up to 166 KB of covariance
+// through L2, by 4 waves) is staged once per workgroup, against 17 us of matrix-core work per group of 64 points at N = 144,
+// and no second workgroup fits the CU to hide it: 42.1 ms at 8 groups, 36.8 at 32, 35.9 at 64 (128^3 x 16 timesteps)
+int gradcov_groups(int64_t Q) { return groups_switch(Q, 14, 32, "VINTERP_K2C_GROUPS"); }
 
 // K2tc: K2c with the covariance chosen per COLUMN (vi_eval_records_gradcov_f64: every point of a track has its own record), as
 // K2te is to K2e.  With U_r(q)[k] the six packed entries of g_c^T 1/2 (dC_r + dC_r^T) g_d at point q:
@@ -1418,33 +1381,8 @@ __global__ __launch_bounds__(COV_WAVES * 64) void k_eval_records_gradcov(int N, 
 }
 
 // blocks of 256 points per workgroup of K2tc: S stays staged across the block borders of a workgroup where the record does not
-// change.  VINTERP_K2TC_GROUPS: tests, experiments.
-int records_gradcov_groups(int64_t Q)
-{
-    int groups = (int)((Q >> 16) < 1 ? 1 : ((Q >> 16) > 8 ? 8 : (Q >> 16)));
-    if (const char* e = getenv("VINTERP_K2TC_GROUPS")) { const int gr = atoi(e); if (gr >= 1 && gr <= 256) groups = gr; }
-    return groups;
-}
-
-template <int NB>
-int launch_eval_records_gradcov(vi_ctx* c, int N, int64_t Q, const double* d_G, const int32_t* d_rec, const double* d_w, int64_t R,
-                                const double* d_dC, double* d_out, int64_t ldo, int* handled)
-{
-    const size_t shm = ((size_t)(NB * (NB + 1) / 2) * 4 * 64 + 6 * RUN_PTS) * sizeof(double) + RUN_PTS * sizeof(int) + RUN_PTS / 8;
-    const int groups = records_gradcov_groups(Q);
-    const int64_t nblk = (Q + (int64_t)RUN_PTS * groups - 1) / ((int64_t)RUN_PTS * groups);
-    if (nblk > 0x7fffffffLL) return VI_OK;
-    const int rc = with_flag(d_w != nullptr, [&](auto interp) -> int {
-        VI_HIP(hipFuncSetAttribute((const void*)k_eval_records_gradcov<NB, interp>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)shm));
-        hipLaunchKernelGGL((k_eval_records_gradcov<NB, interp>), dim3((unsigned)nblk), dim3(COV_WAVES * 64), shm, c->stream, N, Q,
-                           groups, ldo, d_G, d_rec, d_w, (int)R, d_dC, d_out);
-        VI_HIP(hipGetLastError());
-        return VI_OK;
-    });
-    if (rc == VI_OK) *handled = 1;
-    return rc;
-}
+// change.
+int records_gradcov_groups(int64_t Q) { return groups_switch(Q, 16, 8, "VINTERP_K2TC_GROUPS"); }
 
 }  // namespace
 
@@ -1455,17 +1393,17 @@ int vi_eval_records_gradcov_mfma(vi_ctx* c, int N, int64_t Q, const double* d_G,
 {
     *handled = 0;
     if (!vi_eval_resident_gradcov_shape(N)) return VI_OK;
-    switch ((N + 15) / 16) {
-    case 1: return launch_eval_records_gradcov<1>(c, N, Q, d_G, d_rec, d_w, R, d_dC, d_out, ldo, handled);
-    case 2: return launch_eval_records_gradcov<2>(c, N, Q, d_G, d_rec, d_w, R, d_dC, d_out, ldo, handled);
-    case 3: return launch_eval_records_gradcov<3>(c, N, Q, d_G, d_rec, d_w, R, d_dC, d_out, ldo, handled);
-    case 4: return launch_eval_records_gradcov<4>(c, N, Q, d_G, d_rec, d_w, R, d_dC, d_out, ldo, handled);
-    case 5: return launch_eval_records_gradcov<5>(c, N, Q, d_G, d_rec, d_w, R, d_dC, d_out, ldo, handled);
-    case 6: return launch_eval_records_gradcov<6>(c, N, Q, d_G, d_rec, d_w, R, d_dC, d_out, ldo, handled);
-    case 7: return launch_eval_records_gradcov<7>(c, N, Q, d_G, d_rec, d_w, R, d_dC, d_out, ldo, handled);
-    case 8: return launch_eval_records_gradcov<8>(c, N, Q, d_G, d_rec, d_w, R, d_dC, d_out, ldo, handled);
-    default: return launch_eval_records_gradcov<9>(c, N, Q, d_G, d_rec, d_w, R, d_dC, d_out, ldo, handled);
-    }
+    const int groups = records_gradcov_groups(Q);
+    const int64_t nblk = (Q + (int64_t)RUN_PTS * groups - 1) / ((int64_t)RUN_PTS * groups);
+    if (nblk > 0x7fffffffLL) return VI_OK;
+    return at_block_count(N, [&](auto nb) -> int {
+        // S, six first entries per column, the block's rec and the mask of its run starts
+        const size_t shm = staged_bytes(nb) + 6 * RUN_PTS * sizeof(double) + RUN_PTS * sizeof(int) + RUN_PTS / 8;
+        return with_flag(d_w != nullptr, [&](auto interp) -> int {
+            return launch_forms(c, k_eval_records_gradcov<nb, interp>, nblk, COV_WAVES, shm, handled, N, Q, groups, ldo, d_G, d_rec,
+                                d_w, (int)R, d_dC, d_out);
+        });
+    });
 }
 
 // whether K2c takes gradient bases of N rows at all (what a caller that carves a workspace for the library path asks first)
@@ -1478,15 +1416,11 @@ int vi_eval_resident_gradcov_mfma(vi_ctx* c, int N, int64_t Q, int64_t T, const 
 {
     *handled = 0;
     if (!vi_eval_resident_gradcov_shape(N)) return VI_OK;
-    switch ((N + 15) / 16) {
-    case 1: return launch_eval_resident_gradcov<1>(c, N, Q, T, d_G, d_dC, d_out, ldo, handled);
-    case 2: return launch_eval_resident_gradcov<2>(c, N, Q, T, d_G, d_dC, d_out, ldo, handled);
-    case 3: return launch_eval_resident_gradcov<3>(c, N, Q, T, d_G, d_dC, d_out, ldo, handled);
-    case 4: return launch_eval_resident_gradcov<4>(c, N, Q, T, d_G, d_dC, d_out, ldo, handled);
-    case 5: return launch_eval_resident_gradcov<5>(c, N, Q, T, d_G, d_dC, d_out, ldo, handled);
-    case 6: return launch_eval_resident_gradcov<6>(c, N, Q, T, d_G, d_dC, d_out, ldo, handled);
-    case 7: return launch_eval_resident_gradcov<7>(c, N, Q, T, d_G, d_dC, d_out, ldo, handled);
-    case 8: return launch_eval_resident_gradcov<8>(c, N, Q, T, d_G, d_dC, d_out, ldo, handled);
-    default: return launch_eval_resident_gradcov<9>(c, N, Q, T, d_G, d_dC, d_out, ldo, handled);
-    }
+    const int groups = gradcov_groups(Q);
+    int64_t npg, nblk;
+    if (!timestep_blocks(Q, COV_PTS, groups, T, &npg, &nblk)) return VI_OK;
+    return at_block_count(N, [&](auto nb) -> int {
+        return launch_forms(c, k_eval_resident_gradcov<nb>, nblk, COV_WAVES, staged_bytes(nb), handled, N, Q, T, groups, npg, ldo,
+                            d_G, d_dC, d_out);
+    });
 }

@@ -58,3 +58,15 @@ int vi_eval_resident_peak_mfma(vi_ctx* c, int N, int64_t outer, int64_t L, int64
 int vi_peak_columns(vi_ctx* c, int64_t outer, int64_t L, int64_t inner, int64_t T, int kind, const double* d_in, double* d_val,
                     int32_t* d_idx);
 int vi_reduce_basis(vi_ctx* c, int N, int64_t outer, int64_t L, int64_t inner, const double* d_Y, const double* d_w, double* d_Yr);
+
+// ---- forms y^T dC y and g_c^T dC g_d on matrices already built (vi_resident.hip), for the entries of vi_basis.hip that build
+//      the matrix of a chunk themselves; `components`: 1 (a basis column per point) or 3 (a gradient basis) ----
+int64_t vi_forms_chunk(int N, int components);                            // points per chunk of the library route, unclipped
+size_t vi_forms_work_doubles(int N, int components, int64_t chunk);       // work space of the two records routines below
+int vi_forms_tile(vi_ctx* c, int N, int64_t P, const double* A, const double* d_dC, double* B, double* d_out);
+int vi_records_err(vi_model* m, int64_t Q, const double* d_Y, const int32_t* d_rec, const double* d_w, int64_t R,
+                   const double* d_dC, double* d_out, double* work);
+int vi_records_gradcov(vi_model* m, int64_t Q, const double* d_G, const int32_t* d_rec, const double* d_w, int64_t R,
+                       const double* d_dC, double* d_out, int64_t ldo, double* work);
+int vi_resident_gradcov(vi_model* m, int64_t Q, int64_t T, const double* d_G, const double* d_dC, double* d_out, int64_t ldo,
+                        double* AB);
