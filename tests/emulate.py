@@ -1,4 +1,4 @@
-"""Test-only NumPy emulation of the device recurrence in csrc/vi_basis.hip (sph_point), driven by the
+"""Test-only NumPy emulation of the device recurrence in csrc/vi_sph_device.h (sph_point), driven by the
 same host tables (Model.device_tables()).  Lets the CPU suite validate the tables without a GPU.
 Not part of the product path."""
 import numpy as np

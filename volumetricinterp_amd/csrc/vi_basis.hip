@@ -3,72 +3,18 @@
 // (reference: volumetricinterp/models/radbasfun.py:83-112), as
 //   K1  k_basis_*  : materialise A (used by the fit),
 //   K2  k_eval_*   : fused evaluation  out[t,q] = sum_n A[q,n] C[t,n]  (Estimate.__call__,
-//                    estimate.py:110-123) that never writes A, with the convex-hull test fused in.
+//                    estimate.py:110-123) that never writes A, with the convex-hull test fused in: a unit of its own,
+//                    vi_eval.hip; here are its hull pass and call preparation and its kin along tracks and rays.
 // One thread per point; lat/lon/alt are read as coalesced SoA streams; every table the 64 lanes of
 // a wave share (recurrence coefficients, coefficient tiles) is addressed wave-uniformly so it is
 // served by the scalar data path / LDS broadcast and never costs per-lane HBM traffic.
-#include "vi_common.h"
-#include "vi_solver.h"
-#include "vi_sph_device.h"
+#include "vi_chain_device.h"
+#include "vi_eval_host.h"
 
 #include <algorithm>
 #include <cstdlib>
 
 namespace {
-
-// The shared per-point engine.  Sink::consume(l, cur[], cm[], sm[]) is called once per degree l with
-// cur[m] = (normalised) P_{nu_l}^m(cos theta), m = 0..l.
-template <int LCAP, int KCAP, class Sink>
-__device__ __forceinline__ void sph_point(const SphDev& M, const Geom& g, Sink& sink)
-{
-    const int maxl = M.maxl;
-    // azimuthal factors cos(m phi), sin(m phi) by angle addition (sphharmlag.py:278-281 takes them of |m| phi)
-    double cm[LCAP], sm[LCAP];
-    cm[0] = 1.0;
-    sm[0] = 0.0;
-#pragma unroll
-    for (int m = 1; m < LCAP; ++m) {
-        cm[m] = cm[m - 1] * g.cphi - sm[m - 1] * g.sphi;
-        sm[m] = sm[m - 1] * g.cphi + cm[m - 1] * g.sphi;
-    }
-    const double x = g.x;
-    const double zz = 0.5 * (1.0 - x);
-    const int ng = M.ngroups;
-    for (int gi = 0; gi < ng; ++gi) {
-        const SphGroupDev G = M.groups[gi];
-        const bool intseed = (G.nterms == 0);
-        double cur[LCAP], prev[LCAP];
-#pragma unroll
-        for (int m = 0; m < LCAP; ++m) { cur[m] = 0.0; prev[m] = 0.0; }
-        double pmm = 1.0;       // (-1)^m (2m-1)!! s^m
-        double spow = 1.0;      // s^m
-        const int nvmax = G.nvmax;
-        for (int j = 0; j <= nvmax; ++j) {
-            const double* __restrict__ cj = G.c + (size_t)j * maxl;
-#pragma unroll
-            for (int m = 0; m < LCAP; ++m) {
-                if (m < maxl) {
-                    if (j > m + 1) {
-                        const double nw = fma(x, cur[m], -(cj[m] * prev[m]));
-                        prev[m] = cur[m];
-                        cur[m] = nw;
-                    } else if (j == m) {
-                        if (m > 0) { pmm *= -(2.0 * m - 1.0) * g.s; spow *= g.s; }
-                        if (intseed) cur[m] = pmm;
-                        else cur[m] = G.pref[m] * spow * hyp_series(G.q + (size_t)m * G.nterms, G.nterms, zz);
-                    } else if (j == m + 1) {
-                        prev[m] = cur[m];
-                        if (intseed) cur[m] = x * (2.0 * m + 1.0) * cur[m];
-                        else cur[m] = G.pref[maxl + m] * spow *
-                                      hyp_series(G.q + (size_t)(maxl + m) * G.nterms, G.nterms, zz);
-                    }
-                }
-            }
-            const int l = G.pick[j];
-            if (l >= 0) sink.template consume<LCAP>(l, cur, cm, sm);
-        }
-    }
-}
 
 // ---------------------------------------------------------------------------------------------
 // K1: basis assembly.  A[p*ld_p + n*ld_n], n = k*maxl^2 + l(l+1) + m  (sphharmlag.py:79-99)
@@ -324,44 +270,6 @@ __global__ __launch_bounds__(BLOCK) void k_grad_sph(SphDev M, int64_t P, const d
         Gp[2 * ld_c] = sink.ap;
     }
 }
-
-// ---------------------------------------------------------------------------------------------
-// K2: fused evaluation for TT timesteps per pass.  Cp is the coefficient tile reordered to
-// [t][r = l(l+1)+m][k] and pre-multiplied by the per-(l,m) constant (see k_prep_coef).
-template <int KCAP, int TT>
-struct EvalSink {
-    const double* __restrict__ Cp;   // [TT][L2*maxk], wave-uniform reads
-    int maxk, NB;
-    double Lk[KCAP];
-    double acc[TT];
-    template <int LCAP>
-    __device__ __forceinline__ void consume(int l, const double* cur, const double* cm, const double* sm)
-    {
-        const int r0 = l * (l + 1);
-#pragma unroll
-        for (int m = 0; m < LCAP; ++m) {
-            if (m <= l) {
-                const double* __restrict__ cp = Cp + (size_t)(r0 + m) * maxk;
-                const double* __restrict__ cn = Cp + (size_t)(r0 - m) * maxk;
-                const double pc = cur[m] * cm[m];
-                const double ps = cur[m] * sm[m];
-#pragma unroll
-                for (int t = 0; t < TT; ++t) {
-                    double Sp = 0.0, Sm = 0.0;
-#pragma unroll
-                    for (int k = 0; k < KCAP; ++k) {
-                        if (k < maxk) {
-                            Sp = fma(cp[(size_t)t * NB + k], Lk[k], Sp);
-                            if (m > 0) Sm = fma(cn[(size_t)t * NB + k], Lk[k], Sm);
-                        }
-                    }
-                    acc[t] = fma(pc, Sp, acc[t]);
-                    if (m > 0) acc[t] = fma(ps, Sm, acc[t]);
-                }
-            }
-        }
-    }
-};
 
 // Convex-hull test (estimate.py:153-178 semantics: inside <=> max_f (n_f . x + d_f) <= tol), as a mask pass.
 // `hull` is the internal buffer built by k_prep_hull: [c0 (3 doubles, 1 pad)] [F x 4 fp64 facet equations]
@@ -777,116 +685,6 @@ __global__ __launch_bounds__(256) void k_prep_hull(int F, const double* __restri
     prep_hull_body(F, eq, hullbuf, (int)blockIdx.x, (int)gridDim.x);
 }
 
-template <int LCAP, int KCAP, int TT>
-__global__ __launch_bounds__(BLOCK) void k_eval_sph(SphDev M, int64_t Q, const double* __restrict__ lat,
-                                                    const double* __restrict__ lon, const double* __restrict__ alt,
-                                                    int tcount, const double* __restrict__ Cp,
-                                                    const unsigned char* __restrict__ mask, int F, double tol,
-                                                    double* __restrict__ out)
-{
-    const int64_t q = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    const int64_t qc = q < Q ? q : Q - 1;
-    const Geom g = sph_geom(M, lat[qc], lon[qc], alt[qc]);
-    bool in = true;
-    if (F > 0) {
-        in = mask[qc] != 0;
-        if (!__any(in && q < Q)) {            // whole wave outside the hull: skip the basis work
-            if (q < Q)
-                for (int t = 0; t < tcount; ++t) out[(int64_t)t * Q + q] = __builtin_nan("");
-            return;
-        }
-    }
-    EvalSink<KCAP, TT> sink;
-    sink.Cp = Cp;
-    sink.maxk = M.maxk;
-    sink.NB = M.N;
-    laguerre<KCAP>(M.maxk, g.z, sink.Lk);
-#pragma unroll
-    for (int t = 0; t < TT; ++t) sink.acc[t] = 0.0;
-    sph_point<LCAP, KCAP>(M, g, sink);
-    const double E = exp(-0.5 * g.z);
-    if (q < Q) {
-#pragma unroll
-        for (int t = 0; t < TT; ++t)
-            if (t < tcount) out[(int64_t)t * Q + q] = in ? E * sink.acc[t] : __builtin_nan("");
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// K2 fast path: exact template orders (L = MAXL, K = MAXK), one degree group.  Differences to the generic
-// kernel above, all aimed at keeping the fp64 VALU busy (the kernel is VALU-bound):
-//  * the recurrence table c[j][m] and the coefficient tile are staged in LDS once per workgroup and read as
-//    wave-uniform (broadcast) ds_read_b128 - no dependent scalar loads in the inner loop;
-//  * the triangular start-up (degrees j <= L) is unrolled at compile time, so the main degree loop has no
-//    branches: 2 fp64 ops per (degree, order);
-//  * the loop over l is unrolled, so each contraction knows l at compile time (no predication).
-template <int L, int K, int TT>
-struct FastEval {
-    const double* shC;      // LDS [TT][L*L*K] coefficient tile, [t][r = l(l+1)+m][k]
-    double Lk[K];
-    double acc[TT];
-    template <int l, typename CT>
-    __device__ __forceinline__ void consume(const CT* cur, const double* cm, const double* sm)
-    {
-        constexpr int r0 = l * (l + 1);
-        constexpr int NB = L * L * K;
-#pragma unroll
-        for (int m = 0; m <= l; ++m) {
-            const double pc = (double)cur[m] * cm[m];
-            const double ps = (double)cur[m] * sm[m];
-#pragma unroll
-            for (int t = 0; t < TT; ++t) {
-                const double* cp = shC + t * NB + (r0 + m) * K;
-                const double* cn = shC + t * NB + (r0 - m) * K;
-                double Sp = 0.0, Sm = 0.0;
-#pragma unroll
-                for (int k = 0; k < K; ++k) {
-                    Sp = fma(cp[k], Lk[k], Sp);
-                    if (m > 0) Sm = fma(cn[k], Lk[k], Sm);
-                }
-                acc[t] = fma(pc, Sp, acc[t]);
-                if (m > 0) acc[t] = fma(ps, Sm, acc[t]);
-            }
-        }
-    }
-};
-
-template <int L, int K, int TT, int l>
-struct ConsumeAt {
-    // consume degree l if its integer part equals j (start-up phase only: j <= L)
-    template <typename CT>
-    __device__ static __forceinline__ void run(FastEval<L, K, TT>& E, const int* nvl, int j, const CT* cur,
-                                               const double* cm, const double* sm)
-    {
-        if (nvl[l] == j) E.template consume<l>(cur, cm, sm);
-        if constexpr (l + 1 < L) ConsumeAt<L, K, TT, l + 1>::run(E, nvl, j, cur, cm, sm);
-    }
-};
-
-template <int L, int K, int TT, int l>
-struct MainSegments {
-    template <typename CT>
-    __device__ static __forceinline__ void run(FastEval<L, K, TT>& E, const CT* shc, const int* nvl, int& j, CT x,
-                                               CT* cur, CT* prev, const double* cm, const double* sm)
-    {
-        const int jend = nvl[l];
-        if (jend > L) {
-#pragma unroll 2
-            for (; j <= jend; ++j) {
-                const CT* cj = shc + j * L;
-#pragma unroll
-                for (int m = 0; m < L; ++m) {
-                    const CT nw = fma(x, cur[m], -(cj[m] * prev[m]));
-                    prev[m] = cur[m];
-                    cur[m] = nw;
-                }
-            }
-            E.template consume<l>(cur, cm, sm);
-        }
-        if constexpr (l + 1 < L) MainSegments<L, K, TT, l + 1>::run(E, shc, nvl, j, x, cur, prev, cm, sm);
-    }
-};
-
 // One pass of the chains of a point over the tile E.shC, for K2t (k_track_sph_fast below): E.acc[t] = sum_n basis_n(point) *
 // tile[t][n] without the factor exp(-z/2), t = 0 .. TT-1.  shc: the recurrence table [nj][L] in LDS, nvl[l]: the degree at which
 // chain segment l ends.  The contraction, the start-up's consumption and the main segments are the pieces k_eval_sph_fast runs
@@ -936,101 +734,11 @@ __device__ __forceinline__ void fast_chains(FastEval<L, K, TT>& E, const SphGrou
                 else cur[m] = (CT)(G.pref[L + m] * spow * hyp_series(G.q + (size_t)(L + m) * G.nterms, G.nterms, zz));
             }
         }
-        ConsumeAt<L, K, TT, 0>::run(E, nvl, j, cur, cm, sm);
+        ConsumeAt<L, FastEval<L, K, TT>, 0>::run(E, nvl, j, cur, cm, sm);
     }
     // ---- main: all chains in recurrence mode; one segment per degree l --------------------------------
     int j = L + 1;
-    MainSegments<L, K, TT, 0>::run(E, shc, nvl, j, x, cur, prev, cm, sm);
-}
-
-// CT = arithmetic type of the Legendre chains: double, or float for the fp32 variant of BASELINE configs[4]'s tolerance
-// sweep (seeds, trigonometric and Laguerre factors and the contraction with the coefficients stay fp64)
-template <int L, int K, int TT, typename CT>
-__global__ __launch_bounds__(BLOCK) void k_eval_sph_fast(SphDev M, int64_t Q, const double* __restrict__ lat,
-                                                         const double* __restrict__ lon, const double* __restrict__ alt,
-                                                         int tcount, const double* __restrict__ Cp,
-                                                         const unsigned char* __restrict__ mask, int F, double tol,
-                                                         double* __restrict__ out)
-{
-    extern __shared__ __align__(16) double sh[];
-    constexpr int NB = L * L * K;
-    const SphGroupDev G = M.groups[0];
-    const int nj = G.nvmax + 1;
-    CT* shc = reinterpret_cast<CT*>(sh);                // [nj][L] recurrence table in the chain's arithmetic type
-    double* shC = sh + ((nj * L + 1) & ~1);             // [TT][NB]
-    int* nvl = reinterpret_cast<int*>(shC + TT * NB);   // [L]
-    for (int i = threadIdx.x; i < nj * L; i += BLOCK) shc[i] = (CT)G.c[i];
-    for (int i = threadIdx.x; i < TT * NB; i += BLOCK) shC[i] = i < tcount * NB ? Cp[i] : 0.0;
-    for (int j = threadIdx.x; j < nj; j += BLOCK) {
-        const int l = G.pick[j];
-        if (l >= 0) nvl[l] = j;
-    }
-    __syncthreads();
-
-    const int64_t q = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    const int64_t qc = q < Q ? q : Q - 1;
-    const Geom g = sph_geom(M, lat[qc], lon[qc], alt[qc]);
-    bool in = true;
-    if (F > 0) {
-        in = mask[qc] != 0;
-        if (!__any(in && q < Q)) {
-            if (q < Q)
-                for (int t = 0; t < tcount; ++t) out[(int64_t)t * Q + q] = __builtin_nan("");
-            return;
-        }
-    }
-    FastEval<L, K, TT> E;
-    E.shC = shC;
-    laguerre<K>(K, g.z, E.Lk);
-#pragma unroll
-    for (int t = 0; t < TT; ++t) E.acc[t] = 0.0;
-    double cm[L], sm[L];
-    cm[0] = 1.0;
-    sm[0] = 0.0;
-#pragma unroll
-    for (int m = 1; m < L; ++m) {
-        cm[m] = cm[m - 1] * g.cphi - sm[m - 1] * g.sphi;
-        sm[m] = sm[m - 1] * g.cphi + cm[m - 1] * g.sphi;
-    }
-    const CT x = (CT)g.x;
-    const double zz = 0.5 * (1.0 - g.x);
-    const bool intseed = (G.nterms == 0);
-    CT cur[L], prev[L];
-#pragma unroll
-    for (int m = 0; m < L; ++m) { cur[m] = (CT)0.0; prev[m] = (CT)0.0; }
-    double pmm = 1.0, spow = 1.0;
-    // ---- start-up: degrees j = 0 .. L, compile-time triangular structure ------------------------------
-#pragma unroll
-    for (int j = 0; j <= L; ++j) {
-#pragma unroll
-        for (int m = 0; m < L; ++m) {
-            if (j > m + 1) {
-                if (j < nj) {
-                    const CT nw = fma(x, cur[m], -(shc[j * L + m] * prev[m]));
-                    prev[m] = cur[m];
-                    cur[m] = nw;
-                }
-            } else if (j == m) {
-                if (m > 0) { pmm *= -(2.0 * m - 1.0) * g.s; spow *= g.s; }
-                if (intseed) cur[m] = (CT)pmm;
-                else cur[m] = (CT)(G.pref[m] * spow * hyp_series(G.q + (size_t)m * G.nterms, G.nterms, zz));
-            } else if (j == m + 1) {
-                prev[m] = cur[m];
-                if (intseed) cur[m] = (CT)(g.x * (2.0 * m + 1.0) * pmm);
-                else cur[m] = (CT)(G.pref[L + m] * spow * hyp_series(G.q + (size_t)(L + m) * G.nterms, G.nterms, zz));
-            }
-        }
-        ConsumeAt<L, K, TT, 0>::run(E, nvl, j, cur, cm, sm);
-    }
-    // ---- main: all chains in recurrence mode; one segment per degree l --------------------------------
-    int j = L + 1;
-    MainSegments<L, K, TT, 0>::run(E, shc, nvl, j, x, cur, prev, cm, sm);
-    const double Ez = exp(-0.5 * g.z);
-    if (q < Q) {
-#pragma unroll
-        for (int t = 0; t < TT; ++t)
-            if (t < tcount) out[(int64_t)t * Q + q] = in ? Ez * E.acc[t] : __builtin_nan("");
-    }
+    MainSegments<L, FastEval<L, K, TT>, 0>::run(E, shc, nvl, j, x, cur, prev, cm, sm);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1141,19 +849,12 @@ __global__ __launch_bounds__(BLOCK) void k_track_sph(SphDev M, int64_t Q, const 
         return;
     }
     const Geom g = sph_geom(M, lat[qc], lon[qc], alt[qc]);
-    EvalSink<KCAP, TT> sink;
-    sink.Cp = Cp + (int64_t)(live ? r : 0) * M.N;      // (a live lane exists: row 0 does)
-    sink.maxk = M.maxk;
-    sink.NB = M.N;
-    laguerre<KCAP>(M.maxk, g.z, sink.Lk);
-#pragma unroll
-    for (int t = 0; t < TT; ++t) sink.acc[t] = 0.0;
-    sph_point<LCAP, KCAP>(M, g, sink);
-    const double E = exp(-0.5 * g.z);
-    double val = E * sink.acc[0];
+    double v[TT];
+    eval_point<LCAP, KCAP, TT>(M, g, Cp + (int64_t)(live ? r : 0) * M.N, v);      // (a live lane exists: row 0 does)
+    double val = v[0];
     if (INTERP) {
         const double w = wgt[qc];
-        val = (1.0 - w) * val + w * (E * sink.acc[TT - 1]);
+        val = (1.0 - w) * val + w * v[TT - 1];
     }
     if (q < Q) out[q] = live ? val : __builtin_nan("");
 }
@@ -1269,33 +970,6 @@ __global__ __launch_bounds__(TRACK_BLOCK) void k_track_grad_sph(SphDev M, int64_
 // The unit is a WAVE per ray.  The model coordinates are functions of ECEF only (sph_geom_ecef), so the nodes need no geodetic
 // step, and every node of a ray shares the ray's time: the wave needs one coefficient row - in interpolation mode the blend
 // (1 - w) Cp[r] + w Cp[r + 1] of two prepared rows, the preparation being linear - and no window.
-
-// sph_geom (vi_sph_device.h) from its second line on: the model coordinates of an ECEF point.  A function of its own - sph_geom
-// is inlined into the benchmarked kernels and stays as it is.
-__device__ __forceinline__ Geom sph_geom_ecef(const SphDev& M, double X, double Y, double Z)
-{
-    Geom g;
-    g.X = X;
-    g.Y = Y;
-    g.Z = Z;
-    const double kd = M.kx * X + M.ky * Y;
-    const double omc = 1.0 - M.rc;
-    const double Rx = X * M.rc + (M.ky * Z) * M.rs + M.kx * kd * omc;
-    const double Ry = Y * M.rc + (-M.kx * Z) * M.rs + M.ky * kd * omc;
-    const double Rz = Z * M.rc + (M.kx * Y - M.ky * X) * M.rs;
-    const double rho2 = Rx * Rx + Ry * Ry;
-    const double r = sqrt(rho2 + Rz * Rz);
-    g.x = Rz / r;
-    g.s = sqrt(1.0 - g.x * g.x);
-    const double rho = sqrt(rho2);
-    const bool pole = !(rho > 0.0);
-    g.cphi = pole ? 1.0 : Rx / rho;
-    g.sphi = pole ? 0.0 : Ry / rho;
-    g.z = 100.0 * (r / M.RE - 1.0);
-    g.Rx = Rx;
-    g.Ry = Ry;
-    return g;
-}
 
 constexpr int SLANT_WAVES = 4;      // rays (waves) of a workgroup at most; they share the recurrence table of the fast kernel
 
@@ -1492,17 +1166,10 @@ __global__ __launch_bounds__(BLOCK) void k_slant_sph(SphDev M, int64_t P, const 
         double X, Y, Z;
         slant_node(y, xq[on ? i : 0], X, Y, Z);
         const Geom g = sph_geom_ecef(M, X, Y, Z);
-        EvalSink<KCAP, TT> sink;
-        sink.Cp = Cp + (int64_t)y.r * M.N;
-        sink.maxk = M.maxk;
-        sink.NB = M.N;
-        laguerre<KCAP>(M.maxk, g.z, sink.Lk);
-#pragma unroll
-        for (int t = 0; t < TT; ++t) sink.acc[t] = 0.0;
-        sph_point<LCAP, KCAP>(M, g, sink);
-        const double E = exp(-0.5 * g.z);
-        double val = E * sink.acc[0];
-        if (INTERP) val = (1.0 - w) * val + w * (E * sink.acc[TT - 1]);
+        double v[TT];
+        eval_point<LCAP, KCAP, TT>(M, g, Cp + (int64_t)y.r * M.N, v);
+        double val = v[0];
+        if (INTERP) val = (1.0 - w) * val + w * v[TT - 1];
         const double term = wq[on ? i : 0] * val;
         acc += on ? term : 0.0;
     }
@@ -1723,44 +1390,6 @@ __global__ __launch_bounds__(BLOCK) void k_basis_rbf(RbfDev M, int64_t P, const 
     }
 }
 
-template <int TT>
-__global__ __launch_bounds__(BLOCK) void k_eval_rbf(RbfDev M, int64_t Q, const double* __restrict__ lat,
-                                                    const double* __restrict__ lon, const double* __restrict__ alt,
-                                                    int tcount, const double* __restrict__ C,
-                                                    const unsigned char* __restrict__ mask, int F, double tol,
-                                                    double* __restrict__ out)
-{
-    const int64_t q = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    const int64_t qc = q < Q ? q : Q - 1;
-    double X, Y, Z;
-    geodetic2ecef(lat[qc], lon[qc], alt[qc], X, Y, Z);
-    bool in = true;
-    if (F > 0) {
-        in = mask[qc] != 0;
-        if (!__any(in && q < Q)) {
-            if (q < Q)
-                for (int t = 0; t < tcount; ++t) out[(int64_t)t * Q + q] = __builtin_nan("");
-            return;
-        }
-    }
-    double acc[TT];
-#pragma unroll
-    for (int t = 0; t < TT; ++t) acc[t] = 0.0;
-    const double* __restrict__ c = M.centers;
-    for (int n = 0; n < M.N; ++n) {
-        const double dx = X - c[3 * n], dy = Y - c[3 * n + 1], dz = Z - c[3 * n + 2];
-        const double e = exp(-(dx * dx + dy * dy + dz * dz) * M.inv_eps2);
-#pragma unroll
-        for (int t = 0; t < TT; ++t)
-            if (t < tcount) acc[t] = fma(e, C[(size_t)t * M.N + n], acc[t]);
-    }
-    if (q < Q) {
-#pragma unroll
-        for (int t = 0; t < TT; ++t)
-            if (t < tcount) out[(int64_t)t * Q + q] = in ? acc[t] : __builtin_nan("");
-    }
-}
-
 // K2t for the RBF model, per lane: the lane's own coefficient row, or its two rows, from global memory (see k_track_sph)
 template <bool INTERP>
 __global__ __launch_bounds__(BLOCK) void k_track_rbf(RbfDev M, int64_t Q, const double* __restrict__ lat,
@@ -1779,15 +1408,8 @@ __global__ __launch_bounds__(BLOCK) void k_track_rbf(RbfDev M, int64_t Q, const 
     }
     double X, Y, Z;
     geodetic2ecef(lat[qc], lon[qc], alt[qc], X, Y, Z);
-    const double* __restrict__ c = M.centers;
-    const double* __restrict__ Cr = C + (int64_t)(live ? r : 0) * M.N;      // (a live lane exists: row 0 does)
-    double a = 0.0, b = 0.0;
-    for (int n = 0; n < M.N; ++n) {
-        const double dx = X - c[3 * n], dy = Y - c[3 * n + 1], dz = Z - c[3 * n + 2];
-        const double e = exp(-(dx * dx + dy * dy + dz * dz) * M.inv_eps2);
-        a = fma(e, Cr[n], a);
-        if (INTERP) b = fma(e, Cr[M.N + n], b);
-    }
+    double a, b;
+    rbf_rows<INTERP>(M, C + (int64_t)(live ? r : 0) * M.N, X, Y, Z, a, b);      // (a live lane exists: row 0 does)
     double val = a;
     if (INTERP) {
         const double w = wgt[qc];
@@ -1812,7 +1434,6 @@ __global__ __launch_bounds__(BLOCK) void k_slant_rbf(RbfDev M, int64_t P, const 
         return;
     }
     const double w = INTERP ? wgt[p] : 0.0;
-    const double* __restrict__ c = M.centers;
     const double* __restrict__ Cr = C + (int64_t)y.r * M.N;
     double acc = 0.0;
 #pragma unroll 1
@@ -1821,13 +1442,8 @@ __global__ __launch_bounds__(BLOCK) void k_slant_rbf(RbfDev M, int64_t P, const 
         const bool on = i < n;
         double X, Y, Z;
         slant_node(y, xq[on ? i : 0], X, Y, Z);
-        double va = 0.0, vb = 0.0;
-        for (int k = 0; k < M.N; ++k) {
-            const double dx = X - c[3 * k], dy = Y - c[3 * k + 1], dz = Z - c[3 * k + 2];
-            const double e = exp(-(dx * dx + dy * dy + dz * dz) * M.inv_eps2);
-            va = fma(e, Cr[k], va);
-            if (INTERP) vb = fma(e, Cr[M.N + k], vb);
-        }
+        double va, vb;
+        rbf_rows<INTERP>(M, Cr, X, Y, Z, va, vb);
         const double val = INTERP ? (1.0 - w) * va + w * vb : va;
         const double term = wq[on ? i : 0] * val;
         acc += on ? term : 0.0;
@@ -1855,7 +1471,6 @@ __global__ __launch_bounds__(SLANT_WAVES * 64) void k_slant_basis_rbf(RbfDev M, 
     if (y.live) {
         double* tile = sh + (size_t)N * waves + (size_t)wave * TR * RAYB_LD;
         double* acc = sh + wave;
-        const double* __restrict__ c = M.centers;
         for (int i = lane; i < N; i += 64) acc[(size_t)i * waves] = 0.0;
 #pragma unroll 1
         for (int i0 = 0; i0 < n; i0 += 64) {
@@ -1869,8 +1484,7 @@ __global__ __launch_bounds__(SLANT_WAVES * 64) void k_slant_basis_rbf(RbfDev M, 
 #pragma unroll
                 for (int j = 0; j < TR; ++j) {
                     const int k = k0 + j < N ? k0 + j : N - 1;
-                    const double dx = X - c[3 * k], dy = Y - c[3 * k + 1], dz = Z - c[3 * k + 2];
-                    tile[j * RAYB_LD + lane] = wgt * exp(-(dx * dx + dy * dy + dz * dz) * M.inv_eps2);
+                    tile[j * RAYB_LD + lane] = wgt * rbf_gauss(M, k, X, Y, Z);
                 }
                 rayb_sum<TR>(tile, acc, waves, [&](int r) { return k0 + r < N ? k0 + r : -1; });
             }
@@ -1895,38 +1509,6 @@ int launch_basis_sph(vi_model* m, int64_t P, const double* lat, const double* lo
                        lat, lon, alt, A, ld_p, ld_n);
     VI_HIP(hipGetLastError());
     return VI_OK;
-}
-
-template <int LCAP, int KCAP>
-int launch_eval_sph(vi_model* m, int64_t Q, const double* lat, const double* lon, const double* alt, int64_t T,
-                    const double* Cp, const unsigned char* hull, int F, double tol, double* out)
-{
-    const int N = m->N;
-    return for_tiles<4, 1>(T, [&](auto w, int64_t t) {
-        hipLaunchKernelGGL((k_eval_sph<LCAP, KCAP, w>), dim3(nblocks(Q, BLOCK)), dim3(BLOCK), 0, m->ctx->stream, m->sph, Q, lat,
-                           lon, alt, (int)w, Cp + t * N, hull, F, tol, out + t * Q);
-    });
-}
-
-template <int L, int K, typename CT>
-int launch_eval_sph_fast(vi_model* m, int64_t Q, const double* lat, const double* lon, const double* alt, int64_t T,
-                         const double* Cp, const unsigned char* hull, int F, double tol, double* out)
-{
-    const int N = m->N;
-    auto shm = [&](int TT) { return chain_lds_bytes(m->nvmax0 + 1, L, (size_t)TT * N); };
-    // per call, not cached: the attribute is per device and several device contexts may live in one process
-    VI_HIP(hipFuncSetAttribute((const void*)k_eval_sph_fast<L, K, 16, CT>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-    VI_HIP(hipFuncSetAttribute((const void*)k_eval_sph_fast<L, K, 4, CT>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-    VI_HIP(hipFuncSetAttribute((const void*)k_eval_sph_fast<L, K, 1, CT>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-    // timestep tiles of 16 / 4 / 1: the basis is recomputed once per tile, so a wide tile amortises it and the
-    // contraction (2N flop per point-timestep) dominates.  Measured at 128^3, N = 144: 1.4e10 / 3.9e10 / 6.2e10
-    // point-timesteps/s for tiles of 1 / 4 / 16 (a tile of 8 is slower than 16).  Whole tiles of 16 timesteps normally
-    // never get here: vi_eval_mfma.hip contracts them on the matrix cores (1.2e11).
-    const bool wide_ok = shm(16) <= 60 * 1024;
-    return for_tiles<16, 4, 1>(T, [&](int w) { return w < 16 || wide_ok; }, [&](auto w, int64_t t) {
-        hipLaunchKernelGGL((k_eval_sph_fast<L, K, w, CT>), dim3(nblocks(Q, BLOCK)), dim3(BLOCK), shm(w), m->ctx->stream, m->sph,
-                           Q, lat, lon, alt, (int)w, Cp + t * N, hull, F, tol, out + t * Q);
-    });
 }
 
 // K2t launches (vi_eval_track_f64): w == nullptr is nearest mode.  Cp: the R prepared rows.
@@ -1999,41 +1581,6 @@ int launch_slant_sph(vi_model* m, const SlantArgs& s, const double* Cp)
         VI_HIP(hipGetLastError());
         return VI_OK;
     });
-}
-
-bool use_fast_eval()
-{
-    static const bool generic = vi_env_is("VINTERP_EVAL", "generic");
-    return !generic;
-}
-
-// The orders (MAXL, MAXK) the tiled kernels k_eval_sph_fast and k_track_sph_fast are compiled at: X(L, K) for each.  The first
-// two are the orders of the fp32-chain tolerance sweep (vi_model_set_eval_precision), the only ones compiled with float chains.
-#define VI_FAST_ORDERS_F32(X) X(6, 4) X(2, 8)
-#define VI_FAST_ORDERS(X) VI_FAST_ORDERS_F32(X) X(3, 4) X(4, 3) X(3, 2) X(12, 2) X(12, 8)
-
-// Whether a model of one of those orders runs the tiled kernels at a tile of TT timesteps: one degree group, and table plus
-// tile within 60 KB of LDS.  The test is coarser than chain_lds_bytes - it counts neither the padding, the L ints nor the spare
-// 16 bytes - and is not replaced by it, because it decides the route: at (2, 8), (3, 4) and (3, 2) with nvmax0 = 3774, 2510 and
-// 2534 it admits a model whose exact size is 61 448 / 61 452 bytes (the launchers allow 64 KB), which the exact size turns away.
-bool fast_eval_fits(const vi_model* m, int TT)
-{
-    return use_fast_eval() && m->sph.ngroups == 1 &&
-           (size_t)(m->nvmax0 + 1) * m->sph.maxl * 8 + (size_t)TT * m->N * 8 < 60 * 1024;
-}
-
-// The per-lane kernels (k_basis_sph, k_eval_sph, k_track_sph) are compiled at three caps (LCAP, KCAP): the default order, the
-// C5 order, larger orders.  f(integral_constant LCAP, KCAP) at the first cap that holds the model's order.
-template <class F>
-int at_order_cap(const vi_model* m, const char* who, F&& f)
-{
-    const int L = m->sph.maxl, K = m->sph.maxk;
-#define VI_CAP(LC, KC) \
-    if (L <= LC && K <= KC) return f(std::integral_constant<int, LC>{}, std::integral_constant<int, KC>{});
-    VI_CAP(6, 4) VI_CAP(12, 8) VI_CAP(24, 16)
-#undef VI_CAP
-    vi_set_error("%s: order MAXL=%d MAXK=%d beyond the compiled limits (24, 16)", who, L, K);
-    return VI_ERR_UNSUPPORTED;
 }
 
 }  // namespace
@@ -2180,20 +1727,6 @@ extern "C" int vi_eval_err_f64(vi_model* m, int64_t Q, const double* d_lat, cons
     });
 }
 
-// Arithmetic of the Legendre degree recurrences of the fused evaluation: 0 = fp64 (default), 1 = fp32 chains (seeds,
-// trigonometric and Laguerre factors and the contraction stay fp64).  BASELINE configs[4]'s fp32-vs-fp64 tolerance sweep.
-extern "C" int vi_model_set_eval_precision(vi_model* m, int32_t chain_f32)
-{
-    VI_REQUIRE(m, "null model");
-    VI_REQUIRE(chain_f32 == 0 || chain_f32 == 1, "precision must be 0 (fp64) or 1 (fp32 chains)");
-    if (chain_f32 && m->kind != VI_MODEL_SPHHARMLAG) {
-        vi_set_error("vi_model_set_eval_precision: the fp32 variant exists for the sphharmlag model only");
-        return VI_ERR_UNSUPPORTED;
-    }
-    m->chain_f32 = chain_f32 != 0;
-    return VI_OK;
-}
-
 extern "C" int vi_transform_f64(vi_model* m, int64_t P, const double* d_lat, const double* d_lon, const double* d_alt,
                                 double* d_c0, double* d_c1, double* d_c2)
 {
@@ -2246,7 +1779,6 @@ void launch_hull_mask(vi_model* m, int64_t Q, const double* d_lat, const double*
 }
 }  // namespace
 
-namespace {
 // Gets a call ready, the one routine that does: grows the model's hull, mask and coefficient buffers; builds the hull buffer from
 // the F facet equations and m->d_coef from the `rows` coefficient rows of d_C (sphharmlag only: the RBF kernels read d_C as
 // it is, their callers pass rows = 0) - in one launch where the call has both -; then, with F > 0, m->d_mask[q] <- 1 where point
@@ -2276,14 +1808,13 @@ int prepare_call(vi_model* m, int64_t Q, const double* d_lat, const double* d_lo
     }
     return VI_OK;
 }
-}  // namespace
 
 extern "C" int vi_eval_basis_f64(vi_model* m, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt,
                                  const double* d_hull_eq, int32_t F, double hull_tol, double* d_Y)
 {
     VI_REQUIRE(m && d_lat && d_lon && d_alt && d_Y, "null argument");
     VI_REQUIRE(Q >= 0 && F >= 0, "negative size");
-    VI_REQUIRE(F == 0 || d_hull_eq, "hull facet count given without facet equations");
+    VI_REQUIRE_HULL(F, d_hull_eq);
     if (Q == 0) return VI_OK;
     int rc = vi_basis_f64(m, Q, d_lat, d_lon, d_alt, d_Y, 1, Q);
     if (rc != VI_OK || F == 0) return rc;
@@ -2301,8 +1832,8 @@ extern "C" int vi_eval_grad_basis_f64(vi_model* m, int64_t Q, const double* d_la
 {
     VI_REQUIRE(m && d_lat && d_lon && d_alt && d_G, "null argument");
     VI_REQUIRE(Q >= 0 && F >= 0, "negative size");
-    VI_REQUIRE(F == 0 || d_hull_eq, "hull facet count given without facet equations");
-    VI_REQUIRE(frame == VI_FRAME_MODEL || frame == VI_FRAME_ENU, "frame must be VI_FRAME_MODEL or VI_FRAME_ENU");
+    VI_REQUIRE_HULL(F, d_hull_eq);
+    VI_REQUIRE_FRAME(frame);
     if (Q > 0 && F > 0 && m->kind == VI_MODEL_SPHHARMLAG) {          // (the launcher refuses the other model)
         VI_HIP(hipSetDevice(m->ctx->device));
         const int rc = prepare_call(m, Q, d_lat, d_lon, d_alt, d_hull_eq, F, hull_tol, 0, nullptr);
@@ -2310,6 +1841,29 @@ extern "C" int vi_eval_grad_basis_f64(vi_model* m, int64_t Q, const double* d_la
     }
     return launch_grad_resident(m, "vi_eval_grad_basis_f64", Q, d_lat, d_lon, d_alt, F > 0 ? m->d_mask : nullptr, frame, d_G);
 }
+
+namespace {
+// What the two gradient-covariance entries set up alike: the hull pass for all Q points, the chunk - vi_forms_chunk(N, 3), or the
+// smaller one of the switch `chunk_env` -, and the context workspace: the planar gradient basis G of a chunk and, unless every
+// chunk takes the kernels of vi_eval_resident.hip, the work space of the library route behind it without a gap (else nullptr) -
+// A and B of vi_resident_gradcov, or with `records` what vi_records_gradcov asks for.  Each entry walks the chunks itself.
+struct GradcovChunks { int64_t chunk; double *G, *work; };
+int gradcov_setup(vi_model* m, const char* chunk_env, bool records, int64_t Q, const double* d_lat, const double* d_lon,
+                  const double* d_alt, const double* d_hull_eq, int32_t F, double hull_tol, GradcovChunks* k)
+{
+    VI_HIP(hipSetDevice(m->ctx->device));
+    const int N = m->N;
+    int rc = VI_OK;
+    if (F > 0 && (rc = prepare_call(m, Q, d_lat, d_lon, d_alt, d_hull_eq, F, hull_tol, 0, nullptr)) != VI_OK) return rc;
+    k->chunk = std::min(Q, test_chunk(chunk_env, vi_forms_chunk(N, 3), 1));
+    const bool own = vi_eval_resident_gradcov_shape(N);
+    return ws_carve(m->ctx, [&](ws_carver& w) {
+        k->G = w.take<double>((size_t)3 * k->chunk * N);
+        k->work = w.take<double>(own ? 0 : records ? vi_forms_work_doubles(N, 3, k->chunk) : (size_t)6 * k->chunk * N, 8);
+        if (own) k->work = nullptr;
+    });
+}
+}  // namespace
 
 // The gradient covariance of ONE covariance at arbitrary points, d_out[k*Q + q]: in chunks of points the planar gradient basis
 // of the chunk (the launcher of vi_eval_grad_basis_f64: hull mask and frame on the device) goes into the context workspace,
@@ -2321,89 +1875,19 @@ extern "C" int vi_eval_grad_cov_f64(vi_model* m, int64_t Q, const double* d_lat,
 {
     VI_REQUIRE(m && d_lat && d_lon && d_alt && d_dC && d_out, "null argument");
     VI_REQUIRE(Q >= 0 && F >= 0, "negative size");
-    VI_REQUIRE(F == 0 || d_hull_eq, "hull facet count given without facet equations");
-    VI_REQUIRE(frame == VI_FRAME_MODEL || frame == VI_FRAME_ENU, "frame must be VI_FRAME_MODEL or VI_FRAME_ENU");
+    VI_REQUIRE_HULL(F, d_hull_eq);
+    VI_REQUIRE_FRAME(frame);
     int rc = grad_model_check(m, "vi_eval_grad_cov_f64");
     if (rc != VI_OK || Q == 0) return rc;
-    vi_ctx* c = m->ctx;
-    VI_HIP(hipSetDevice(c->device));
-    const int N = m->N;
-    if (F > 0 && (rc = prepare_call(m, Q, d_lat, d_lon, d_alt, d_hull_eq, F, hull_tol, 0, nullptr)) != VI_OK) return rc;
-    const int64_t chunk = std::min(Q, test_chunk("VINTERP_GRADCOV_CHUNK", vi_forms_chunk(N, 3), 1));
-    const bool own = vi_eval_resident_gradcov_shape(N);
-    double *G, *AB;                                       // AB: A and B of the library route, behind G without a gap
-    rc = ws_carve(c, [&](ws_carver& w) {
-        G = w.take<double>((size_t)3 * chunk * N);
-        AB = w.take<double>(own ? 0 : (size_t)6 * chunk * N, 8);
-        if (own) AB = nullptr;
-    });
+    GradcovChunks k;
+    rc = gradcov_setup(m, "VINTERP_GRADCOV_CHUNK", false, Q, d_lat, d_lon, d_alt, d_hull_eq, F, hull_tol, &k);
     if (rc != VI_OK) return rc;
-    return for_chunks(Q, chunk, [&](int64_t q0, int64_t qc) -> int {
+    return for_chunks(Q, k.chunk, [&](int64_t q0, int64_t qc) -> int {
         const int rc = launch_grad_resident(m, "vi_eval_grad_cov_f64", qc, d_lat + q0, d_lon + q0, d_alt + q0,
-                                            F > 0 ? m->d_mask + q0 : nullptr, frame, G);
+                                            F > 0 ? m->d_mask + q0 : nullptr, frame, k.G);
         if (rc != VI_OK) return rc;
-        EvalTimer timer(c);
-        return vi_resident_gradcov(m, qc, 1, G, d_dC, d_out + q0, Q, AB);
-    });
-}
-
-extern "C" int vi_eval_f64(vi_model* m, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt,
-                           int64_t T, const double* d_C, const double* d_hull_eq, int32_t F, double hull_tol,
-                           double* d_out)
-{
-    VI_REQUIRE(m && d_lat && d_lon && d_alt && d_C && d_out, "null argument");
-    VI_REQUIRE(Q >= 0 && T >= 0 && F >= 0, "negative size");
-    VI_REQUIRE(F == 0 || d_hull_eq, "hull facet count given without facet equations");
-    if (Q == 0 || T == 0) return VI_OK;
-    VI_HIP(hipSetDevice(m->ctx->device));
-    const int N = m->N;
-    const bool sph = m->kind == VI_MODEL_SPHHARMLAG;
-    int rc = prepare_call(m, Q, d_lat, d_lon, d_alt, d_hull_eq, F, hull_tol, sph ? T : 0, d_C);
-    if (rc != VI_OK) return rc;
-    const unsigned char* d_mask = F > 0 ? m->d_mask : nullptr;
-    EvalTimer timer(m->ctx);
-    if (sph) {
-        const int L = m->sph.maxl, K = m->sph.maxk;
-        // whole tiles of 16 timesteps go to the matrix-core kernel (vi_eval_mfma.hip); the rest to the VALU kernels
-        int64_t done = 0;
-        if (use_fast_eval() && !m->chain_f32) {
-            rc = vi_eval_sph_mfma(m, Q, d_lat, d_lon, d_alt, T, m->d_coef, d_mask, (int)F, d_out, &done);
-            if (rc != VI_OK) return rc;
-            if (done == T) return VI_OK;
-        }
-        const int64_t Tr = T - done;
-        const double* coef = m->d_coef + done * N;
-        double* outp = d_out + done * Q;
-        if (use_fast_eval()) {                  // high orders: the chains in groups (vi_eval_split.hip)
-            int handled = 0;
-            rc = vi_eval_sph_split(m, Q, d_lat, d_lon, d_alt, Tr, coef, d_mask, (int)F, outp, &handled);
-            if (rc != VI_OK || handled) return rc;
-        }
-        if (fast_eval_fits(m, 4)) {
-#define VI_FAST(CT, LL, KK) \
-    if (L == LL && K == KK) return launch_eval_sph_fast<LL, KK, CT>(m, Q, d_lat, d_lon, d_alt, Tr, coef, d_mask, F, hull_tol, outp);
-#define VI_FAST_F32(LL, KK) VI_FAST(float, LL, KK)
-#define VI_FAST_F64(LL, KK) VI_FAST(double, LL, KK)
-            if (m->chain_f32) {     // fp32 Legendre chains (vi_model_set_eval_precision): the orders of the tolerance sweep
-                VI_FAST_ORDERS_F32(VI_FAST_F32)
-                vi_set_error("vi_eval_f64: no fp32-chain kernel for MAXL=%d MAXK=%d", L, K);
-                return VI_ERR_UNSUPPORTED;
-            }
-            VI_FAST_ORDERS(VI_FAST_F64)
-#undef VI_FAST_F64
-#undef VI_FAST_F32
-#undef VI_FAST
-        }
-        return at_order_cap(m, "vi_eval_f64", [&](auto lc, auto kc) {
-            return launch_eval_sph<lc, kc>(m, Q, d_lat, d_lon, d_alt, Tr, coef, d_mask, F, hull_tol, outp);
-        });
-    }
-    // the exponential of a (point, centre) pair is the cost (~20 of the ~28 fp64 operations per pair): it is computed once per
-    // tile of timesteps, so the tile is as wide as the registers allow (16 accumulators; a tile of 4 recomputed every
-    // exponential four times for 16 timesteps: 10.7 ms instead of 3.4 at 1000 centres x 128^3 points)
-    return for_tiles<16, 4, 1>(T, [&](auto w, int64_t t) {
-        hipLaunchKernelGGL(k_eval_rbf<w>, dim3(nblocks(Q, BLOCK)), dim3(BLOCK), 0, m->ctx->stream, m->rbf, Q, d_lat, d_lon, d_alt,
-                           (int)w, d_C + t * N, d_mask, F, hull_tol, d_out + t * Q);
+        EvalTimer timer(m->ctx);
+        return vi_resident_gradcov(m, qc, 1, k.G, d_dC, d_out + q0, Q, k.work);
     });
 }
 
@@ -2416,10 +1900,9 @@ extern "C" int vi_eval_track_f64(vi_model* m, int64_t Q, const double* d_lat, co
 {
     VI_REQUIRE(m && d_lat && d_lon && d_alt && d_rec && d_out, "null argument");
     VI_REQUIRE(Q >= 0 && R >= 0 && F >= 0, "negative size");
-    VI_REQUIRE(R == 0 || d_C, "record count given without coefficients");
-    VI_REQUIRE(R <= 0x7fffffffLL, "more records than a 32-bit record index");
+    VI_REQUIRE_RECORDS(R, d_C, "coefficients");
     VI_REQUIRE(Q <= (int64_t)TRACK_BLOCK * 0x7fffffffLL, "more points than one launch takes");
-    VI_REQUIRE(F == 0 || d_hull_eq, "hull facet count given without facet equations");
+    VI_REQUIRE_HULL(F, d_hull_eq);
     if (Q == 0) return VI_OK;
     VI_HIP(hipSetDevice(m->ctx->device));
     const bool sph = m->kind == VI_MODEL_SPHHARMLAG;
@@ -2436,14 +1919,12 @@ extern "C" int vi_eval_track_f64(vi_model* m, int64_t Q, const double* d_lat, co
             VI_HIP(hipGetLastError());
             return VI_OK;
         });
-    const int L = m->sph.maxl, K = m->sph.maxk;
     const double* coef = m->d_coef;
-    if (fast_eval_fits(m, TRACK_TT)) {
-#define VI_TRACK_FAST(LL, KK) \
-    if (L == LL && K == KK) return launch_track_sph_fast<LL, KK>(m, Q, d_lat, d_lon, d_alt, d_rec, d_w, Ri, coef, d_mask, F, d_out);
-        VI_FAST_ORDERS(VI_TRACK_FAST)
-#undef VI_TRACK_FAST
-    }
+    int rcf;
+    if (fast_eval_fits(m, TRACK_TT) && at_fast_order(m, &rcf, [&](auto l, auto k) {
+            return launch_track_sph_fast<l, k>(m, Q, d_lat, d_lon, d_alt, d_rec, d_w, Ri, coef, d_mask, F, d_out);
+        }))
+        return rcf;
     return at_order_cap(m, "vi_eval_track_f64", [&](auto lc, auto kc) {
         return launch_track_sph<lc, kc>(m, Q, d_lat, d_lon, d_alt, d_rec, d_w, Ri, coef, d_mask, F, d_out);
     });
@@ -2457,11 +1938,10 @@ extern "C" int vi_eval_track_grad_f64(vi_model* m, int64_t Q, const double* d_la
 {
     VI_REQUIRE(m && d_lat && d_lon && d_alt && d_rec && d_out, "null argument");
     VI_REQUIRE(Q >= 0 && R >= 0 && F >= 0, "negative size");
-    VI_REQUIRE(R == 0 || d_C, "record count given without coefficients");
-    VI_REQUIRE(R <= 0x7fffffffLL, "more records than a 32-bit record index");
+    VI_REQUIRE_RECORDS(R, d_C, "coefficients");
     VI_REQUIRE(Q <= (int64_t)TRACK_BLOCK * 0x7fffffffLL, "more points than one launch takes");
-    VI_REQUIRE(F == 0 || d_hull_eq, "hull facet count given without facet equations");
-    VI_REQUIRE(frame == VI_FRAME_MODEL || frame == VI_FRAME_ENU, "frame must be VI_FRAME_MODEL or VI_FRAME_ENU");
+    VI_REQUIRE_HULL(F, d_hull_eq);
+    VI_REQUIRE_FRAME(frame);
     int rc = grad_model_check(m, "vi_eval_track_grad_f64");
     if (rc != VI_OK || Q == 0) return rc;
     VI_HIP(hipSetDevice(m->ctx->device));
@@ -2510,9 +1990,8 @@ extern "C" int vi_eval_track_err_f64(vi_model* m, int64_t Q, const double* d_lat
 {
     VI_REQUIRE(m && d_lat && d_lon && d_alt && d_rec && d_out, "null argument");
     VI_REQUIRE(Q >= 0 && R >= 0 && F >= 0, "negative size");
-    VI_REQUIRE(R == 0 || d_dC, "record count given without covariances");
-    VI_REQUIRE(R <= 0x7fffffffLL, "more records than a 32-bit record index");
-    VI_REQUIRE(F == 0 || d_hull_eq, "hull facet count given without facet equations");
+    VI_REQUIRE_RECORDS(R, d_dC, "covariances");
+    VI_REQUIRE_HULL(F, d_hull_eq);
     if (Q == 0) return VI_OK;
     VI_HIP(hipSetDevice(m->ctx->device));
     int rc = prepare_call(m, Q, d_lat, d_lon, d_alt, d_hull_eq, F, hull_tol, 0, nullptr);
@@ -2541,31 +2020,20 @@ extern "C" int vi_eval_track_grad_cov_f64(vi_model* m, int64_t Q, const double* 
 {
     VI_REQUIRE(m && d_lat && d_lon && d_alt && d_rec && d_out, "null argument");
     VI_REQUIRE(Q >= 0 && R >= 0 && F >= 0, "negative size");
-    VI_REQUIRE(R == 0 || d_dC, "record count given without covariances");
-    VI_REQUIRE(R <= 0x7fffffffLL, "more records than a 32-bit record index");
-    VI_REQUIRE(F == 0 || d_hull_eq, "hull facet count given without facet equations");
-    VI_REQUIRE(frame == VI_FRAME_MODEL || frame == VI_FRAME_ENU, "frame must be VI_FRAME_MODEL or VI_FRAME_ENU");
+    VI_REQUIRE_RECORDS(R, d_dC, "covariances");
+    VI_REQUIRE_HULL(F, d_hull_eq);
+    VI_REQUIRE_FRAME(frame);
     int rc = grad_model_check(m, "vi_eval_track_grad_cov_f64");
     if (rc != VI_OK || Q == 0) return rc;
-    vi_ctx* c = m->ctx;
-    VI_HIP(hipSetDevice(c->device));
-    const int N = m->N;
-    if (F > 0 && (rc = prepare_call(m, Q, d_lat, d_lon, d_alt, d_hull_eq, F, hull_tol, 0, nullptr)) != VI_OK) return rc;
-    const int64_t chunk = std::min(Q, test_chunk("VINTERP_TRACK_GRADCOV_CHUNK", vi_forms_chunk(N, 3), 1));
-    const bool own = vi_eval_resident_gradcov_shape(N);
-    double *G, *work;                                     // work: that of the library route, behind G without a gap
-    rc = ws_carve(c, [&](ws_carver& w) {
-        G = w.take<double>((size_t)3 * chunk * N);
-        work = w.take<double>(own ? 0 : vi_forms_work_doubles(N, 3, chunk), 8);
-        if (own) work = nullptr;
-    });
+    GradcovChunks k;
+    rc = gradcov_setup(m, "VINTERP_TRACK_GRADCOV_CHUNK", true, Q, d_lat, d_lon, d_alt, d_hull_eq, F, hull_tol, &k);
     if (rc != VI_OK) return rc;
-    EvalTimer timer(c);
-    return for_chunks(Q, chunk, [&](int64_t q0, int64_t qc) -> int {
+    EvalTimer timer(m->ctx);
+    return for_chunks(Q, k.chunk, [&](int64_t q0, int64_t qc) -> int {
         const int rc = launch_grad_resident(m, "vi_eval_track_grad_cov_f64", qc, d_lat + q0, d_lon + q0, d_alt + q0,
-                                            F > 0 ? m->d_mask + q0 : nullptr, frame, G);
+                                            F > 0 ? m->d_mask + q0 : nullptr, frame, k.G);
         if (rc != VI_OK) return rc;
-        return vi_records_gradcov(m, qc, G, d_rec + q0, d_w ? d_w + q0 : nullptr, R, d_dC, d_out + q0, Q, work);
+        return vi_records_gradcov(m, qc, k.G, d_rec + q0, d_w ? d_w + q0 : nullptr, R, d_dC, d_out + q0, Q, k.work);
     });
 }
 
@@ -2579,11 +2047,10 @@ extern "C" int vi_eval_slant_f64(vi_model* m, int64_t P, const double* d_a, cons
 {
     VI_REQUIRE(m && d_a && d_b && d_rec && d_x && d_wq && d_out, "null argument");
     VI_REQUIRE(P >= 0 && R >= 0 && F >= 0, "negative size");
-    VI_REQUIRE(n >= 1, "a rule has at least one node");
-    VI_REQUIRE(R == 0 || d_C, "record count given without coefficients");
-    VI_REQUIRE(R <= 0x7fffffffLL, "more records than a 32-bit record index");
-    VI_REQUIRE(P <= 0x7fffffffLL, "more rays than one launch takes");
-    VI_REQUIRE(F == 0 || d_hull_eq, "hull facet count given without facet equations");
+    VI_REQUIRE_RULE(n);
+    VI_REQUIRE_RECORDS(R, d_C, "coefficients");
+    VI_REQUIRE_RAYS(P);
+    VI_REQUIRE_HULL(F, d_hull_eq);
     if (P == 0) return VI_OK;
     VI_HIP(hipSetDevice(m->ctx->device));
     const bool sph = m->kind == VI_MODEL_SPHHARMLAG;
@@ -2599,13 +2066,9 @@ extern "C" int vi_eval_slant_f64(vi_model* m, int64_t P, const double* d_a, cons
             VI_HIP(hipGetLastError());
             return VI_OK;
         });
-    const int L = m->sph.maxl, K = m->sph.maxk;
-    if (fast_eval_fits(m, 1)) {
-#define VI_SLANT_FAST(LL, KK) \
-    if (L == LL && K == KK) return launch_slant_sph_fast<LL, KK>(m, s, m->d_coef);
-        VI_FAST_ORDERS(VI_SLANT_FAST)
-#undef VI_SLANT_FAST
-    }
+    int rcf;
+    if (fast_eval_fits(m, 1) && at_fast_order(m, &rcf, [&](auto l, auto k) { return launch_slant_sph_fast<l, k>(m, s, m->d_coef); }))
+        return rcf;
     return at_order_cap(m, "vi_eval_slant_f64", [&](auto lc, auto kc) { return launch_slant_sph<lc, kc>(m, s, m->d_coef); });
 }
 
@@ -2646,9 +2109,9 @@ extern "C" int vi_eval_slant_basis_f64(vi_model* m, int64_t P, const double* d_a
 {
     VI_REQUIRE(m && d_a && d_b && d_x && d_wq && d_Y, "null argument");
     VI_REQUIRE(P >= 0 && F >= 0, "negative size");
-    VI_REQUIRE(n >= 1, "a rule has at least one node");
-    VI_REQUIRE(P <= 0x7fffffffLL, "more rays than one launch takes");
-    VI_REQUIRE(F == 0 || d_hull_eq, "hull facet count given without facet equations");
+    VI_REQUIRE_RULE(n);
+    VI_REQUIRE_RAYS(P);
+    VI_REQUIRE_HULL(F, d_hull_eq);
     if (P == 0) return VI_OK;
     VI_HIP(hipSetDevice(m->ctx->device));
     const SlantArgs s{P, d_a, d_b, nullptr, nullptr, 0, d_hull_eq, (int)F, hull_tol, (int)n, d_x, d_wq, d_Y, d_chord};
@@ -2667,10 +2130,9 @@ extern "C" int vi_eval_slant_err_f64(vi_model* m, int64_t P, const double* d_a, 
 {
     VI_REQUIRE(m && d_a && d_b && d_rec && d_x && d_wq && d_out, "null argument");
     VI_REQUIRE(P >= 0 && R >= 0 && F >= 0, "negative size");
-    VI_REQUIRE(n >= 1, "a rule has at least one node");
-    VI_REQUIRE(R == 0 || d_dC, "record count given without covariances");
-    VI_REQUIRE(R <= 0x7fffffffLL, "more records than a 32-bit record index");
-    VI_REQUIRE(F == 0 || d_hull_eq, "hull facet count given without facet equations");
+    VI_REQUIRE_RULE(n);
+    VI_REQUIRE_RECORDS(R, d_dC, "covariances");
+    VI_REQUIRE_HULL(F, d_hull_eq);
     if (P == 0) return VI_OK;
     vi_ctx* c = m->ctx;
     VI_HIP(hipSetDevice(c->device));

@@ -31,7 +31,7 @@
 // the rate is the same, so the widest tile is 32.
 #include "vi_common.h"
 #include "vi_solver.h"
-#include "vi_sph_device.h"
+#include "vi_chain_device.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -86,40 +86,6 @@ struct MfmaSink {
             feed(r0 + m, cur[m] * cm[m]);
             if (m > 0) feed(r0 - m, cur[m] * sm[m]);
         }
-    }
-};
-
-template <int L, class Sink, int l>
-struct PickAt {
-    // consume degree l if its integer part equals j (start-up phase only: j <= L)
-    __device__ static __forceinline__ void run(Sink& E, const int* nvr, int j, const double* cur, const double* cm,
-                                               const double* sm)
-    {
-        if (nvr[l] == j) E.template consume<l>(cur, cm, sm);
-        if constexpr (l + 1 < L) PickAt<L, Sink, l + 1>::run(E, nvr, j, cur, cm, sm);
-    }
-};
-
-template <int L, class Sink, int l>
-struct MainSeg {
-    __device__ static __forceinline__ void run(Sink& E, const double* shc, const int* nvr, int& j, double x, double* cur,
-                                               double* prev, const double* cm, const double* sm)
-    {
-        const int jend = nvr[l];
-        if (jend > L) {
-#pragma unroll 2
-            for (; j <= jend; ++j) {
-                const double* cj = shc + j * L;
-#pragma unroll
-                for (int m = 0; m < L; ++m) {
-                    const double nw = fma(x, cur[m], -(cj[m] * prev[m]));
-                    prev[m] = cur[m];
-                    cur[m] = nw;
-                }
-            }
-            E.template consume<l>(cur, cm, sm);
-        }
-        if constexpr (l + 1 < L) MainSeg<L, Sink, l + 1>::run(E, shc, nvr, j, x, cur, prev, cm, sm);
     }
 };
 
@@ -251,11 +217,11 @@ __global__ __launch_bounds__(MBLOCK, (NT >= 2 ? 2 : 1)) void k_eval_sph_mfma(Sph
                     else cur[m] = G.pref[L + m] * spow * hyp_series(G.q + (size_t)(L + m) * G.nterms, G.nterms, zz);
                 }
             }
-            PickAt<L, Sink, 0>::run(E, nvr, j, cur, cm, sm);
+            ConsumeAt<L, Sink, 0>::run(E, nvr, j, cur, cm, sm);
         }
         // ---- main: all chains in recurrence mode; one segment per degree l ----------------------------------
         int j = L + 1;
-        MainSeg<L, Sink, 0>::run(E, shc, nvr, j, x, cur, prev, cm, sm);
+        MainSegments<L, Sink, 0>::run(E, shc, nvr, j, x, cur, prev, cm, sm);
         // ---- operand role: D[i][tile][v] is (timestep tile*16 + g + 4 v, point q0 + 16 i + pi) ---------------
         if (tcount == TT && q0 + 64 <= Q) {                  // whole tile in range (wave-uniform): plain stores
             double* o = out + (int64_t)g * Q + q0 + pi;

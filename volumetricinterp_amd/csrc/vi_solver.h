@@ -59,6 +59,13 @@ int vi_peak_columns(vi_ctx* c, int64_t outer, int64_t L, int64_t inner, int64_t 
                     int32_t* d_idx);
 int vi_reduce_basis(vi_ctx* c, int N, int64_t outer, int64_t L, int64_t inner, const double* d_Y, const double* d_w, double* d_Yr);
 
+// ---- what vi_basis.hip and vi_eval.hip (K2) share on the host; internal to the library, not among its dynamic symbols ----
+#define VI_INTERNAL __attribute__((visibility("hidden")))
+VI_INTERNAL int prepare_call(vi_model* m, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt,      // vi_basis.hip
+                             const double* d_hull_eq, int32_t F, double hull_tol, int64_t rows, const double* d_C);
+VI_INTERNAL bool use_fast_eval();                                                                                        // vi_eval.hip
+VI_INTERNAL bool fast_eval_fits(const vi_model* m, int TT);
+
 // ---- forms y^T dC y and g_c^T dC g_d on matrices already built (vi_resident.hip), for the entries of vi_basis.hip that build
 //      the matrix of a chunk themselves; `components`: 1 (a basis column per point) or 3 (a gradient basis) ----
 int64_t vi_forms_chunk(int N, int components);                            // points per chunk of the library route, unclipped

@@ -1,5 +1,6 @@
-// Device helpers shared by the basis / evaluation kernels (vi_basis.hip, vi_eval_mfma.hip): geodetic -> model
-// coordinates (sphharmlag.py:324-359), the 2F1 seed series and the Laguerre recurrence.
+// Device helpers shared by the basis / evaluation kernels (vi_basis.hip, vi_eval.hip, vi_eval_mfma.hip): geodetic -> model
+// coordinates (sphharmlag.py:324-359), the 2F1 seed series and the Laguerre recurrence; the per-point engine of the basis
+// (sph_point) with the evaluation's sink.
 #pragma once
 #include "vi_common.h"
 
@@ -55,16 +56,41 @@ __device__ __forceinline__ void geodetic2ecef(double lat, double lon, double alt
     Z = (Nn * (ba * ba) + alt) * sl;
 }
 
-// sphharmlag.py:345-359: Rodrigues rotation about k = (kx, ky, 0) by +theta0 (sign as written, F3)
-__device__ __forceinline__ Geom sph_geom(const SphDev& M, double lat, double lon, double alt)
+// Gaussian RBF model (radbasfun.py:83-112): basis function n at the ECEF point R, exp(-|R - c_n|^2 / eps^2)
+__device__ __forceinline__ double rbf_gauss(const RbfDev& M, int n, double X, double Y, double Z)
+{
+    const double* __restrict__ c = M.centers;
+    const double dx = X - c[3 * n], dy = Y - c[3 * n + 1], dz = Z - c[3 * n + 2];
+    return exp(-(dx * dx + dy * dy + dz * dz) * M.inv_eps2);
+}
+
+// the RBF model's value at an ECEF point with the coefficient row Cr and, with INTERP, with the row after it: va, vb
+template <bool INTERP>
+__device__ __forceinline__ void rbf_rows(const RbfDev& M, const double* __restrict__ Cr, double X, double Y, double Z, double& va,
+                                         double& vb)
+{
+    va = 0.0;
+    vb = 0.0;
+    for (int n = 0; n < M.N; ++n) {
+        const double e = rbf_gauss(M, n, X, Y, Z);
+        va = fma(e, Cr[n], va);
+        if (INTERP) vb = fma(e, Cr[M.N + n], vb);
+    }
+}
+
+// sphharmlag.py:345-359: the model coordinates of an ECEF point - Rodrigues rotation about k = (kx, ky, 0) by +theta0 (sign as
+// written, F3).  K2l and K1l start here: the nodes of a ray need no geodetic step.
+__device__ __forceinline__ Geom sph_geom_ecef(const SphDev& M, double X, double Y, double Z)
 {
     Geom g;
-    geodetic2ecef(lat, lon, alt, g.X, g.Y, g.Z);
-    const double kd = M.kx * g.X + M.ky * g.Y;
+    g.X = X;
+    g.Y = Y;
+    g.Z = Z;
+    const double kd = M.kx * X + M.ky * Y;
     const double omc = 1.0 - M.rc;
-    const double Rx = g.X * M.rc + (M.ky * g.Z) * M.rs + M.kx * kd * omc;
-    const double Ry = g.Y * M.rc + (-M.kx * g.Z) * M.rs + M.ky * kd * omc;
-    const double Rz = g.Z * M.rc + (M.kx * g.Y - M.ky * g.X) * M.rs;
+    const double Rx = X * M.rc + (M.ky * Z) * M.rs + M.kx * kd * omc;
+    const double Ry = Y * M.rc + (-M.kx * Z) * M.rs + M.ky * kd * omc;
+    const double Rz = Z * M.rc + (M.kx * Y - M.ky * X) * M.rs;
     const double rho2 = Rx * Rx + Ry * Ry;
     const double r = sqrt(rho2 + Rz * Rz);
     g.x = Rz / r;
@@ -77,6 +103,13 @@ __device__ __forceinline__ Geom sph_geom(const SphDev& M, double lat, double lon
     g.Rx = Rx;
     g.Ry = Ry;
     return g;
+}
+
+__device__ __forceinline__ Geom sph_geom(const SphDev& M, double lat, double lon, double alt)
+{
+    double X, Y, Z;
+    geodetic2ecef(lat, lon, alt, X, Y, Z);
+    return sph_geom_ecef(M, X, Y, Z);
 }
 
 // 2F1(a,b;c;zz) series with host-tabulated term ratios q[i] = (a+i)(b+i)/((c+i)(i+1)); the exit test
@@ -119,6 +152,116 @@ __device__ __forceinline__ void laguerre(int maxk, double z, double* Lk)
         Lk[k + 1] = ((2.0 * k + 1.0 - z) * Lk[k] - (double)k * Lk[k - 1]) * inv;
     }
     (void)maxk;
+}
+
+// The shared per-point engine.  Sink::consume(l, cur[], cm[], sm[]) is called once per degree l with
+// cur[m] = (normalised) P_{nu_l}^m(cos theta), m = 0..l.
+template <int LCAP, int KCAP, class Sink>
+__device__ __forceinline__ void sph_point(const SphDev& M, const Geom& g, Sink& sink)
+{
+    const int maxl = M.maxl;
+    // azimuthal factors cos(m phi), sin(m phi) by angle addition (sphharmlag.py:278-281 takes them of |m| phi)
+    double cm[LCAP], sm[LCAP];
+    cm[0] = 1.0;
+    sm[0] = 0.0;
+#pragma unroll
+    for (int m = 1; m < LCAP; ++m) {
+        cm[m] = cm[m - 1] * g.cphi - sm[m - 1] * g.sphi;
+        sm[m] = sm[m - 1] * g.cphi + cm[m - 1] * g.sphi;
+    }
+    const double x = g.x;
+    const double zz = 0.5 * (1.0 - x);
+    const int ng = M.ngroups;
+    for (int gi = 0; gi < ng; ++gi) {
+        const SphGroupDev G = M.groups[gi];
+        const bool intseed = (G.nterms == 0);
+        double cur[LCAP], prev[LCAP];
+#pragma unroll
+        for (int m = 0; m < LCAP; ++m) { cur[m] = 0.0; prev[m] = 0.0; }
+        double pmm = 1.0;       // (-1)^m (2m-1)!! s^m
+        double spow = 1.0;      // s^m
+        const int nvmax = G.nvmax;
+        for (int j = 0; j <= nvmax; ++j) {
+            const double* __restrict__ cj = G.c + (size_t)j * maxl;
+#pragma unroll
+            for (int m = 0; m < LCAP; ++m) {
+                if (m < maxl) {
+                    if (j > m + 1) {
+                        const double nw = fma(x, cur[m], -(cj[m] * prev[m]));
+                        prev[m] = cur[m];
+                        cur[m] = nw;
+                    } else if (j == m) {
+                        if (m > 0) { pmm *= -(2.0 * m - 1.0) * g.s; spow *= g.s; }
+                        if (intseed) cur[m] = pmm;
+                        else cur[m] = G.pref[m] * spow * hyp_series(G.q + (size_t)m * G.nterms, G.nterms, zz);
+                    } else if (j == m + 1) {
+                        prev[m] = cur[m];
+                        if (intseed) cur[m] = x * (2.0 * m + 1.0) * cur[m];
+                        else cur[m] = G.pref[maxl + m] * spow *
+                                      hyp_series(G.q + (size_t)(maxl + m) * G.nterms, G.nterms, zz);
+                    }
+                }
+            }
+            const int l = G.pick[j];
+            if (l >= 0) sink.template consume<LCAP>(l, cur, cm, sm);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// K2: fused evaluation for TT timesteps per pass.  Cp is the coefficient tile reordered to
+// [t][r = l(l+1)+m][k] and pre-multiplied by the per-(l,m) constant (see k_prep_coef).
+template <int KCAP, int TT>
+struct EvalSink {
+    const double* __restrict__ Cp;   // [TT][L2*maxk], wave-uniform reads
+    int maxk, NB;
+    double Lk[KCAP];
+    double acc[TT];
+    template <int LCAP>
+    __device__ __forceinline__ void consume(int l, const double* cur, const double* cm, const double* sm)
+    {
+        const int r0 = l * (l + 1);
+#pragma unroll
+        for (int m = 0; m < LCAP; ++m) {
+            if (m <= l) {
+                const double* __restrict__ cp = Cp + (size_t)(r0 + m) * maxk;
+                const double* __restrict__ cn = Cp + (size_t)(r0 - m) * maxk;
+                const double pc = cur[m] * cm[m];
+                const double ps = cur[m] * sm[m];
+#pragma unroll
+                for (int t = 0; t < TT; ++t) {
+                    double Sp = 0.0, Sm = 0.0;
+#pragma unroll
+                    for (int k = 0; k < KCAP; ++k) {
+                        if (k < maxk) {
+                            Sp = fma(cp[(size_t)t * NB + k], Lk[k], Sp);
+                            if (m > 0) Sm = fma(cn[(size_t)t * NB + k], Lk[k], Sm);
+                        }
+                    }
+                    acc[t] = fma(pc, Sp, acc[t]);
+                    if (m > 0) acc[t] = fma(ps, Sm, acc[t]);
+                }
+            }
+        }
+    }
+};
+
+// The per-lane evaluation of one point over TT prepared rows through EvalSink, the one copy k_eval_sph, k_track_sph and
+// k_slant_sph run: val[t] = exp(-z/2) sum_n basis_n(point) Cp[t][n], the rows M.N doubles apart.  Correct, not tuned.
+template <int LCAP, int KCAP, int TT>
+__device__ __forceinline__ void eval_point(const SphDev& M, const Geom& g, const double* __restrict__ Cp, double* val)
+{
+    EvalSink<KCAP, TT> sink;
+    sink.Cp = Cp;
+    sink.maxk = M.maxk;
+    sink.NB = M.N;
+    laguerre<KCAP>(M.maxk, g.z, sink.Lk);
+#pragma unroll
+    for (int t = 0; t < TT; ++t) sink.acc[t] = 0.0;
+    sph_point<LCAP, KCAP>(M, g, sink);
+    const double E = exp(-0.5 * g.z);
+#pragma unroll
+    for (int t = 0; t < TT; ++t) val[t] = E * sink.acc[t];
 }
 
 }  // namespace

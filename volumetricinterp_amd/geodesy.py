@@ -1,7 +1,7 @@
 """WGS84 geodetic -> ECEF on the host (pymap3d.geodetic2ecef; the reference calls it at
 models/sphharmlag.py:345, interpolate.py:422, estimate.py:172), and its inverse.  Host one-offs only (rotation
 constants, RBF centres, convex hull, the end points of Estimate.slant's rays); per-point work uses the device version in
-csrc/vi_basis.hip."""
+csrc/vi_sph_device.h."""
 import numpy as np
 
 WGS84_A = 6378137.0
