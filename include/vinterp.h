@@ -161,7 +161,7 @@ int  vi_eval_f64(vi_model* model, int64_t Q, const double* d_lat, const double* 
  * evaluates its points once per window of 4 rows (3 in interpolation mode) between its lowest and highest row.  SORT the
  * points by d_rec: the passes beyond one per group are then at most about R / 3 in the whole call, whatever Q is.
  * Models and orders as vi_eval_f64 (sphharmlag up to (24, 16), RBF), fp64 chains whatever vi_model_set_eval_precision set.
- * The orders of vi_eval_f64's fast kernels run the tiled kernel K2t (csrc/vi_basis.hip); other orders, VINTERP_EVAL=generic and the RBF model
+ * The orders of vi_eval_f64's fast kernels run the tiled kernel K2t (csrc/vi_track.hip); other orders, VINTERP_EVAL=generic and the RBF model
  * read each point's own row(s) from global memory (correct, not tuned).  Asynchronous on the context's stream; timed for
  * vi_eval_kernel_ms like its siblings (tests/test_gpu_track.py). */
 int  vi_eval_track_f64(vi_model* model, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt,
@@ -181,7 +181,7 @@ int  vi_eval_track_f64(vi_model* model, int64_t Q, const double* d_lat, const do
  * bits depend on the point, its row(s) and d_w[q], not on the other points or their order.  Correct for ANY order of d_rec;
  * the cost grows with the span of rows in a group of 64 consecutive points as in vi_eval_track_f64 (windows of 4 rows, 3 when
  * blending): SORT the points by d_rec.  sphharmlag only, at the orders of vi_grad_basis_f64 - (MAXL, MAXK) within (6, 4),
- * (12, 8) or (2, 12) -, else VI_ERR_UNSUPPORTED.  Kernel K2tg (csrc/vi_basis.hip).  Asynchronous on the context's stream;
+ * (12, 8) or (2, 12) -, else VI_ERR_UNSUPPORTED.  Kernel K2tg (csrc/vi_track.hip).  Asynchronous on the context's stream;
  * timed for vi_eval_kernel_ms like its siblings (tests/test_gpu_track_gradient.py). */
 int  vi_eval_track_grad_f64(vi_model* model, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt,
                             const int32_t* d_rec, const double* d_w, int64_t R, const double* d_C,
@@ -200,7 +200,7 @@ int  vi_eval_track_grad_f64(vi_model* model, int64_t Q, const double* d_lat, con
  * NaN d_out where d_rec[p] < 0 or a row the ray needs is >= R (R = 0: every ray), and where such a row holds a NaN.  A segment
  * of length zero inside the hull gives 0.  A wave integrates a ray, 64 nodes per pass, and adds the nodes in a fixed order: a
  * ray's bits depend on the ray, its row(s) and the rule, not on the other rays or their order - no sorting is needed.
- * Models and orders as vi_eval_track_f64; the orders of vi_eval_f64's fast kernels run K2l's tiled form (csrc/vi_basis.hip),
+ * Models and orders as vi_eval_track_f64; the orders of vi_eval_f64's fast kernels run K2l's tiled form (csrc/vi_slant.hip),
  * other orders, VINTERP_EVAL=generic and the RBF model the per-lane forms (correct, not tuned).  fp64 chains.  Asynchronous
  * on the context's stream; timed for vi_eval_kernel_ms like its siblings (tests/test_gpu_slant.py). */
 int  vi_eval_slant_f64(vi_model* model, int64_t P, const double* d_a, const double* d_b, const int32_t* d_rec, const double* d_w,
@@ -217,7 +217,7 @@ int  vi_eval_slant_f64(vi_model* model, int64_t P, const double* d_a, const doub
  * d_a, d_b, d_hull_eq, F, hull_tol, (n, d_x, d_wq) and d_chord (or NULL) exactly as in vi_eval_slant_f64: the same clip, in fp64,
  * straight from the facet list; F = 0 keeps [0, 1].  A ray that does not enter the hull (not s0 < s1) or has a non-finite end
  * point gets the NaN of vi_eval_basis_f64 in ALL N rows (and a NaN chord); a segment of length zero inside the hull a column
- * of zeros.  Kernel K1l (csrc/vi_basis.hip): a wave per ray, 64 nodes per pass, every basis function summed over the lanes
+ * of zeros.  Kernel K1l (csrc/vi_slant.hip): a wave per ray, 64 nodes per pass, every basis function summed over the lanes
  * through an LDS tile in one fixed order, the passes in pass order, no atomics - a column's bits depend on the ray and the rule,
  * not on P, the other rays or their order.  Models and orders as vi_basis_f64 while the N accumulators of a ray fit a
  * workgroup's LDS (N <= 7000; beyond: VI_ERR_UNSUPPORTED).  Asynchronous on the context's stream; timed for vi_eval_kernel_ms

@@ -10,7 +10,7 @@ REPO_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_k_eval_sph_fast_registers(tmp_path):
     """hipcc's resource report of csrc/vi_eval.hip (device pass, the Makefile's flags): no k_eval_sph_fast instantiation uses
     scratch, and k_eval_sph_fast<6, 4, 1, double> - the default order at a tile of one timestep - stays within 96 VGPRs, five
-    waves per SIMD: the figure the comments at fast_chains (vi_basis.hip) and bench.py's roofline entry rest on
+    waves per SIMD: the figure the comments at fast_chains (vi_chain_device.h) and bench.py's roofline entry rest on
     (95 when this test was written)."""
     csrc = os.path.join(REPO_ROOT, 'volumetricinterp_amd', 'csrc')
     # the command the Makefile has for the unit's object file (make -n prints it), so that the pin follows its flags

@@ -1,4 +1,4 @@
-"""Cost of the ray-integrated basis of fixed rays (Estimate.resident_rays, vi_eval_slant_basis_f64 - K1l, csrc/vi_basis.hip) and of
+"""Cost of the ray-integrated basis of fixed rays (Estimate.resident_rays, vi_eval_slant_basis_f64 - K1l, csrc/vi_slant.hip) and of
 the products on it, against what exists without it.
 
   set-up        kernel time of K1l for 65 536 and 262 144 rays, against the device route that exists today on 65 536 rays: the

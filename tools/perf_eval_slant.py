@@ -1,4 +1,4 @@
-"""Rate of the line integrals along straight rays (Estimate.slant, vi_eval_slant_f64 - K2l, csrc/vi_basis.hip): every ray at its own
+"""Rate of the line integrals along straight rays (Estimate.slant, vi_eval_slant_f64 - K2l, csrc/vi_slant.hip): every ray at its own
 time, one library call, in nearest and in interpolation mode, against
   (b) the floor: one vi_eval_f64 call with a single coefficient row and no hull on as many points as (a) has live nodes (what
       the nodes cost when they are plain points that share a time), and

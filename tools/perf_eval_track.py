@@ -1,4 +1,4 @@
-"""Rate of the evaluation along a trajectory (Estimate.track, vi_eval_track_f64 - K2t, csrc/vi_basis.hip): every point at its
+"""Rate of the evaluation along a trajectory (Estimate.track, vi_eval_track_f64 - K2t, csrc/vi_track.hip): every point at its
 own time, one library call, in nearest and in interpolation mode, against
   (a) the floor: the same points at ONE time, one vi_eval_f64 call with a single coefficient row (what the points cost when
       they share a time; and with four rows: what the tile of four costs in k_eval_sph_fast's workgroups of 256), and

@@ -1,4 +1,4 @@
-"""Rate of the gradient along a trajectory (Estimate.track_gradient, vi_eval_track_grad_f64 - K2tg, csrc/vi_basis.hip): every
+"""Rate of the gradient along a trajectory (Estimate.track_gradient, vi_eval_track_grad_f64 - K2tg, csrc/vi_track.hip): every
 point at its own time, one library call, in nearest and in interpolation mode, in the model frame and in east-north-up, against
   (a) the floor: vi_eval_track_f64 (K2t, the density) on the same points, records and mode, and
   (b) the loop it replaces: one vi_eval_grad_f64 call per record on that record's points (nearest mode) - the summed kernel time

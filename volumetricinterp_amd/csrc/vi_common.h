@@ -153,6 +153,17 @@ int for_chunks(int64_t B, int64_t Bc, F&& f)
 
 inline unsigned nblocks(int64_t n, int64_t b) { return (unsigned)((n + b - 1) / b); }
 
+// One kernel launch on a stream and its check.  A launch with dynamic LDS first raises the kernel's limit to the 64 KB of a
+// workgroup.  (static: an instantiation is its unit's own, none is among the library's dynamic symbols)
+template <class K, class... A>
+static int vi_launch(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const A&... args)
+{
+    if (lds > 0) VI_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+    hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
+    VI_HIP(hipGetLastError());
+    return VI_OK;
+}
+
 // T timesteps in tiles of the widths W..., given widest first and ending in 1: launch(integral_constant<int, w>, t0) for the
 // first width w that what is left fills and that ok(w) admits (ok(1) must hold), then the launch check, until all are done
 template <int... W, class OK, class F>
@@ -204,6 +215,17 @@ inline bool vi_env_is(const char* name, const char* value)
 {
     const char* e = getenv(name);
     return e && !strcmp(e, value);
+}
+
+// A smaller chunk for a call from the switch `name` (tests: several chunks at a small point count), read at every call: its
+// value rounded down to a multiple of `multiple`, taken where it is at least that and below `chunk`
+inline int64_t test_chunk(const char* name, int64_t chunk, int multiple)
+{
+    if (const char* e = getenv(name)) {
+        const long long v = atoll(e) / multiple * multiple;
+        if (v >= multiple && v < chunk) chunk = v;
+    }
+    return chunk;
 }
 
 // ---- device-side model tables ----------------------------------------------------------------

@@ -1,5 +1,5 @@
-// What vi_basis.hip and vi_eval.hip share on the host beside the functions vi_solver.h declares: the dispatch of a model's order
-// to the compiled kernel orders and the argument checks their entries repeat.
+// What vi_basis.hip, vi_eval.hip, vi_track.hip and vi_slant.hip share on the host beside the functions vi_solver.h declares: the
+// dispatch of a model's order to the compiled kernel orders and the argument checks their entries repeat.
 #pragma once
 #include "vi_solver.h"
 
@@ -37,6 +37,20 @@ int at_order_cap(const vi_model* m, const char* who, F&& f)
     VI_CAP(6, 4) VI_CAP(12, 8) VI_CAP(24, 16)
 #undef VI_CAP
     vi_set_error("%s: order MAXL=%d MAXK=%d beyond the compiled limits (24, 16)", who, L, K);
+    return VI_ERR_UNSUPPORTED;
+}
+
+// The gradient kernels (k_grad_sph, k_track_grad_sph) are compiled at (MAXL, MAXK) up to (6, 4), (12, 8) or (2, 12):
+// f(integral_constant LCAP, KCAP) at the first of those orders that holds the model's
+template <class F>
+int at_grad_cap(const vi_model* m, const char* who, F&& f)
+{
+    const int L = m->sph.maxl, K = m->sph.maxk;
+#define VI_CAP(LC, KC) \
+    if (L <= LC && K <= KC) return f(std::integral_constant<int, LC>{}, std::integral_constant<int, KC>{});
+    VI_CAP(6, 4) VI_CAP(12, 8) VI_CAP(2, 12)
+#undef VI_CAP
+    vi_set_error("%s: order MAXL=%d MAXK=%d beyond the compiled limits (6, 4), (12, 8) and (2, 12)", who, L, K);
     return VI_ERR_UNSUPPORTED;
 }
 

@@ -1,6 +1,6 @@
 // Entries that work on a matrix ALREADY BUILT on the device - the resident basis Y (N x Q) of vi_eval_basis_f64, the gradient
 // basis G (N x 3 x Q) of vi_eval_grad_basis_f64, the ray-integrated basis of vi_eval_slant_basis_f64 - and evaluate no basis
-// function themselves (those are vi_basis.hip's):
+// function themselves (those are vi_basis.hip's, vi_track.hip's and vi_slant.hip's):
 //   products        out = Y C of many timesteps (K2r), peak maps of it (K2p), the reduced basis along an axis;
 //   forms           y^T dC y (standard errors: K2e, K2eg, K2te) and g_c^T dC g_d (gradient covariances: K2c, K2tc).
 // Each entry asks its own kernel first (vi_eval_resident.hip).  What that declines - N > 144, odd Q, unaligned pointers,
@@ -296,6 +296,30 @@ int64_t vi_forms_chunk(int N, int components) { return std::max<int64_t>(1, ((in
 size_t vi_forms_work_doubles(int N, int components, int64_t chunk)
 {
     return (size_t)2 * components * chunk * N + (size_t)2 * form_planes(components) * chunk;
+}
+
+// Points (rays) per chunk of vi_eval_track_err_f64 and vi_eval_slant_err_f64: the basis of a chunk takes at most 256 MB of the
+// context workspace, half of what the library route of vi_eval_resident_err_f64 asks for its two matrices - with which the
+// library route of a chunk (vi_records_err) fits beside it.  Even, so that every chunk of an even call keeps K2te's shape.
+// VINTERP_TRACK_ERR_CHUNK: a smaller chunk (tests: several chunks at a small Q).
+int64_t track_err_chunk(int N, int64_t Q)
+{
+    const int64_t chunk = std::max<int64_t>(2, vi_forms_chunk(N, 1) & ~(int64_t)1);
+    return std::min(Q, test_chunk("VINTERP_TRACK_ERR_CHUNK", chunk, 2));
+}
+
+// The workspace of a chunked call: the basis Y (N x chunk), `extra` doubles for the caller, and - unless every chunk is K2te's -
+// the work space of the library route (else *work = nullptr)
+int track_err_workspace(vi_model* m, int64_t Q, int64_t chunk, const double* d_out, size_t extra, double** Y, double** X,
+                        double** work)
+{
+    const bool own = vi_eval_records_err_shape(m->N, Q, nullptr, d_out);      // (chunks are even, Y is the workspace's)
+    return ws_carve(m->ctx, [&](ws_carver& w) {
+        *Y = w.take<double>((size_t)chunk * m->N, 256);
+        *X = w.take<double>(extra, 256);
+        *work = w.take<double>(own ? 0 : vi_forms_work_doubles(m->N, 1, chunk), 256);
+        if (own) *work = nullptr;
+    });
 }
 
 // d_out[p] = sqrt(a_p^T dC a_p) of the P rows of the row-major tile A (P x N); B: P N doubles

@@ -59,17 +59,30 @@ int vi_peak_columns(vi_ctx* c, int64_t outer, int64_t L, int64_t inner, int64_t 
                     int32_t* d_idx);
 int vi_reduce_basis(vi_ctx* c, int N, int64_t outer, int64_t L, int64_t inner, const double* d_Y, const double* d_w, double* d_Yr);
 
-// ---- what vi_basis.hip and vi_eval.hip (K2) share on the host; internal to the library, not among its dynamic symbols ----
+// ---- what vi_basis.hip and the evaluation units vi_eval.hip (K2), vi_track.hip (K2t, K2tg) and vi_slant.hip (K2l, K1l) share
+//      on the host; internal to the library, not among its dynamic symbols ----
 #define VI_INTERNAL __attribute__((visibility("hidden")))
 VI_INTERNAL int prepare_call(vi_model* m, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt,      // vi_basis.hip
                              const double* d_hull_eq, int32_t F, double hull_tol, int64_t rows, const double* d_C);
+VI_INTERNAL int grad_model_check(const vi_model* m, const char* who);
+VI_INTERNAL int launch_grad_resident(vi_model* m, const char* who, int64_t Q, const double* d_lat, const double* d_lon,
+                                     const double* d_alt, const unsigned char* d_mask, int32_t frame, double* d_G);
+VI_INTERNAL int mask_basis(vi_model* m, int64_t Q, const unsigned char* d_mask, double* d_Y);
+struct GradcovChunks { int64_t chunk; double *G, *work; };
+VI_INTERNAL int gradcov_setup(vi_model* m, const char* chunk_env, bool records, int64_t Q, const double* d_lat,
+                              const double* d_lon, const double* d_alt, const double* d_hull_eq, int32_t F, double hull_tol,
+                              GradcovChunks* k);
 VI_INTERNAL bool use_fast_eval();                                                                                        // vi_eval.hip
 VI_INTERNAL bool fast_eval_fits(const vi_model* m, int TT);
 
-// ---- forms y^T dC y and g_c^T dC g_d on matrices already built (vi_resident.hip), for the entries of vi_basis.hip that build
-//      the matrix of a chunk themselves; `components`: 1 (a basis column per point) or 3 (a gradient basis) ----
+// ---- forms y^T dC y and g_c^T dC g_d on matrices already built (vi_resident.hip), for the entries of vi_basis.hip, vi_track.hip
+//      and vi_slant.hip that build the matrix of a chunk themselves; `components`: 1 (a basis column per point) or 3 (a
+//      gradient basis) ----
 int64_t vi_forms_chunk(int N, int components);                            // points per chunk of the library route, unclipped
 size_t vi_forms_work_doubles(int N, int components, int64_t chunk);       // work space of the two records routines below
+VI_INTERNAL int64_t track_err_chunk(int N, int64_t Q);                    // chunk and workspace of the track and ray error entries
+VI_INTERNAL int track_err_workspace(vi_model* m, int64_t Q, int64_t chunk, const double* d_out, size_t extra, double** Y,
+                                    double** X, double** work);
 int vi_forms_tile(vi_ctx* c, int N, int64_t P, const double* A, const double* d_dC, double* B, double* d_out);
 int vi_records_err(vi_model* m, int64_t Q, const double* d_Y, const int32_t* d_rec, const double* d_w, int64_t R,
                    const double* d_dC, double* d_out, double* work);

@@ -1,6 +1,7 @@
-// Device helpers shared by the basis / evaluation kernels (vi_basis.hip, vi_eval.hip, vi_eval_mfma.hip): geodetic -> model
-// coordinates (sphharmlag.py:324-359), the 2F1 seed series and the Laguerre recurrence; the per-point engine of the basis
-// (sph_point) with the evaluation's sink.
+// Device helpers shared by the basis / evaluation kernels (vi_basis.hip, vi_eval.hip, vi_track.hip, vi_slant.hip,
+// vi_eval_mfma.hip): geodetic -> model coordinates (sphharmlag.py:324-359), the 2F1 seed series and the Laguerre recurrence; the
+// per-point engine of the basis (sph_point) with the evaluation's sink; the point's east-north-up matrix and the chains of the
+// gradient basis (enu_frame, grad_point: k_grad_sph of vi_basis.hip and K2tg of vi_track.hip).
 #pragma once
 #include "vi_common.h"
 
@@ -262,6 +263,120 @@ __device__ __forceinline__ void eval_point(const SphDev& M, const Geom& g, const
     const double E = exp(-0.5 * g.z);
 #pragma unroll
     for (int t = 0; t < TT; ++t) val[t] = E * sink.acc[t];
+}
+
+// F[3 i + c] = (east, north, up)_i . (model direction z, theta, phi)_c at the point.  The local geodetic unit vectors are
+// rotated as sph_geom rotates the position (Rodrigues, +theta0) and meet the unit vectors of the rotated spherical coordinates
+// there: r' = (s c_phi, s s_phi, x), theta' = (x c_phi, x s_phi, -s), phi' = (-s_phi, c_phi, 0) with s = rho / r.  `up` is the
+// geodetic normal, not the radial direction.
+__device__ __forceinline__ void enu_frame(const SphDev& M, const Geom& g, double lat, double lon, double* F)
+{
+    double sl, cl, so, co;
+    sincos(lat * DEG2RAD, &sl, &cl);
+    sincos(lon * DEG2RAD, &so, &co);
+    const double enu[3][3] = {{-so, co, 0.0}, {-sl * co, -sl * so, cl}, {cl * co, cl * so, sl}};
+    const double st = sqrt(g.Rx * g.Rx + g.Ry * g.Ry) / (M.RE * (g.z / 100.0 + 1.0));
+    const double omc = 1.0 - M.rc;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const double vx = enu[i][0], vy = enu[i][1], vz = enu[i][2];
+        const double kd = M.kx * vx + M.ky * vy;
+        const double wx = vx * M.rc + (M.ky * vz) * M.rs + M.kx * kd * omc;
+        const double wy = vy * M.rc + (-M.kx * vz) * M.rs + M.ky * kd * omc;
+        const double wz = vz * M.rc + (M.kx * vy - M.ky * vx) * M.rs;
+        const double wh = wx * g.cphi + wy * g.sphi;            // component along the horizontal direction of azimuth phi'
+        F[3 * i] = st * wh + g.x * wz;
+        F[3 * i + 1] = g.x * wh - st * wz;
+        F[3 * i + 2] = wy * g.cphi - wx * g.sphi;
+    }
+}
+
+// The chains of the gradient basis at one point, the one copy k_grad_sph and K2tg (k_track_grad_sph) instantiate:
+// sink.term(n, tz, tt, tp, L0k, L1k) is called once per basis function n = k L2 + r; its three gradient components at the point
+// are tz (L0k + 2 L1k), tt L0k and tp L0k - handed over as factors, so that k_grad_sph's sink forms them where that kernel did.
+template <int LCAP, int KCAP, class Sink>
+__device__ __forceinline__ void grad_point(const SphDev& M, const Geom& g, Sink& sink)
+{
+    const int maxl = M.maxl, maxk = M.maxk, L2 = maxl * maxl;
+    double L0[KCAP], L1[KCAP];          // L_k(z) and L^(1)_{k-1}(z)
+    laguerre<KCAP>(maxk, g.z, L0);
+    L1[0] = 0.0;                        // eval_genlaguerre(-1, 1, z) = 0
+    if (KCAP > 1) L1[1] = 1.0;
+    if (KCAP > 2) L1[2] = 2.0 - g.z;
+#pragma unroll
+    for (int k = 3; k < KCAP; ++k) {    // n L^(1)_n = (2n - z) L^(1)_{n-1} - n L^(1)_{n-2},  n = k-1
+        const int n = k - 1;
+        L1[k] = ((2.0 * n - g.z) * L1[k - 1] - (double)n * L1[k - 2]) / (double)n;
+    }
+    const double e = exp(-0.5 * g.z);
+    const double x = g.x, y = g.s;
+    const double inv_hr = 1.0 / (y * (g.z / 100.0 + 1.0) * M.RE);       // 1 / (y (z/100+1) RE)
+    const double zfac = -0.5 * e * 100.0 / M.RE;
+    double cm[LCAP], sm[LCAP];
+    cm[0] = 1.0;
+    sm[0] = 0.0;
+#pragma unroll
+    for (int m = 1; m < LCAP; ++m) {
+        cm[m] = cm[m - 1] * g.cphi - sm[m - 1] * g.sphi;
+        sm[m] = sm[m - 1] * g.cphi + cm[m - 1] * g.sphi;
+    }
+    const double zz = 0.5 * (1.0 - x);
+    for (int gi = 0; gi < M.ngroups; ++gi) {
+        const SphGroupDev G = M.groups[gi];
+        const bool intseed = (G.nterms == 0);
+        double cur[LCAP], prev[LCAP];
+#pragma unroll
+        for (int m = 0; m < LCAP; ++m) { cur[m] = 0.0; prev[m] = 0.0; }
+        double pmm = 1.0, spow = 1.0;
+        for (int j = 0; j <= G.nvmax + 1; ++j) {
+            const double* __restrict__ cj = G.c + (size_t)j * maxl;
+#pragma unroll
+            for (int m = 0; m < LCAP; ++m) {
+                if (m < maxl) {
+                    if (j > m + 1) {
+                        const double nw = fma(x, cur[m], -(cj[m] * prev[m]));
+                        prev[m] = cur[m];
+                        cur[m] = nw;
+                    } else if (j == m) {
+                        if (m > 0) { pmm *= -(2.0 * m - 1.0) * g.s; spow *= g.s; }
+                        if (intseed) cur[m] = pmm;
+                        else cur[m] = G.pref[m] * spow * hyp_series(G.q + (size_t)m * G.nterms, G.nterms, zz);
+                    } else if (j == m + 1) {
+                        prev[m] = cur[m];
+                        if (intseed) cur[m] = x * (2.0 * m + 1.0) * cur[m];
+                        else cur[m] = G.pref[maxl + m] * spow *
+                                      hyp_series(G.q + (size_t)(maxl + m) * G.nterms, G.nterms, zz);
+                    }
+                }
+            }
+            const int l = j >= 1 ? G.pick[j - 1] : -1;      // degree nu_l + 1 reached
+            if (l >= 0) {
+                const int r0 = l * (l + 1);
+                const double v = M.nu[l];
+#pragma unroll
+                for (int m = 0; m < LCAP; ++m) {
+                    if (m <= l) {
+#pragma unroll
+                        for (int sgn = 0; sgn < 2; ++sgn) {
+                            if (sgn == 1 && m == 0) continue;
+                            const int r = sgn ? r0 - m : r0 + m;
+                            const double ms = sgn ? -(double)m : (double)m;            // signed order
+                            const double Q0 = M.scale[r] * prev[m];                      // Kvm * lpmv(m, v, x)
+                            const double Q1 = M.scale1[r] * cur[m];                      // Kvm * lpmv(m, v+1, x)
+                            const double trig = sgn ? sm[m] : cm[m];
+                            const double dtrig = sgn ? (double)m * cm[m] : -(double)m * sm[m];
+                            const double tz = zfac * Q0 * trig;
+                            const double tt = e * (-(v + 1.0) * x * Q0 + (v - ms + 1.0) * Q1) * trig * inv_hr;
+                            const double tp = e * Q0 * dtrig * inv_hr;
+#pragma unroll
+                            for (int k = 0; k < KCAP; ++k)
+                                if (k < maxk) sink.term(k * L2 + r, tz, tt, tp, L0[k], L1[k]);
+                        }
+                    }
+                }
+            }
+        }
+    }
 }
 
 }  // namespace
