@@ -33,6 +33,65 @@
 namespace {
 
 typedef double v4f64 __attribute__((ext_vector_type(4)));
+typedef double v2f64 __attribute__((ext_vector_type(2)));
+
+// ---- the stores of K2r's densities, cache policy a compile-time constant per site ----------------------------------------------
+// K2r writes as many bytes as it reads, nobody reads them again within the call, and every written line that stays in the XCD's
+// L2 takes the place of a line of Y that the sibling timestep tiles of the same points are about to ask for.  The policies, as
+// measured on the bench grid (profiles/r23_k2r_stores.txt; one call of 512 timesteps, 32.5 - 34.4 ms with plain stores):
+#define VI_STORE_PLAIN  0    // global_store_dwordx4            write back
+#define VI_STORE_SC1    1    // global_store_dwordx4 ... sc1    write through: a lane's two 16-byte halves leave L2 one by one as
+                             //                                 partial writes, WRITE_SIZE doubles (53.5 ms at both sites)
+#define VI_STORE_SC0SC1 2    // global_store_dwordx4 ... sc0 sc1   the same (53.6 ms)
+#define VI_STORE_NT     3    // global_store_dwordx4 ... nt     write back, the line first in turn to leave: reads of Y - 11 .. - 25 %
+// The two sites, each with its own constant (make EXTRA="-DVI_K2R_PRODUCT_STORE=3 -DVI_K2R_DEAD_STORE=0" builds a variant
+// library to be selected with VINTERP_LIB; no run-time switch): the product stores of tile_product, 32 bytes per lane, and the
+// NaN stores of the dead pieces in the LIVE branch of k_eval_resident, 16-byte chunks contiguous over the wave.  What ships: nt
+// on the dead stores - whole lines from one instruction, written bytes unchanged, 29.0 - 29.3 ms - and plain product stores: nt
+// there takes another 1.0 ms off (28.1 - 28.2) but a lane's halves then reach HBM apart more often, WRITE_SIZE + 7 %.
+#ifndef VI_K2R_PRODUCT_STORE
+#define VI_K2R_PRODUCT_STORE VI_STORE_PLAIN
+#endif
+#ifndef VI_K2R_DEAD_STORE
+#define VI_K2R_DEAD_STORE VI_STORE_NT
+#endif
+
+// plain and nt are the compiler's own stores.  sc1 and sc0 sc1, kept for the record, are inline asm, not
+// __builtin_amdgcn_raw_buffer_store_b128(..., aux): a buffer store wants a wave-uniform base and a 32-bit offset, one call's tile
+// of densities spans 64 rows of Q doubles (8 GB on a 256^3 grid) and the lanes of the list path hold unrelated pieces - a
+// descriptor per row group, offsets next to the 64-bit addresses and a plain path for the rows that do not fit 32 bits, where
+// this is one route with the addresses the plain store has.  The compiler sees no store in an asm statement, so the statement
+// itself ends with the wait states a 16-byte store needs before a VALU instruction may overwrite its data registers (s_nop 1),
+// and the "memory" clobber orders it against the compiler's own loads and stores.
+#define VI_STORE32_ASM(BITS)                                                                                                      \
+    asm volatile("global_store_dwordx4 %0, %1, off" BITS "\n\tglobal_store_dwordx4 %0, %2, off offset:16" BITS "\n\ts_nop 1"      \
+                 :: "v"(dst), "v"(lo), "v"(hi) : "memory")
+#define VI_STORE16_ASM(BITS) asm volatile("global_store_dwordx4 %0, %1, off" BITS "\n\ts_nop 1" :: "v"(dst), "v"(v) : "memory")
+
+template <int POLICY>
+__device__ __forceinline__ void store32(double* dst, v4f64 v)
+{
+    static_assert(POLICY >= VI_STORE_PLAIN && POLICY <= VI_STORE_NT, "store policy");
+    if constexpr (POLICY == VI_STORE_PLAIN) {
+        *reinterpret_cast<v4f64*>(dst) = v;
+    } else if constexpr (POLICY == VI_STORE_NT) {
+        __builtin_nontemporal_store(v, reinterpret_cast<v4f64*>(dst));
+    } else {
+        const v2f64 lo = {v.x, v.y}, hi = {v.z, v.w};
+        if constexpr (POLICY == VI_STORE_SC1) VI_STORE32_ASM(" sc1");
+        else VI_STORE32_ASM(" sc0 sc1");
+    }
+}
+
+template <int POLICY>
+__device__ __forceinline__ void store16(double* dst, v2f64 v)
+{
+    static_assert(POLICY >= VI_STORE_PLAIN && POLICY <= VI_STORE_NT, "store policy");
+    if constexpr (POLICY == VI_STORE_PLAIN) *reinterpret_cast<v2f64*>(dst) = v;
+    else if constexpr (POLICY == VI_STORE_NT) __builtin_nontemporal_store(v, reinterpret_cast<v2f64*>(dst));
+    else if constexpr (POLICY == VI_STORE_SC1) VI_STORE16_ASM(" sc1");
+    else VI_STORE16_ASM(" sc0 sc1");
+}
 
 constexpr int RT = 4;        // row tiles (16 timesteps each) per wave
 constexpr int PF = 4;        // k-steps of B in flight
@@ -120,7 +179,7 @@ __device__ __forceinline__ void tile_product(const double* shA, int lane, int g,
             for (int v = 0; v < 4; ++v) {
                 const int64_t t = t0 + 16 * i + g + 4 * v;
                 if (t < T)
-                    *reinterpret_cast<v4f64*>(out + t * Q + qa) = (v4f64){D[i][0][v], D[i][1][v], D[i][2][v], D[i][3][v]};
+                    store32<VI_K2R_PRODUCT_STORE>(out + t * Q + qa, (v4f64){D[i][0][v], D[i][1][v], D[i][2][v], D[i][3][v]});
             }
     }
 }
@@ -170,7 +229,7 @@ __global__ __launch_bounds__(256, 2) void k_eval_resident(int N, int KSp, int64_
         __shared__ int shCnt[4];                              // live pieces per wave's share of the batch
         const int wv = __builtin_amdgcn_readfirstlane(wave);                       // uniform: the loops below are scalar
         const int nt = (int)((T - t0) < 16 * RT ? (T - t0) : 16 * RT);             // timesteps of this tile
-        const v4f64 nan4 = {__builtin_nan(""), __builtin_nan(""), __builtin_nan(""), __builtin_nan("")};
+        const v2f64 nan2 = {__builtin_nan(""), __builtin_nan("")};
         bool staged = false;
         for (int gb0 = 0; gb0 < groups; gb0 += LIVE_BATCH) {
             const int64_t q0 = (pg * groups + gb0) * 256;                           // first point of the batch
@@ -216,13 +275,21 @@ __global__ __launch_bounds__(256, 2) void k_eval_resident(int N, int KSp, int64_
             // ---- dead pieces: NaN at the timesteps of this tile (the bits the product gives for a column of NaNs as
             // k_mask_basis writes them; a row-0 NaN of another payload or sign in a caller's own Y gives this NaN too, where the
             // plain loop carries the caller's through), by the wave that looked at them, before the product (measured: after
-            // it, or a round after each chunk, 4 % slower)
+            // it, or a round after each chunk, 4 % slower).  The 64 pieces of a round are 2048 contiguous bytes of a row and every
+            // dead one gets the same bits, so the lanes do not store their own piece (16 bytes at a stride of 32 per instruction:
+            // half-written lines) but the 16-byte chunks ln and 64 + ln of the round, where those belong to a dead piece: an
+            // instruction writes whole lines wherever a run of pieces is dead, and the same bytes in all.
+#pragma unroll
             for (int it = 0; it < LIVE_PIECES / 256; ++it) {
-                const bool dead = (dd >> it) & 1;
-                if (__ballot(dead) == 0) continue;
-                double* o = out + t0 * Q + q0 + 4 * (wv * (LIVE_PIECES / 4) + it * 64 + ln);
-                if (dead)
-                    for (int tl = 0; tl < nt; ++tl) *reinterpret_cast<v4f64*>(o + (int64_t)tl * Q) = nan4;
+                const unsigned long long m = __ballot((dd >> it) & 1);
+                if (m == 0) continue;
+                double* o = out + t0 * Q + q0 + 4 * (wv * (LIVE_PIECES / 4) + it * 64);   // the round's first piece
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const int c = 64 * h + ln;                                          // chunk c: a half of piece c >> 1
+                    if ((m >> (c >> 1)) & 1)
+                        for (int tl = 0; tl < nt; ++tl) store16<VI_K2R_DEAD_STORE>(o + 2 * c + (int64_t)tl * Q, nan2);
+                }
             }
             if (nlive == 0) continue;
             if (!staged) {                                                          // a workgroup without a live piece never needs it
@@ -726,8 +793,6 @@ int vi_eval_resident_mfma(vi_ctx* c, int N, int64_t Q, int64_t T, const double* 
 // Bound: the fp64 matrix peak, N_p (N_p + 16) flop issued per point-timestep (N_p = 16 NB; 23 040 at N = 144) against
 // 8 (N / T_concurrent + 1) bytes.
 namespace {
-
-typedef double v2f64 __attribute__((ext_vector_type(2)));
 
 constexpr int ERR_WAVES = 8;                              // waves per workgroup
 constexpr int ERR_PTS = ERR_WAVES * 32;                   // points per workgroup and group (= RUN_PTS, the block of K2te's walk)
