@@ -364,6 +364,28 @@ int  vi_eval_records_gradcov_f64(vi_model* model, int64_t Q, const double* d_G, 
 int  vi_eval_track_grad_cov_f64(vi_model* model, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt,
                                 const int32_t* d_rec, const double* d_w, int64_t R, const double* d_dC,
                                 const double* d_hull_eq, int32_t F, double hull_tol, int32_t frame, double* d_out);
+/* SECOND derivatives of the fitted parameter (the reference has none; its grad_basis, sphharmlag.py:148-184, stops at the first):
+ * the Hessian of a basis function f = g(r) T(theta') A(phi') in closed form - Legendre's equation gives T'', the azimuth
+ * A'' = -m^2 A, the radial part one more generalised-Laguerre recurrence - as a true tensor in 1/m^2 times the function's unit:
+ * the second covariant derivatives in the orthonormal frame of the gradient, (r', theta', phi') of the rotated cap
+ * (VI_FRAME_MODEL) or east, north, geodetic up (VI_FRAME_ENU: F H F^T with the point's matrix of vi_eval_grad_basis_f64, on the
+ * device; entry (2, 2) is then the second derivative along the ellipsoid's normal, the horizontal entries second derivatives
+ * along straight tangent lines, not along curves of constant altitude).  Its six distinct entries are packed in the order of
+ * the gradient covariance, (0,0) (1,1) (2,2) (0,1) (0,2) (1,2); their first three add up to the Laplacian in either frame.
+ *   vi_eval_hess_f64        d_out[k*Q + q] = sum_n hess_basis[q][k][n] * d_C[n], (6, Q) planar, for ONE coefficient vector; the
+ *                           6N values of a point are never formed.
+ *   vi_eval_hess_basis_f64  d_H[(n*6 + k)*Q + q], N x 6 x Q doubles: the Hessian basis of a resident grid, a matrix of the kind
+ *                           vi_eval_grad_basis_f64 makes - vi_eval_resident_f64 with 6Q for Q gives the Hessian maps of T
+ *                           timesteps, out[(t*6 + k)*Q + q].
+ * Both run the hull pass of vi_eval_grad_cov_f64 first (F = 0: no test) and write NaN into every entry of a point that fails it.
+ * Non-finite at the pole of the cap (sin theta' = 0), as the gradient is; next to it the accuracy falls as eps / sin^2 theta'.
+ * Models and orders as vi_grad_basis_f64 - sphharmlag within (6, 4), (12, 8) or (2, 12) -, others return VI_ERR_UNSUPPORTED and
+ * launch nothing.  Q = 0 is a no-op.  Kernel k_hess_sph (csrc/vi_hess.hip), a lane per point.  Asynchronous on the context's
+ * stream; timed for vi_eval_kernel_ms like their siblings (tests/test_gpu_hessian.py). */
+int  vi_eval_hess_f64(vi_model* model, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt,
+                      const double* d_C, const double* d_hull_eq, int32_t F, double hull_tol, int32_t frame, double* d_out);
+int  vi_eval_hess_basis_f64(vi_model* model, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt,
+                            const double* d_hull_eq, int32_t F, double hull_tol, int32_t frame, double* d_H);
 /* Column maps of many timesteps on the same resident grid, without the volume.  The grid is seen as (outer, L, inner), point
  * q = (o*L + l)*inner + i, column m = o*inner + i: any axis of a C-ordered grid, the last one with inner = 1.  What a user of
  * Estimate.__call__ (estimate.py:110-123) takes from a (lat, lon, alt) volume per column: the peak of the parameter along
@@ -399,7 +421,7 @@ int    vi_reduce_basis_f64(vi_model* model, int64_t outer, int64_t L, int64_t in
  * others return VI_ERR_UNSUPPORTED from vi_eval_f64 while the flag is set. */
 int  vi_model_set_eval_precision(vi_model* model, int32_t chain_f32);
 /* device time (ms) of the evaluation kernel launches of the last vi_eval_f64 / vi_eval_track_f64 / vi_eval_track_grad_f64 / vi_eval_slant_f64 / vi_eval_slant_basis_f64 / vi_eval_resident_f64 /
- * vi_eval_resident_err_f64 / vi_eval_resident_err_at_f64 / vi_eval_resident_gradcov_f64 / vi_eval_grad_cov_f64 (its last chunk) / vi_eval_records_gradcov_f64 / vi_eval_track_grad_cov_f64 /vi_eval_resident_peak_f64 call on this context, from HIP events recorded on the context's stream around them (the preparation kernels are excluded).
+ * vi_eval_resident_err_f64 / vi_eval_resident_err_at_f64 / vi_eval_resident_gradcov_f64 / vi_eval_grad_cov_f64 (its last chunk) / vi_eval_hess_f64 / vi_eval_hess_basis_f64 / vi_eval_records_gradcov_f64 / vi_eval_track_grad_cov_f64 /vi_eval_resident_peak_f64 call on this context, from HIP events recorded on the context's stream around them (the preparation kernels are excluded).
  * The events are recorded only while vi_ctx_set_eval_timing(ctx, 1) is in force (default: off - the pair costs a 0.2 ms call about 7 us);
  * vi_eval_kernel_ms fails with VI_ERR_ARG while it is off or before a call has been timed. */
 int  vi_ctx_set_eval_timing(vi_ctx* ctx, int32_t on);

@@ -1,7 +1,8 @@
 // Device helpers shared by the basis / evaluation kernels (vi_basis.hip, vi_eval.hip, vi_track.hip, vi_slant.hip,
 // vi_eval_mfma.hip): geodetic -> model coordinates (sphharmlag.py:324-359), the 2F1 seed series and the Laguerre recurrence; the
 // per-point engine of the basis (sph_point) with the evaluation's sink; the point's east-north-up matrix and the chains of the
-// gradient basis (enu_frame, grad_point: k_grad_sph of vi_basis.hip and K2tg of vi_track.hip).
+// gradient basis (enu_frame, grad_point: k_grad_sph of vi_basis.hip and K2tg of vi_track.hip) and, on the same walk, of the
+// Hessian basis (hess_point: k_hess_sph of vi_hess.hip).
 #pragma once
 #include "vi_common.h"
 
@@ -291,11 +292,24 @@ __device__ __forceinline__ void enu_frame(const SphDev& M, const Geom& g, double
     }
 }
 
-// The chains of the gradient basis at one point, the one copy k_grad_sph and K2tg (k_track_grad_sph) instantiate:
-// sink.term(n, tz, tt, tp, L0k, L1k) is called once per basis function n = k L2 + r; its three gradient components at the point
-// are tz (L0k + 2 L1k), tt L0k and tp L0k - handed over as factors, so that k_grad_sph's sink forms them where that kernel did.
-template <int LCAP, int KCAP, class Sink>
-__device__ __forceinline__ void grad_point(const SphDev& M, const Geom& g, Sink& sink)
+// The chains of the gradient basis at one point and, with HESS, of the Hessian basis on the same walk - one copy of the Legendre
+// seeds and recurrences for both (grad_point, hess_point below).  When chain m of a group has reached degree nu_l + 1, prev holds
+// P at nu_l and cur at nu_l + 1: Q0 = Kvm lpmv(ms, v, x), Q1 = Kvm lpmv(ms, v+1, x) for the signed orders ms = +-m.
+//   gradient: sink.term(n, tz, tt, tp, L0k, L1k) once per basis function n = k L2 + r; its three gradient components at the point
+//             are tz (L0k + 2 L1k), tt L0k and tp L0k - handed over as factors, so that k_grad_sph's sink forms them where that
+//             kernel did.
+//   Hessian:  with the basis function f = g(r) T(theta') A(phi'), r = RE (z/100 + 1), a = 100/RE,
+//               g0 = e L0,  g1 = dg/dr = -e/2 (L0 + 2 L1) a,  g2 = d2g/dr2 = e (L0/4 + L1 + L2) a^2,  L2 = L^(2)_{k-2}(z),
+//               T = Q0,  T' = dT/dtheta' = (-(v+1) x Q0 + (v-ms+1) Q1) / y,  T'' = -(x/y) T' - (v(v+1) - m^2/y^2) T
+//               (Legendre's equation),  A'' = -m^2 A,
+//             the second covariant derivatives in the orthonormal frame (r', theta', phi') of the gradient, in 1/m^2:
+//               H_rr = g2 T A                                        H_rt = (g1/r - g0/r^2) T' A
+//               H_tt = g0 T'' A / r^2 + g1 T A / r                   H_rp = (g1/r - g0/r^2) T A' / y
+//               H_pp = g0 (T A''/y^2 + x T' A/y) / r^2 + g1 T A / r  H_tp = g0 A' (T'/y - x T/y^2) / r^2
+//             sink.term(n, h) once per basis function with h[6] in the packed order rr, tt, pp, rt, rp, tp - (0,0) (1,1) (2,2)
+//             (0,1) (0,2) (1,2), the gradient covariance's.  Non-finite at the pole of the cap (y = 0), as the gradient is.
+template <int LCAP, int KCAP, bool HESS, class Sink>
+__device__ __forceinline__ void grad_hess_point(const SphDev& M, const Geom& g, Sink& sink)
 {
     const int maxl = M.maxl, maxk = M.maxk, L2 = maxl * maxl;
     double L0[KCAP], L1[KCAP];          // L_k(z) and L^(1)_{k-1}(z)
@@ -312,6 +326,25 @@ __device__ __forceinline__ void grad_point(const SphDev& M, const Geom& g, Sink&
     const double x = g.x, y = g.s;
     const double inv_hr = 1.0 / (y * (g.z / 100.0 + 1.0) * M.RE);       // 1 / (y (z/100+1) RE)
     const double zfac = -0.5 * e * 100.0 / M.RE;
+    // the Hessian's radial factors of every k: g0, g1/r and g2
+    constexpr int HK = HESS ? KCAP : 1;
+    double G0[HK], G1[HK], G2[HK];
+    const double inv_r = 1.0 / ((g.z / 100.0 + 1.0) * M.RE), inv_y = 1.0 / y;
+    const double inv_r2 = inv_r * inv_r, inv_y2 = inv_y * inv_y;
+    if constexpr (HESS) {
+        const double a = 100.0 / M.RE;
+        double Lb = 0.0, La = 0.0;      // L^(2)_{k-3}, L^(2)_{k-2}:  n L^(2)_n = (2n + 1 - z) L^(2)_{n-1} - (n + 1) L^(2)_{n-2}
+#pragma unroll
+        for (int k = 0; k < KCAP; ++k) {
+            const int n = k - 2;
+            const double Lc = n < 0 ? 0.0 : n == 0 ? 1.0 : ((2.0 * n + 1.0 - g.z) * La - (double)(n + 1) * Lb) / (double)n;
+            Lb = La;
+            La = Lc;
+            G0[k] = e * L0[k];
+            G1[k] = (-0.5 * e * a * inv_r) * (L0[k] + 2.0 * L1[k]);
+            G2[k] = (e * a * a) * (0.25 * L0[k] + L1[k] + Lc);
+        }
+    }
     double cm[LCAP], sm[LCAP];
     cm[0] = 1.0;
     sm[0] = 0.0;
@@ -365,18 +398,54 @@ __device__ __forceinline__ void grad_point(const SphDev& M, const Geom& g, Sink&
                             const double Q1 = M.scale1[r] * cur[m];                      // Kvm * lpmv(m, v+1, x)
                             const double trig = sgn ? sm[m] : cm[m];
                             const double dtrig = sgn ? (double)m * cm[m] : -(double)m * sm[m];
-                            const double tz = zfac * Q0 * trig;
-                            const double tt = e * (-(v + 1.0) * x * Q0 + (v - ms + 1.0) * Q1) * trig * inv_hr;
-                            const double tp = e * Q0 * dtrig * inv_hr;
+                            if constexpr (!HESS) {
+                                const double tz = zfac * Q0 * trig;
+                                const double tt = e * (-(v + 1.0) * x * Q0 + (v - ms + 1.0) * Q1) * trig * inv_hr;
+                                const double tp = e * Q0 * dtrig * inv_hr;
 #pragma unroll
-                            for (int k = 0; k < KCAP; ++k)
-                                if (k < maxk) sink.term(k * L2 + r, tz, tt, tp, L0[k], L1[k]);
+                                for (int k = 0; k < KCAP; ++k)
+                                    if (k < maxk) sink.term(k * L2 + r, tz, tt, tp, L0[k], L1[k]);
+                            } else {
+                                const double m2 = (double)(m * m);
+                                const double Tp = (-(v + 1.0) * x * Q0 + (v - ms + 1.0) * Q1) * inv_y;
+                                const double Tpp = -(x * inv_y) * Tp - (v * (v + 1.0) - m2 * inv_y2) * Q0;
+                                const double TA = Q0 * trig;
+                                const double a_tt = Tpp * trig * inv_r2;
+                                const double a_pp = (x * inv_y * Tp - m2 * inv_y2 * Q0) * trig * inv_r2;
+                                const double a_rt = Tp * trig;
+                                const double a_rp = Q0 * dtrig * inv_y;
+                                const double a_tp = dtrig * (Tp - x * inv_y * Q0) * inv_y * inv_r2;
+#pragma unroll
+                                for (int k = 0; k < KCAP; ++k) {
+                                    if (k < maxk) {
+                                        const double dr = G1[k] * TA;                          // g1 T A / r
+                                        const double gd = fma(-G0[k], inv_r2, G1[k]);          // g1/r - g0/r^2
+                                        const double h[6] = {G2[k] * TA,  fma(G0[k], a_tt, dr), fma(G0[k], a_pp, dr),
+                                                             gd * a_rt,   gd * a_rp,            G0[k] * a_tp};
+                                        sink.term(k * L2 + r, h);
+                                    }
+                                }
+                            }
                         }
                     }
                 }
             }
         }
     }
+}
+
+// the gradient basis at one point: the one copy k_grad_sph and K2tg (k_track_grad_sph) instantiate
+template <int LCAP, int KCAP, class Sink>
+__device__ __forceinline__ void grad_point(const SphDev& M, const Geom& g, Sink& sink)
+{
+    grad_hess_point<LCAP, KCAP, false>(M, g, sink);
+}
+
+// the Hessian basis at one point (k_hess_sph, vi_hess.hip)
+template <int LCAP, int KCAP, class Sink>
+__device__ __forceinline__ void hess_point(const SphDev& M, const Geom& g, Sink& sink)
+{
+    grad_hess_point<LCAP, KCAP, true>(M, g, sink);
 }
 
 }  // namespace

@@ -400,7 +400,7 @@ class Estimate(object):
                                              out.ctypes.data_as(P)), 'vi_eval_f64_host')
         return out
 
-    def resident_grid(self, gdlat, gdlon, gdalt, check_hull=True, gradient=None):
+    def resident_grid(self, gdlat, gdlon, gdalt, check_hull=True, gradient=None, hessian=None):
         """The points of a grid that MANY timesteps are going to be evaluated on (the reference calls Estimate.__call__ once
         per timestep and rebuilds the basis of the grid every time, estimate.py:110-115): their basis matrix is assembled once
         and stays in device memory (N x Q doubles - 19 GB at the default order on a 256^3 grid), and every batch of timesteps
@@ -409,8 +409,12 @@ class Estimate(object):
         `gradient`: None (no gradient maps, nothing more allocated), 'model' or 'enu' - the grid also keeps its gradient basis
         (N x 3 x Q doubles, three times the basis matrix: 57 GB of the 76 GB the two take at the default order on 256^3) and
         ResidentGrid.gradient / evaluate_gradients give the gradient maps of many timesteps as one product, with components
-        along the model coordinates (z, theta, phi, as Estimate.gradient) or along local east, north, up."""
-        return ResidentGrid(self, gdlat, gdlon, gdalt, check_hull, gradient)
+        along the model coordinates (z, theta, phi, as Estimate.gradient) or along local east, north, up.
+
+        `hessian`: None, 'model' or 'enu' in the same way - the grid also keeps its Hessian basis (N x 6 x Q doubles, six times
+        the basis matrix, counted in the free-memory check) and ResidentGrid.hessian / evaluate_hessians / laplacian give the
+        maps of the second derivatives (Estimate.hessian's entries, packed in GRADCOV_PAIRS order) as one product."""
+        return ResidentGrid(self, gdlat, gdlon, gdalt, check_hull, gradient, hessian)
 
     def resident_rays(self, start, end, nodes=64, rule=None, coords='geodetic', check_hull=True):
         """The rays of a fixed geometry that MANY timesteps are going to be integrated along (an all-sky imager's lines of
@@ -461,6 +465,45 @@ class Estimate(object):
         packed = self._gradient_covariance(time, gdlat, gdlon, gdalt, check_hull, frame)
         with np.errstate(invalid='ignore'):
             return np.sqrt(packed[:3].T).reshape(np.shape(gdlat) + (3,))
+
+    def hessian(self, time, gdlat, gdlon, gdalt, check_hull=True, frame='model'):
+        """Hessian of the fitted parameter at the points: array of shape gdlat.shape + (3, 3), symmetric, in the parameter's
+        unit per m^2 - the second covariant derivatives (a true tensor) in the orthonormal frame of gradient: (r', theta',
+        phi') of the rotated cap, or with frame='enu' local east, north, up, H_enu = F H F^T with Model.gradient_frame's F.
+        [..., 2, 2] of frame='enu' is exactly the second derivative along the geodetic normal - the curvature of a layer at
+        its peak; the horizontal entries are second derivatives along straight tangent lines, not along curves of constant
+        altitude (those differ by the first derivative along `up` over the radius of curvature).  Closed form, no differences:
+        the reference has no counterpart.  NaN outside the hull; non-finite at the pole of the cap (sin theta' = 0), as
+        gradient is there, and next to it the accuracy falls as eps / sin^2 theta'.  One library call (vi_eval_hess_f64):
+        hull test, frame and the contraction with the coefficients on the device, the (Q, 6, N) basis is never formed.
+        sphharmlag only, at the orders of gradient."""
+        return gradcov_matrix(self._hessian(time, gdlat, gdlon, gdalt, check_hull, frame)).reshape(np.shape(gdlat) + (3, 3))
+
+    def laplacian(self, time, gdlat, gdlon, gdalt, check_hull=True):
+        """Laplacian of the fitted parameter at the points, shape of gdlat: the trace of hessian (the same in either frame)."""
+        p = self._hessian(time, gdlat, gdlon, gdalt, check_hull, 'model')
+        return (p[0] + p[1] + p[2]).reshape(np.shape(gdlat))
+
+    def _hessian(self, time, gdlat, gdlon, gdalt, check_hull, frame):
+        """What hessian and laplacian share: the packed (6, Q) result of vi_eval_hess_f64, entries in GRADCOV_PAIRS order."""
+        if frame not in GRADIENT_FRAMES:
+            raise ValueError("frame must be 'model' or 'enu', not %r" % (frame,))
+        C, dC = self.get_C(time)
+        C = np.ascontiguousarray(C, dtype=np.float64)
+        if C.shape != (self.model.nbasis,):
+            raise ValueError('coefficient vector length %d != nbasis %d' % (C.size, self.model.nbasis))
+        lat, lon, alt = ravel_points(gdlat, gdlon, gdalt)
+        Q = lat.size
+        if Q == 0:
+            return np.empty((6, 0))
+        eq, F, tol = self._hull_args(check_hull)
+        with self.model.ctx.scope() as dev:
+            dlat, dlon, dalt, dC_ = dev.up(lat), dev.up(lon), dev.up(alt), dev.up(C)
+            dO = dev.empty((6, Q))
+            _lib.check(_lib.lib.vi_eval_hess_f64(self.model.handle(), Q, dlat.ptr, dlon.ptr, dalt.ptr, dC_.ptr,
+                                                 _ptr(None if eq is None else dev.up(eq)), F, tol, GRADIENT_FRAMES[frame],
+                                                 dO.ptr), 'vi_eval_hess_f64')
+            return dO.download()
 
     def _need_covariance(self):
         if self.Covariance is None:
@@ -721,44 +764,54 @@ class Estimate(object):
 class ResidentGrid(object):
     """Basis matrix of a fixed set of points, resident on the device (Estimate.resident_grid)."""
 
-    def __init__(self, est, gdlat, gdlon, gdalt, check_hull=True, gradient=None):
+    def __init__(self, est, gdlat, gdlon, gdalt, check_hull=True, gradient=None, hessian=None):
         if gradient is not None and gradient not in GRADIENT_FRAMES:
             raise ValueError("gradient must be None, 'model' or 'enu', not %r" % (gradient,))
+        if hessian is not None and hessian not in GRADIENT_FRAMES:
+            raise ValueError("hessian must be None, 'model' or 'enu', not %r" % (hessian,))
         shape = np.asarray(gdlat).shape
         lat, lon, alt = ravel_points(gdlat, gdlon, gdalt)
 
         def build(up, hp, F, tol):
             h, Q = est.model.handle(), lat.size
             dlat, dlon, dalt = up(lat), up(lon), up(alt)
-            if gradient is not None:    # first: the call that refuses a model or an order
+            if gradient is not None:    # first: the calls that refuse a model or an order
                 _lib.check(_lib.lib.vi_eval_grad_basis_f64(h, Q, dlat.ptr, dlon.ptr, dalt.ptr, hp, F, tol,
                                                            GRADIENT_FRAMES[gradient], self.dG.ptr), 'vi_eval_grad_basis_f64')
+            if hessian is not None:
+                _lib.check(_lib.lib.vi_eval_hess_basis_f64(h, Q, dlat.ptr, dlon.ptr, dalt.ptr, hp, F, tol,
+                                                           GRADIENT_FRAMES[hessian], self.dH.ptr), 'vi_eval_hess_basis_f64')
             _lib.check(_lib.lib.vi_eval_basis_f64(h, Q, dlat.ptr, dlon.ptr, dalt.ptr, hp, F, tol, self.dY.ptr), 'vi_eval_basis_f64')
-        self._setup(est, shape, lat.size, check_hull, gradient, build)
+        self._setup(est, shape, lat.size, check_hull, gradient, build, hessian)
 
-    def _setup(self, est, shape, Q, check_hull, gradient, build):
+    def _setup(self, est, shape, Q, check_hull, gradient, build, hessian=None):
         """What every resident matrix shares: the state, the free-memory check, the allocation of dY (N x Q) and - with a
-        gradient frame - dG, and build(up, hull pointer, F, tol) filling them: up(host array[, dtype]) gives a device copy in
-        the scope of the set-up, freed when it ends whatever happens.  A failed set-up closes the object."""
+        gradient frame - dG, with a Hessian frame dH, and build(up, hull pointer, F, tol) filling them: up(host array[, dtype])
+        gives a device copy in the scope of the set-up, freed when it ends whatever happens.  A failed set-up closes the
+        object."""
         self.est = est
         self.frame = gradient
+        self.hessian_frame = hessian
         self.shape = shape
         self.Q = Q
         ctx = est.model.ctx
         N = est.model.nbasis
         free, _ = ctx.mem_info()
-        nmat = 1 if gradient is None else 4             # the basis matrix, and three times as much for the gradient basis
+        # the basis matrix, three times as much for the gradient basis, six times as much for the Hessian basis
+        nmat = 1 + (0 if gradient is None else 3) + (0 if hessian is None else 6)
         if nmat * self.Q * N * 8 > 0.9 * free:
+            also = [what for what, frame in (('gradient basis', gradient), ('Hessian basis', hessian)) if frame is not None]
             raise MemoryError('basis matrix%s of %d points x %d functions (%.1f GB) does not fit the device (%.1f GB free)'
-                              % ('' if gradient is None else ' and gradient basis', self.Q, N, nmat * self.Q * N * 8 / 1e9,
-                                 free / 1e9))
-        self.dY = self.dG = None
+                              % (''.join(' and ' + what for what in also), self.Q, N, nmat * self.Q * N * 8 / 1e9, free / 1e9))
+        self.dY = self.dG = self.dH = None
         self._reduced = {}              # (axis, weight bytes) -> reduced basis on the device (evaluate_integrals)
-        with ctx.scope() as dev:        # the temporaries of the set-up; dY and dG are the object's
+        with ctx.scope() as dev:        # the temporaries of the set-up; dY, dG and dH are the object's
             try:
                 self.dY = ctx.empty((N, self.Q))
                 if gradient is not None:
                     self.dG = ctx.empty((N, 3, self.Q))
+                if hessian is not None:
+                    self.dH = ctx.empty((N, 6, self.Q))
                 if self.Q == 0:
                     return
                 eq, F, tol = est._hull_args(check_hull)
@@ -868,6 +921,35 @@ class ResidentGrid(object):
         Estimate.gradient is."""
         self._need_gradient_basis()
         return self.evaluate_gradients(self._coeffs_at(times)).reshape((len(times), 3) + tuple(self.shape))
+
+    def _need_hessian_basis(self):
+        if self.hessian_frame is None:
+            raise ValueError("this ResidentGrid holds no Hessian basis: build it with resident_grid(..., hessian='model') "
+                             "or hessian='enu'")
+
+    def evaluate_hessians(self, C, out=None):
+        """out[t, k] = entry GRADCOV_PAIRS[k] of the Hessian of the parameter with coefficient row C[t] on the grid; (T, 6, Q)
+        host array, packed (gradcov_matrix unpacks it), in the frame the grid was built with (hessian=).  The same product as
+        evaluate_coeffs on the Hessian basis: 6Q columns."""
+        self._need_hessian_basis()
+        C, out, slab = self._slabs(C, out, (6, self.Q))
+        if slab == 0:
+            return out
+        return self._products(self._open(self.dH), 6 * self.Q, C, out, slab)
+
+    def hessian(self, times):
+        """Hessian maps at the grid for a list of datetimes (coefficients of Estimate.get_C per time): array (len(times), 6) +
+        grid shape, the six distinct entries in the order of GRADCOV_PAIRS, in 1/m^2 times the parameter's unit and in the frame
+        of hessian= - see Estimate.hessian for what the entries are.  NaN outside the hull and for a timestep whose
+        coefficients are NaN; non-finite at the pole of the cap."""
+        self._need_hessian_basis()
+        return self.evaluate_hessians(self._coeffs_at(times)).reshape((len(times), 6) + tuple(self.shape))
+
+    def laplacian(self, times):
+        """Laplacian maps at the grid for a list of datetimes: array (len(times),) + grid shape, the sum of the first three
+        planes of hessian (the trace, the same in either frame)."""
+        H = self.hessian(times)
+        return (H[:, 0] + H[:, 1]) + H[:, 2]
 
     def _covariances(self, dC):
         """The covariances of a batch as (T, N, N) float64, checked."""
@@ -1153,9 +1235,9 @@ class ResidentGrid(object):
         return self.evaluate_integral_errors(self._covariances_at(times), weights=weights, axis=axis).reshape(rest)
 
     def close(self):
-        """Give the basis matrix (the gradient basis, the reduced bases of evaluate_integrals) back to the device (idempotent).  Also runs
-        on `with est.resident_grid(...) as g:` exit and when the object is collected."""
-        for name in ('dY', 'dG'):
+        """Give the basis matrix (the gradient basis, the Hessian basis, the reduced bases of evaluate_integrals) back to the device
+        (idempotent).  Also runs on `with est.resident_grid(...) as g:` exit and when the object is collected."""
+        for name in ('dY', 'dG', 'dH'):
             a = getattr(self, name, None)
             setattr(self, name, None)
             if a is not None:

@@ -219,6 +219,27 @@ class Model(DeviceModel):
                        'vi_grad_basis_f64')
             return dG.download()
 
+    def hess_basis(self, gdlat, gdlon, gdalt, frame='model'):
+        """Hessian of every basis function: (P, 6, N), the six distinct second covariant derivatives in 1/m^2 in the packed
+        order (0,0) (1,1) (2,2) (0,1) (0,2) (1,2) of estimate.GRADCOV_PAIRS, in the orthonormal frame of grad_basis
+        (frame='model': r', theta', phi' of the rotated cap) or along local east, north, up (frame='enu': F H F^T with
+        gradient_frame's F, on the device).  Closed form (csrc/vi_sph_device.h, hess_point); the reference has no counterpart.
+        Non-finite at the pole of the cap, as grad_basis is.  1-D inputs, no hull test."""
+        frames = {'model': _lib.VI_FRAME_MODEL, 'enu': _lib.VI_FRAME_ENU}
+        if frame not in frames:
+            raise ValueError("frame must be 'model' or 'enu', not %r" % (frame,))
+        gdlat = np.asarray(gdlat, dtype=np.float64)
+        P, N = gdlat.size, self.nbasis
+        if P == 0:
+            return np.zeros((0, 6, N))
+        h = self.handle()
+        with self._ctx.scope() as dev:
+            dlat, dlon, dalt = self._upload_coords(dev, gdlat, gdlon, gdalt)
+            dH = dev.empty((N, 6, P))
+            _lib.check(_lib.lib.vi_eval_hess_basis_f64(h, P, dlat.ptr, dlon.ptr, dalt.ptr, None, 0, 0., frames[frame], dH.ptr),
+                       'vi_eval_hess_basis_f64')
+            return np.ascontiguousarray(dH.download().reshape(N, 6, P).transpose(2, 1, 0))
+
     def gradient_frame(self, gdlat, gdlon, gdalt):
         """(P, 3, 3) matrices M with g_enu = M @ g_model: the components of a gradient along the model coordinates
         (z, theta, phi of the rotated cap, as grad_basis gives them) turned into local east, north, up - `up` the geodetic

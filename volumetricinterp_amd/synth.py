@@ -53,6 +53,14 @@ def synth_records(A, T, seed0=1000):
     return np.array(vals), np.array(errs)
 
 
+def chapman_record(alt, nmax=3e11, hm=300e3, scale=50e3):
+    """One noise-free record of a Chapman-like layer at the altitudes `alt` (m): peak density nmax at hm, scale height
+    `scale` - a layer with a curvature to measure (Estimate.hessian).  Returns value, error (5 % + 1e10, as synth_record)."""
+    zeta = (np.asarray(alt, dtype=np.float64) - hm) / scale
+    value = nmax * np.exp(0.5 * (1. - zeta - np.exp(-zeta)))
+    return value, 0.05 * value + 1e10
+
+
 def unix_times(T, t0=1480286700.0, dt=60.0):
     """(T,2) start/end Unix times, 2016-11-27T22:45:00Z onwards, 1-minute records."""
     s = t0 + dt * np.arange(T)
