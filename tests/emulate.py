@@ -21,10 +21,32 @@ def geom(tb, lat, lon, alt):
     return dict(x=x, s=np.sqrt(1 - x * x), cphi=Rx / rho, sphi=Ry / rho, z=100 * (r / RE - 1))
 
 
+def seed_limit(q):
+    """SphGroupDev.zzmax as vi_model_create forms it (seed_limit, csrc/vi_api.hip): the largest (1 - x)/2 in [0, 1], by bisection,
+    at which every seed series of the table q (series, terms) meets the exit test at the end of its table."""
+    def converge(zz):
+        r = np.ones(len(q))
+        ssum = np.ones(len(q))
+        for i in range(q.shape[1]):
+            r = r * q[:, i] * zz
+            ssum = ssum + r
+        return bool(np.all(np.abs(r) <= 1e-17 * np.abs(ssum)))
+    if converge(1.0):
+        return 1.0
+    lo, hi = 0.0, 1.0
+    for _ in range(60):
+        mid = 0.5 * (lo + hi)
+        if converge(mid):
+            lo = mid
+        else:
+            hi = mid
+    return lo
+
+
 def basis_from_tables(tb, maxk, maxl, lat, lon, alt):
     g = geom(tb, np.asarray(lat, float), np.asarray(lon, float), np.asarray(alt, float))
     P = g['x'].size
-    x, s, zz = g['x'], g['s'], 0.5 * (1 - g['x'])
+    x, s, zz0 = g['x'], g['s'], 0.5 * (1 - g['x'])
     cm = [np.ones(P)]
     sm = [np.zeros(P)]
     for m in range(1, maxl):
@@ -41,6 +63,8 @@ def basis_from_tables(tb, maxk, maxl, lat, lon, alt):
         prev = [np.zeros(P) for _ in range(maxl)]
         pmm = np.ones(P)
         spow = np.ones(P)
+        # seed_arg of csrc/vi_sph_device.h: past the group's limit the argument of the seed series, and so the seeds, are NaN
+        zz = zz0 if G['nterms'] == 0 else np.where(zz0 <= seed_limit(G['q'].reshape(-1, G['nterms'])), zz0, np.nan)
 
         def hyp(q):
             r = np.ones(P)

@@ -321,6 +321,35 @@ extern "C" void vi_model_destroy(vi_model* m)
     delete m;
 }
 
+// whether each of the nser seed series q[s][0 .. nterms-1] meets the exit test of hyp_series (vi_sph_device.h) at the end of its
+// table at the argument zz
+static bool seeds_converge(const double* q, int nser, int nterms, double zz)
+{
+    for (int s = 0; s < nser; ++s) {
+        double r = 1.0, sum = 1.0;
+        for (int i = 0; i < nterms; ++i) {
+            r *= q[(size_t)s * nterms + i] * zz;
+            sum += r;
+        }
+        if (!(fabs(r) <= 1e-17 * fabs(sum))) return false;
+    }
+    return true;
+}
+
+// SphGroupDev::zzmax: the largest argument (1 - x)/2 in [0, 1] at which seeds_converge holds, by bisection; +inf for a group of
+// integer degrees, which has no series.  What lies past it is NaN on the device (seed_arg).
+static double seed_limit(const double* q, int nser, int nterms)
+{
+    if (nterms == 0) return INFINITY;
+    if (seeds_converge(q, nser, nterms, 1.0)) return 1.0;
+    double lo = 0.0, hi = 1.0;
+    for (int it = 0; it < 60; ++it) {
+        const double mid = 0.5 * (lo + hi);
+        (seeds_converge(q, nser, nterms, mid) ? lo : hi) = mid;
+    }
+    return lo;
+}
+
 extern "C" int vi_model_create(vi_ctx* c, const vi_model_desc* d, vi_model** out)
 {
     VI_REQUIRE(c && d && out, "null argument");
@@ -366,6 +395,7 @@ extern "C" int vi_model_create(vi_ctx* c, const vi_model_desc* d, vi_model** out
             hg[g].nvmax = G.nvmax;
             if (g == 0) m->nvmax0 = G.nvmax;
             hg[g].nterms = G.nterms;
+            hg[g].zzmax = seed_limit(G.seed_q, 2 * d->maxl, G.nterms);
             const size_t nj = (size_t)G.nvmax + 2;
             if ((rc = upload(m, G.pick, nj, &hg[g].pick)) != VI_OK) break;
             if ((rc = upload(m, G.c, nj * d->maxl, &hg[g].c)) != VI_OK) break;

@@ -116,7 +116,7 @@ __device__ __forceinline__ void fast_chains(FastEval<L, K, TT>& E, const SphGrou
         sm[m] = sm[m - 1] * g.cphi + cm[m - 1] * g.sphi;
     }
     const CT x = (CT)g.x;
-    const double zz = 0.5 * (1.0 - g.x);
+    const double zz = seed_arg(G, g.x);
     const bool intseed = (G.nterms == 0);
     CT cur[L], prev[L];
 #pragma unroll

@@ -237,6 +237,7 @@ struct SphGroupDev {
     const double* c;        // [(nvmax+1) x maxl]
     const double* pref;     // [2 x maxl]
     const double* q;        // [2 x maxl x nterms]
+    double zzmax;           // the largest (1 - x)/2 with every seed series converged at the end of its table; +inf if nterms == 0
 };
 
 struct SphDev {

@@ -86,7 +86,7 @@ __global__ __launch_bounds__(BLOCK) void k_eval_sph_fast(SphDev M, int64_t Q, co
         sm[m] = sm[m - 1] * g.cphi + cm[m - 1] * g.sphi;
     }
     const CT x = (CT)g.x;
-    const double zz = 0.5 * (1.0 - g.x);
+    const double zz = seed_arg(G, g.x);
     const bool intseed = (G.nterms == 0);
     CT cur[L], prev[L];
 #pragma unroll

@@ -191,7 +191,7 @@ __global__ __launch_bounds__(MBLOCK, (NT >= 2 ? 2 : 1)) void k_eval_sph_mfma(Sph
 #pragma unroll
             for (int tile = 0; tile < NT; ++tile) E.D[i][tile] = v4f64{0.0, 0.0, 0.0, 0.0};
         const double x = gm.x;
-        const double zz = 0.5 * (1.0 - x);
+        const double zz = seed_arg(G, x);
         double cur[L], prev[L];
 #pragma unroll
         for (int m = 0; m < L; ++m) { cur[m] = 0.0; prev[m] = 0.0; }

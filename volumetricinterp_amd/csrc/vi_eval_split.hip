@@ -122,7 +122,7 @@ __device__ __forceinline__ void run_group(const SphGroupDev& G, const Geom& g, c
 #pragma unroll
     for (int i = 1; i < M0; ++i) { pmm *= -(2.0 * i - 1.0) * g.s; spow *= g.s; }
     const CT x = (CT)g.x;
-    const double zz = 0.5 * (1.0 - g.x);
+    const double zz = seed_arg(G, g.x);
     const bool intseed = (G.nterms == 0);
     CT cur[MW], prev[MW];
 #pragma unroll

@@ -142,6 +142,16 @@ __device__ __forceinline__ double hyp_series(const double* __restrict__ q, int n
     return sum;
 }
 
+// The argument (1 - x)/2 of the seed series of degree group G, or NaN past G.zzmax - the largest argument at which every series
+// of the group has met the exit test of hyp_series when its table ends (seed_limit, vi_api.hip).  Farther from the pole of the cap
+// the seeds, and everything formed from them, are NaN and not the partial sums.  The test stands here, ahead of the chains and
+// outside hyp_series, because one more live value inside the series costs k_eval_sph_fast<6, 4, 4> (168 VGPRs) its third wave.
+__device__ __forceinline__ double seed_arg(const SphGroupDev& G, double x)
+{
+    const double zz = 0.5 * (1.0 - x);
+    return zz <= G.zzmax ? zz : __builtin_nan("");
+}
+
 // scipy.special.eval_laguerre(k, z), k = 0..maxk-1, by the three-term recurrence (sphharmlag.py:141)
 template <int KCAP>
 __device__ __forceinline__ void laguerre(int maxk, double z, double* Lk)
@@ -158,7 +168,11 @@ __device__ __forceinline__ void laguerre(int maxk, double z, double* Lk)
 
 // The shared per-point engine.  Sink::consume(l, cur[], cm[], sm[]) is called once per degree l with
 // cur[m] = (normalised) P_{nu_l}^m(cos theta), m = 0..l.
-template <int LCAP, int KCAP, class Sink>
+// ON_POWER: where the domain test of a degree group stands (seed_arg).  false: on the argument of the seed series; true: on
+// s^m, the factor of every series seed, with the argument left alone - the same NaNs.  The register allocation decides: at
+// (12, 8) the basis kernel loses its second wave with the test on s^m, at (6, 4) the per-lane track and ray kernels lose one with
+// the test on the argument (profiles/r25_kernel_resources.txt), so eval_point takes the one and the basis sinks the other.
+template <int LCAP, int KCAP, class Sink, bool ON_POWER = false>
 __device__ __forceinline__ void sph_point(const SphDev& M, const Geom& g, Sink& sink)
 {
     const int maxl = M.maxl;
@@ -172,16 +186,17 @@ __device__ __forceinline__ void sph_point(const SphDev& M, const Geom& g, Sink& 
         sm[m] = sm[m - 1] * g.cphi + cm[m - 1] * g.sphi;
     }
     const double x = g.x;
-    const double zz = 0.5 * (1.0 - x);
     const int ng = M.ngroups;
     for (int gi = 0; gi < ng; ++gi) {
         const SphGroupDev G = M.groups[gi];
         const bool intseed = (G.nterms == 0);
+        const double zz = ON_POWER ? 0.5 * (1.0 - x) : seed_arg(G, x);
         double cur[LCAP], prev[LCAP];
 #pragma unroll
         for (int m = 0; m < LCAP; ++m) { cur[m] = 0.0; prev[m] = 0.0; }
         double pmm = 1.0;       // (-1)^m (2m-1)!! s^m
         double spow = 1.0;      // s^m
+        if (ON_POWER && !(zz <= G.zzmax)) spow = __builtin_nan("");
         const int nvmax = G.nvmax;
         for (int j = 0; j <= nvmax; ++j) {
             const double* __restrict__ cj = G.c + (size_t)j * maxl;
@@ -260,7 +275,7 @@ __device__ __forceinline__ void eval_point(const SphDev& M, const Geom& g, const
     laguerre<KCAP>(M.maxk, g.z, sink.Lk);
 #pragma unroll
     for (int t = 0; t < TT; ++t) sink.acc[t] = 0.0;
-    sph_point<LCAP, KCAP>(M, g, sink);
+    sph_point<LCAP, KCAP, EvalSink<KCAP, TT>, true>(M, g, sink);
     const double E = exp(-0.5 * g.z);
 #pragma unroll
     for (int t = 0; t < TT; ++t) val[t] = E * sink.acc[t];
@@ -353,10 +368,10 @@ __device__ __forceinline__ void grad_hess_point(const SphDev& M, const Geom& g, 
         cm[m] = cm[m - 1] * g.cphi - sm[m - 1] * g.sphi;
         sm[m] = sm[m - 1] * g.cphi + cm[m - 1] * g.sphi;
     }
-    const double zz = 0.5 * (1.0 - x);
     for (int gi = 0; gi < M.ngroups; ++gi) {
         const SphGroupDev G = M.groups[gi];
         const bool intseed = (G.nterms == 0);
+        const double zz = seed_arg(G, x);
         double cur[LCAP], prev[LCAP];
 #pragma unroll
         for (int m = 0; m < LCAP; ++m) { cur[m] = 0.0; prev[m] = 0.0; }

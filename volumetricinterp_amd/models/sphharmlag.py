@@ -32,7 +32,13 @@ from ._base import DeviceModel
 RE = 6371.2 * 1000.           # Earth radius (m), sphharmlag.py:9
 
 SNAP_TOL = 1e-12              # degrees whose fractional parts differ by less share one recurrence
-HYP_TERMS = 256               # 2F1 series table length (converges for colatitudes < ~135 deg)
+# 2F1 series table length.  A seed series that has not met its exit test (last term <= 1e-17 of the sum) when the table ends has
+# no value: the device returns NaN there (seed_arg, csrc/vi_sph_device.h), not the partial sum.  Measured against 50 digits
+# (tests/test_basis_domain_host.py, 0.25 deg steps): with 512 terms the basis holds 1e-11 of its column maxima up to a colatitude
+# theta' from the pole of the cap of 147 deg at MAXL 4, 145 deg at MAXL 5 and 6, 140.75 deg at MAXL 12, and is NaN past that.
+# With the 256 terms this table had before, MAXL 12 was 4e-10 off at 134 deg and 2e-5 at 140 deg; MAXL 6 reached 1e-11 at
+# 139 deg.  Integer degrees (CAP_LIM = 10, 18, 30, ...) have closed-form seeds and no limit.
+HYP_TERMS = 512
 
 
 class Model(DeviceModel):
