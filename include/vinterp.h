@@ -386,6 +386,41 @@ int  vi_eval_hess_f64(vi_model* model, int64_t Q, const double* d_lat, const dou
                       const double* d_C, const double* d_hull_eq, int32_t F, double hull_tol, int32_t frame, double* d_out);
 int  vi_eval_hess_basis_f64(vi_model* model, int64_t Q, const double* d_lat, const double* d_lon, const double* d_alt,
                             const double* d_hull_eq, int32_t F, double hull_tol, int32_t frame, double* d_H);
+/* SUB-GRID PEAKS of the fitted parameter along the geodetic normal (the reference has none): for T coefficient rows and Q
+ * columns per row the height at which the parameter has its maximum (kind = +1) or minimum (kind = -1) between two bounds, by
+ * a safeguarded Newton search on the analytic model itself.  Value f, slope d1 = df/dh = u . grad f and curvature
+ * d2 = d2f/dh2 = u^T H u - u the `up` row of the point's east-north-up matrix, so d2 is entry (2, 2) of vi_eval_hess_f64 with
+ * VI_FRAME_ENU - come from ONE walk of the chains per iteration.  Point p = t*Q + q (column q of row t) reads d_lat[p],
+ * d_lon[p] (degrees), the start d_h0[p] and the bracket d_lo[p] <= d_h0[p] <= d_hi[p] (metres) and the raw coefficient row
+ * d_C + t*N, and runs, with s = kind:
+ *     h = h0; a = lo; b = hi; done = false; it = 0
+ *     loop:  f, d1, d2 at (lat, lon, h)
+ *            any of them not finite: status 3, stop
+ *            done or it == max_iter: stop
+ *            it += 1;  if s*d1 > 0: a = h, else b = h
+ *            hn = h - d1/d2 if s*d2 < 0, else NaN;  if not (a < hn < b): hn = (a + b)/2
+ *            done = |hn - h| <= tol;  h = hn
+ * so that the reported f, d1, d2 belong to the returned h (a converged search makes it + 1 walks).
+ *   d_out     (4, T*Q) planar: d_out[k*T*Q + p] = h, f, d1, d2 for k = 0..3
+ *   d_status  0  done, s*d2 < 0 and h farther than tol from both d_lo[p] and d_hi[p]: an interior peak
+ *             1  done otherwise: the search ran into an end of the bracket or the curvature has the wrong sign
+ *             2  not done within max_iter; h is the last iterate (max_iter = 0: the start itself and its values)
+ *             3  the four outputs are NaN: the start is outside the hull, an input is not finite or not lo <= h0 <= hi, or the
+ *                coefficient row or the chains gave a non-finite f, d1 or d2
+ *   d_iter    the iterations made, or NULL
+ * The hull pass of vi_eval_grad_cov_f64 runs once on the T*Q start points (F = 0: no test); later iterates are not tested.
+ * Kernel k_peak_sph (csrc/vi_peak.hip): a lane per column, the grid (blocks of 256 columns, rows), coefficient reads
+ * wave-uniform; a lane that has stopped is frozen, a wave leaves when none of its lanes is searching, a wave without a lane to
+ * search leaves before any walk.  The bits of a point depend on its column, its row, kind, max_iter and tol - not on Q, T, the
+ * other points or its place among them.  A NaN in a row reaches only that row.
+ * Models and orders as vi_grad_basis_f64 - sphharmlag within (6, 4), (12, 8) or (2, 12) -, others return VI_ERR_UNSUPPORTED and
+ * launch nothing; kind other than +-1, max_iter < 0, tol not finite or <= 0, a null pointer (d_iter excepted), a negative size
+ * or F > 0 without facets return VI_ERR_INVALID.  T = 0 or Q = 0 is a no-op.  Asynchronous on the context's stream; timed for
+ * vi_eval_kernel_ms like its siblings (tests/test_gpu_peak.py). */
+int  vi_eval_peak_f64(vi_model* model, int64_t T, int64_t Q, const double* d_lat, const double* d_lon, const double* d_h0,
+                      const double* d_lo, const double* d_hi, const double* d_C, const double* d_hull_eq, int32_t F,
+                      double hull_tol, int32_t kind, int32_t max_iter, double tol, double* d_out, int32_t* d_status,
+                      int32_t* d_iter);
 /* Column maps of many timesteps on the same resident grid, without the volume.  The grid is seen as (outer, L, inner), point
  * q = (o*L + l)*inner + i, column m = o*inner + i: any axis of a C-ordered grid, the last one with inner = 1.  What a user of
  * Estimate.__call__ (estimate.py:110-123) takes from a (lat, lon, alt) volume per column: the peak of the parameter along
@@ -421,7 +456,7 @@ int    vi_reduce_basis_f64(vi_model* model, int64_t outer, int64_t L, int64_t in
  * others return VI_ERR_UNSUPPORTED from vi_eval_f64 while the flag is set. */
 int  vi_model_set_eval_precision(vi_model* model, int32_t chain_f32);
 /* device time (ms) of the evaluation kernel launches of the last vi_eval_f64 / vi_eval_track_f64 / vi_eval_track_grad_f64 / vi_eval_slant_f64 / vi_eval_slant_basis_f64 / vi_eval_resident_f64 /
- * vi_eval_resident_err_f64 / vi_eval_resident_err_at_f64 / vi_eval_resident_gradcov_f64 / vi_eval_grad_cov_f64 (its last chunk) / vi_eval_hess_f64 / vi_eval_hess_basis_f64 / vi_eval_records_gradcov_f64 / vi_eval_track_grad_cov_f64 /vi_eval_resident_peak_f64 call on this context, from HIP events recorded on the context's stream around them (the preparation kernels are excluded).
+ * vi_eval_resident_err_f64 / vi_eval_resident_err_at_f64 / vi_eval_resident_gradcov_f64 / vi_eval_grad_cov_f64 (its last chunk) / vi_eval_hess_f64 / vi_eval_hess_basis_f64 / vi_eval_peak_f64 / vi_eval_records_gradcov_f64 / vi_eval_track_grad_cov_f64 /vi_eval_resident_peak_f64 call on this context, from HIP events recorded on the context's stream around them (the preparation kernels are excluded).
  * The events are recorded only while vi_ctx_set_eval_timing(ctx, 1) is in force (default: off - the pair costs a 0.2 ms call about 7 us);
  * vi_eval_kernel_ms fails with VI_ERR_ARG while it is off or before a call has been timed. */
 int  vi_ctx_set_eval_timing(vi_ctx* ctx, int32_t on);

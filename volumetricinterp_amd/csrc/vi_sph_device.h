@@ -2,7 +2,8 @@
 // vi_eval_mfma.hip): geodetic -> model coordinates (sphharmlag.py:324-359), the 2F1 seed series and the Laguerre recurrence; the
 // per-point engine of the basis (sph_point) with the evaluation's sink; the point's east-north-up matrix and the chains of the
 // gradient basis (enu_frame, grad_point: k_grad_sph of vi_basis.hip and K2tg of vi_track.hip) and, on the same walk, of the
-// Hessian basis (hess_point: k_hess_sph of vi_hess.hip).
+// Hessian basis (hess_point: k_hess_sph of vi_hess.hip) or of value, gradient and Hessian together (peak_point: k_peak_sph of
+// vi_peak.hip).
 #pragma once
 #include "vi_common.h"
 
@@ -323,9 +324,14 @@ __device__ __forceinline__ void enu_frame(const SphDev& M, const Geom& g, double
 //               H_pp = g0 (T A''/y^2 + x T' A/y) / r^2 + g1 T A / r  H_tp = g0 A' (T'/y - x T/y^2) / r^2
 //             sink.term(n, h) once per basis function with h[6] in the packed order rr, tt, pp, rt, rp, tp - (0,0) (1,1) (2,2)
 //             (0,1) (0,2) (1,2), the gradient covariance's.  Non-finite at the pole of the cap (y = 0), as the gradient is.
-template <int LCAP, int KCAP, bool HESS, class Sink>
+//   all:      the Hessian's walk, and sink.term(n, f, d, h) once per basis function with its value f = g0 T A, its gradient
+//             d[3] = (g1 T A, g0 T' A / r, g0 T A' / (r y)) in the same orthonormal frame, in 1/m - the three components of the
+//             gradient mode - and h[6] as above, all from the factors the Hessian's entries are made of.
+enum { WALK_GRAD = 0, WALK_HESS = 1, WALK_ALL = 2 };
+template <int LCAP, int KCAP, int MODE, class Sink>
 __device__ __forceinline__ void grad_hess_point(const SphDev& M, const Geom& g, Sink& sink)
 {
+    constexpr bool HESS = MODE != WALK_GRAD;
     const int maxl = M.maxl, maxk = M.maxk, L2 = maxl * maxl;
     double L0[KCAP], L1[KCAP];          // L_k(z) and L^(1)_{k-1}(z)
     laguerre<KCAP>(maxk, g.z, L0);
@@ -346,6 +352,7 @@ __device__ __forceinline__ void grad_hess_point(const SphDev& M, const Geom& g, 
     double G0[HK], G1[HK], G2[HK];
     const double inv_r = 1.0 / ((g.z / 100.0 + 1.0) * M.RE), inv_y = 1.0 / y;
     const double inv_r2 = inv_r * inv_r, inv_y2 = inv_y * inv_y;
+    const double rr = (g.z / 100.0 + 1.0) * M.RE;                       // r, for the all mode: g1 T A = (g1 T A / r) r
     if constexpr (HESS) {
         const double a = 100.0 / M.RE;
         double Lb = 0.0, La = 0.0;      // L^(2)_{k-3}, L^(2)_{k-2}:  n L^(2)_n = (2n + 1 - z) L^(2)_{n-1} - (n + 1) L^(2)_{n-2}
@@ -437,7 +444,13 @@ __device__ __forceinline__ void grad_hess_point(const SphDev& M, const Geom& g, 
                                         const double gd = fma(-G0[k], inv_r2, G1[k]);          // g1/r - g0/r^2
                                         const double h[6] = {G2[k] * TA,  fma(G0[k], a_tt, dr), fma(G0[k], a_pp, dr),
                                                              gd * a_rt,   gd * a_rp,            G0[k] * a_tp};
-                                        sink.term(k * L2 + r, h);
+                                        if constexpr (MODE == WALK_ALL) {
+                                            const double gi = G0[k] * inv_r;                   // g0 / r
+                                            const double d[3] = {dr * rr, gi * a_rt, gi * a_rp};
+                                            sink.term(k * L2 + r, G0[k] * TA, d, h);
+                                        } else {
+                                            sink.term(k * L2 + r, h);
+                                        }
                                     }
                                 }
                             }
@@ -453,14 +466,21 @@ __device__ __forceinline__ void grad_hess_point(const SphDev& M, const Geom& g, 
 template <int LCAP, int KCAP, class Sink>
 __device__ __forceinline__ void grad_point(const SphDev& M, const Geom& g, Sink& sink)
 {
-    grad_hess_point<LCAP, KCAP, false>(M, g, sink);
+    grad_hess_point<LCAP, KCAP, WALK_GRAD>(M, g, sink);
 }
 
 // the Hessian basis at one point (k_hess_sph, vi_hess.hip)
 template <int LCAP, int KCAP, class Sink>
 __device__ __forceinline__ void hess_point(const SphDev& M, const Geom& g, Sink& sink)
 {
-    grad_hess_point<LCAP, KCAP, true>(M, g, sink);
+    grad_hess_point<LCAP, KCAP, WALK_HESS>(M, g, sink);
+}
+
+// value, gradient and Hessian of every basis function at one point on one walk (k_peak_sph, vi_peak.hip)
+template <int LCAP, int KCAP, class Sink>
+__device__ __forceinline__ void peak_point(const SphDev& M, const Geom& g, Sink& sink)
+{
+    grad_hess_point<LCAP, KCAP, WALK_ALL>(M, g, sink);
 }
 
 }  // namespace

@@ -9,6 +9,7 @@ instead of materialising ``A`` (1 152 B per point at N = 144) and calling
 (estimate.py:153-178) becomes one host Qhull plus a half-space test fused in
 the kernel.
 """
+import collections
 import configparser
 import datetime as dt
 import importlib
@@ -316,6 +317,36 @@ def column_points(shape, axis, index):
     return np.where(index < 0, -1, (o * L + index) * inner + i)
 
 
+PEAK_HEIGHT_KINDS = {'max': 1, 'min': -1}         # vi_eval_peak_f64's kind
+PEAK_HEIGHT_FIELDS = ('height', 'value', 'slope', 'curvature', 'status', 'iterations')
+PeakHeight = collections.namedtuple('PeakHeight', PEAK_HEIGHT_FIELDS)
+PeakHeightError = collections.namedtuple('PeakHeightError', PEAK_HEIGHT_FIELDS + ('height_error', 'value_error'))
+
+
+def peak_brackets(alt_axis, index):
+    """(start, lo, hi) for Estimate.peak_height from the altitude axis of a grid and the index map of ResidentGrid.peak: the
+    grid altitude at `index` and the altitudes of its two neighbours on the axis - the lower and the higher of them, the sample
+    itself where it is the first or the last of the axis -, NaN where index is -1 (a column without a peak; peak_height gives
+    such a column status 3).  alt_axis: 1-D, finite, at least one sample; index: integers in [-1, len(alt_axis)) of any shape.
+    Three float64 arrays of the shape of index.  On the host."""
+    alt = np.asarray(alt_axis, dtype=np.float64)
+    if alt.ndim != 1 or alt.size == 0 or not np.isfinite(alt).all():
+        raise ValueError('alt_axis must be a 1-D array of finite altitudes with at least one sample')
+    index = np.asarray(index)
+    if index.dtype.kind not in 'iu':
+        raise ValueError('index must be an integer array, not %s' % index.dtype)
+    index = index.astype(np.int64)
+    L = alt.size
+    if index.size and (index.min() < -1 or index.max() >= L):
+        raise ValueError('index must lie in [-1, %d)' % L)
+    none = index < 0
+    i = np.where(none, 0, index)
+    below, above = alt[np.maximum(i - 1, 0)], alt[np.minimum(i + 1, L - 1)]
+    start, lo, hi = alt[i], np.minimum(below, above), np.maximum(below, above)
+    lo, hi = np.minimum(lo, start), np.maximum(hi, start)
+    return tuple(np.where(none, np.nan, a) for a in (start, lo, hi))
+
+
 class Estimate(object):
     def __init__(self, coeff_filename, timetol=60., timeinterp=False, ctx=None):
         self.timetol = timetol
@@ -504,6 +535,94 @@ class Estimate(object):
                                                  _ptr(None if eq is None else dev.up(eq)), F, tol, GRADIENT_FRAMES[frame],
                                                  dO.ptr), 'vi_eval_hess_f64')
             return dO.download()
+
+    def peak_height(self, times, gdlat, gdlon, start, lo, hi, kind='max', tol=1e-3, max_iter=48, check_hull=True, error=False):
+        """Sub-grid layer peaks: per column (gdlat, gdlon) and time the height in [lo, hi] at which the fitted parameter has its
+        maximum (kind='min': minimum) along the geodetic normal, and the parameter there - hmF2 and NmF2 of a fitted volume.
+        A safeguarded Newton search from `start` on the analytic model itself, not on grid samples: value, slope df/dh and
+        curvature d2f/dh2 (hessian(frame='enu')[..., 2, 2]) are closed-form and come from one walk of the basis per iteration;
+        a step that leaves the bracket, or a curvature of the wrong sign, is replaced by a bisection of the bracket.  All
+        columns and times in ONE library call (vi_eval_peak_f64, kernel k_peak_sph, include/vinterp.h has the iteration).
+
+        times: one naive-UTC datetime or a sequence of T of them; the coefficients of get_C per time, as hessian takes them.
+        gdlat, gdlon: the columns, of one shape S, degrees.  start, lo, hi: metres, broadcast to (T,) + S (to S for one time),
+        lo <= start <= hi; peak_brackets makes them from the index map of ResidentGrid.peak.  tol: the search stops when a step
+        is at most tol metres.  max_iter=48: bisecting 600 km down to 1e-3 m takes 30 steps, Newton on top a handful, the rest
+        is slack.
+
+        Returns the named tuple (height, value, slope, curvature, status, iterations), each of shape (T,) + S (S for one time):
+        status 0  an interior peak: converged, the curvature has the sign of the kind, farther than tol from lo and hi
+               1  converged, but onto an end of the bracket or with a curvature of the wrong sign: no interior peak
+               2  not converged within max_iter; max_iter=0 evaluates the start
+               3  nothing to report: the start is outside the hull (check_hull) or NaN - what peak_brackets makes of a column
+                  without a grid peak -, not lo <= start <= hi, or the record or the basis is not finite there
+               4  the search ended outside the hull (tested on the host, self.check_hull); all four values are NaN
+        height and value are NaN wherever status is not 0; slope and curvature are those of the last iterate (NaN with status
+        3 and 4), iterations the steps made.
+
+        error=True: the named tuple grows by (height_error, value_error), first-order error propagation at the refined peaks,
+        NaN where status is not 0: height_error = sqrt(cov_up,up) / |curvature| with the gradient covariance of
+        gradient_covariance(frame='enu') - the peak is where the slope is zero, so its height moves by -(error of the slope) /
+        curvature - and value_error = error() at the peak.  These are the existing entries called once per time at the refined
+        points, not fused into the search.  Raises ValueError when the Estimate holds no covariance.
+        sphharmlag only, at the orders of gradient."""
+        if kind not in PEAK_HEIGHT_KINDS:
+            raise ValueError("kind must be 'max' or 'min', not %r" % (kind,))
+        tol = float(tol)
+        if not (np.isfinite(tol) and tol > 0.):
+            raise ValueError('tol must be finite and positive, not %r' % (tol,))
+        if not isinstance(max_iter, (int, np.integer)) or isinstance(max_iter, bool) or max_iter < 0:
+            raise ValueError('max_iter must be a non-negative integer, not %r' % (max_iter,))
+        if error:
+            self._need_covariance()
+        single = isinstance(times, dt.datetime)
+        times = [times] if single else list(times)
+        lat, lon = np.asarray(gdlat, dtype=np.float64), np.asarray(gdlon, dtype=np.float64)
+        if lat.shape != lon.shape:
+            raise ValueError('gdlat and gdlon must have one shape, not %r and %r' % (lat.shape, lon.shape))
+        T, Q, N = len(times), lat.size, self.model.nbasis
+        full = (T,) + lat.shape
+        try:
+            h0, a, b = (np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), full)).reshape(T, Q)
+                        for v in (start, lo, hi))
+        except ValueError:
+            raise ValueError('start, lo and hi must broadcast to the shape %r' % (full,))
+        C = np.empty((T, N))
+        for t, time in enumerate(times):
+            C[t] = self.get_C(time)[0]
+        shape = lat.shape if single else full
+        res, status, iters = np.full((4, T, Q), np.nan), np.full((T, Q), 3, dtype=np.int32), np.zeros((T, Q), dtype=np.int32)
+        if T and Q:
+            latq, lonq = np.tile(lat.ravel(), T), np.tile(lon.ravel(), T)
+            eq, F, htol = self._hull_args(check_hull)
+            with self.model.ctx.scope() as dev:
+                dlat, dlon, dh0, da, db, dC_ = (dev.up(v) for v in (latq, lonq, h0, a, b, C))
+                dO, dS, dI = dev.empty((4, T, Q)), dev.empty((T, Q), np.int32), dev.empty((T, Q), np.int32)
+                _lib.check(_lib.lib.vi_eval_peak_f64(self.model.handle(), T, Q, dlat.ptr, dlon.ptr, dh0.ptr, da.ptr, db.ptr,
+                                                     dC_.ptr, _ptr(None if eq is None else dev.up(eq)), F, htol,
+                                                     PEAK_HEIGHT_KINDS[kind], int(max_iter), tol, dO.ptr, dS.ptr, dI.ptr),
+                           'vi_eval_peak_f64')
+                res, status, iters = dO.download(), dS.download(), dI.download()
+            if check_hull:
+                ran = status != 3
+                left = np.zeros((T, Q), dtype=bool)
+                left[ran] = ~self.check_hull(latq.reshape(T, Q)[ran], lonq.reshape(T, Q)[ran], res[0][ran])
+                status[left] = 4
+                res[:, left] = np.nan
+        res[:2, status != 0] = np.nan
+        out = tuple(r.reshape(shape) for r in res) + (status.reshape(shape), iters.reshape(shape))
+        if not error:
+            return PeakHeight(*out)
+        herr, verr = np.full((T, Q), np.nan), np.full((T, Q), np.nan)
+        for t, time in enumerate(times):
+            ok = status[t] == 0
+            if ok.any():
+                pts = lat.ravel()[ok], lon.ravel()[ok], res[0, t][ok]
+                cov = self._gradient_covariance(time, *pts, check_hull, 'enu')
+                with np.errstate(invalid='ignore', divide='ignore'):
+                    herr[t, ok] = np.sqrt(cov[2]) / np.abs(res[3, t][ok])
+                verr[t, ok] = self.error(time, *pts, check_hull)
+        return PeakHeightError(*(out + (herr.reshape(shape), verr.reshape(shape))))
 
     def _need_covariance(self):
         if self.Covariance is None:
