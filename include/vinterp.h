@@ -421,6 +421,52 @@ int  vi_eval_peak_f64(vi_model* model, int64_t T, int64_t Q, const double* d_lat
                       const double* d_lo, const double* d_hi, const double* d_C, const double* d_hull_eq, int32_t F,
                       double hull_tol, int32_t kind, int32_t max_iter, double tol, double* d_out, int32_t* d_status,
                       int32_t* d_iter);
+/* LEVEL CROSSINGS of the fitted parameter along the geodetic normal (the reference has none): for T coefficient rows and Q
+ * columns per row the height between two bounds at which the parameter crosses a given level - the reflection height of a
+ * sounding frequency, the half-peak heights of a layer, an isodensity surface -, by a safeguarded Newton search on the analytic
+ * model itself.  A root search needs no curvature: value f and slope d1 = df/dh = u . grad f - u the `up` row of the point's
+ * east-north-up matrix - come from ONE gradient walk of the chains per iteration, four sums against the ten of
+ * vi_eval_peak_f64.  Point p = t*Q + q (column q of row t) reads d_lat[p], d_lon[p] (degrees), the bracket lo = d_ends[p],
+ * hi = d_ends[T*Q + p] (metres), the level L = d_level[p] and the raw coefficient row d_C + t*N, and runs
+ *     a = lo; b = hi
+ *     not finite(lat, lon, a, b, L), not a < b, or an end outside the hull: status 3, stop
+ *     fa = f(a) - L, da = d1(a);  fb = f(b) - L, db = d1(b)              (two walks)
+ *     fa or fb not finite: status 3, stop
+ *     fa == 0: h = a, report f(a), da, status 0, it = 0, stop.   fb == 0: the same at b.
+ *     fa and fb of one sign (tested by comparisons, not by their product): status 1, stop
+ *     h = a - fa (b - a)/(fb - fa);  if not (a < h < b): h = (a + b)/2;   done = false; it = 0
+ *     loop:  f, d1 at (lat, lon, h);  phi = f - L
+ *            phi or d1 not finite: status 3, stop
+ *            phi == 0 or done or it == max_iter: stop - status 0 if phi == 0 or done, else 2
+ *            it += 1;  if (phi > 0) == (fa > 0): a = h, else b = h
+ *            hn = h - phi/d1 if d1 != 0, else NaN;  if not (a < hn < b): hn = (a + b)/2
+ *            done = |hn - h| <= tol;  h = hn
+ * so that the reported f and d1 belong to the returned h (a converged search makes it + 3 walks), and every pass of the loop
+ * either stops or adds one to `it`, which max_iter bounds.
+ *   d_lat, d_lon  (2, T*Q) planar, the second plane a copy of the first: point T*Q + p is the column of point p again
+ *   d_ends    (2, T*Q) planar: plane 0 the lower ends, plane 1 the upper ends
+ *   d_out     (3, T*Q) planar: d_out[k*T*Q + p] = h, f, d1 for k = 0..2; all NaN with status 1 and 3, the last iterate with 2
+ *   d_status  0  a crossing: phi == 0 exactly, or the last step was at most tol
+ *             1  f - L has one sign at both ends: no crossing is bracketed
+ *             2  not done within max_iter; h is the last iterate (max_iter = 0: the secant point of the two ends)
+ *             3  the outputs are NaN: an end of the bracket is outside the hull, an input is not finite, not lo < hi, or the
+ *                coefficient row or the chains gave a non-finite f or d1
+ *   d_iter    the iterations made (0 with status 1, and with status 3 before the loop), or NULL
+ * The hull pass of vi_eval_grad_cov_f64 runs ONCE on the 2*T*Q points (d_lat, d_lon, d_ends) - both ends of every bracket
+ * (F = 0: no test).  Later iterates need no test and there is no "left the hull" status: a column's geodetic normal is a
+ * straight line in ECEF and the hull test is an intersection of half-spaces, a convex set, so every point between two points
+ * inside is inside.
+ * Kernel k_level_sph (csrc/vi_level.hip): a lane per column, the grid (blocks of 256 columns, rows), coefficient reads
+ * wave-uniform; a lane that has stopped stores at once and is frozen, a wave leaves when none of its lanes is searching, a wave
+ * without a lane to search leaves before any walk.  The bits of a point depend on its column, its row, level, bracket, max_iter
+ * and tol - not on Q, T, the other points or its place among them.  A NaN in a row reaches only that row.
+ * Models and orders as vi_eval_peak_f64, others return VI_ERR_UNSUPPORTED and launch nothing; max_iter < 0 or > 10000, tol not
+ * finite or <= 0, a null pointer (d_iter excepted), a negative size or F > 0 without facets return VI_ERR_INVALID.  T = 0 or
+ * Q = 0 is a no-op.  Asynchronous on the context's stream; timed for vi_eval_kernel_ms like its siblings
+ * (tests/test_gpu_level.py). */
+int  vi_eval_level_f64(vi_model* model, int64_t T, int64_t Q, const double* d_lat, const double* d_lon, const double* d_ends,
+                       const double* d_level, const double* d_C, const double* d_hull_eq, int32_t F, double hull_tol,
+                       int32_t max_iter, double tol, double* d_out, int32_t* d_status, int32_t* d_iter);
 /* Column maps of many timesteps on the same resident grid, without the volume.  The grid is seen as (outer, L, inner), point
  * q = (o*L + l)*inner + i, column m = o*inner + i: any axis of a C-ordered grid, the last one with inner = 1.  What a user of
  * Estimate.__call__ (estimate.py:110-123) takes from a (lat, lon, alt) volume per column: the peak of the parameter along
@@ -450,13 +496,25 @@ int    vi_eval_resident_peak_f64(vi_model* model, int64_t outer, int64_t L, int6
 size_t vi_eval_resident_peak_work_bytes(vi_model* model, int64_t outer, int64_t L, int64_t inner, int64_t T);
 int    vi_reduce_basis_f64(vi_model* model, int64_t outer, int64_t L, int64_t inner, const double* d_Y, const double* d_w,
                            double* d_Yr);
+/* Crossing maps on the same view (outer, L, inner) of a resident grid: d_idx[t*M + m] = the index l of the first (which = 0) or
+ * last (which = 1) pair of neighbours (l, l + 1) along the axis of column m whose densities f_l, f_{l+1} of
+ * vi_eval_resident_f64 are both numbers and hold the level d_level[t*M + m] between them - direction 1 (up):
+ * f_l <= level <= f_{l+1}; 2 (down): f_l >= level >= f_{l+1}; 0: either -, decided by comparisons, never by a product; -1 where
+ * the column has no such pair: a NaN level, a timestep whose coefficients hold a NaN, a column outside the hull, L = 1.  The
+ * grid bracket vi_eval_level_f64 starts from.  d_work: at least Q doubles; the product of vi_eval_resident_f64 runs into it, a
+ * slab of as many timesteps as work_bytes holds (VI_ERR_INVALID below one), then a column kernel over the slab
+ * (k_cross_columns, csrc/vi_level.hip): the same map whatever the cut of T into slabs or calls.  VINTERP_EVAL_RESIDENT=blas
+ * applies as in vi_eval_resident_f64.  Asynchronous on the context's stream; timed for vi_eval_kernel_ms. */
+int    vi_eval_resident_cross_f64(vi_model* model, int64_t outer, int64_t L, int64_t inner, int64_t T, const double* d_Y,
+                                  const double* d_C, const double* d_level, int32_t which, int32_t direction, int32_t* d_idx,
+                                  void* d_work, size_t work_bytes);
 /* Arithmetic of the Legendre degree recurrences inside vi_eval_f64 for this model: 0 = fp64 (default; the reference
  * computes in float64 throughout, sphharmlag.py:118-145), 1 = fp32 chains with everything else in fp64 - the variant
  * BASELINE configs[4] sweeps against the 1e-6 tolerance.  Orders with an fp32 kernel: (MAXL, MAXK) = (6,4), (2,8), (12,8);
  * others return VI_ERR_UNSUPPORTED from vi_eval_f64 while the flag is set. */
 int  vi_model_set_eval_precision(vi_model* model, int32_t chain_f32);
 /* device time (ms) of the evaluation kernel launches of the last vi_eval_f64 / vi_eval_track_f64 / vi_eval_track_grad_f64 / vi_eval_slant_f64 / vi_eval_slant_basis_f64 / vi_eval_resident_f64 /
- * vi_eval_resident_err_f64 / vi_eval_resident_err_at_f64 / vi_eval_resident_gradcov_f64 / vi_eval_grad_cov_f64 (its last chunk) / vi_eval_hess_f64 / vi_eval_hess_basis_f64 / vi_eval_peak_f64 / vi_eval_records_gradcov_f64 / vi_eval_track_grad_cov_f64 /vi_eval_resident_peak_f64 call on this context, from HIP events recorded on the context's stream around them (the preparation kernels are excluded).
+ * vi_eval_resident_err_f64 / vi_eval_resident_err_at_f64 / vi_eval_resident_gradcov_f64 / vi_eval_grad_cov_f64 (its last chunk) / vi_eval_hess_f64 / vi_eval_hess_basis_f64 / vi_eval_peak_f64 / vi_eval_level_f64 / vi_eval_records_gradcov_f64 / vi_eval_track_grad_cov_f64 /vi_eval_resident_peak_f64 / vi_eval_resident_cross_f64 call on this context, from HIP events recorded on the context's stream around them (the preparation kernels are excluded).
  * The events are recorded only while vi_ctx_set_eval_timing(ctx, 1) is in force (default: off - the pair costs a 0.2 ms call about 7 us);
  * vi_eval_kernel_ms fails with VI_ERR_ARG while it is off or before a call has been timed. */
 int  vi_ctx_set_eval_timing(vi_ctx* ctx, int32_t on);

@@ -98,6 +98,36 @@ extern "C" int vi_eval_resident_peak_f64(vi_model* m, int64_t outer, int64_t L, 
     return VI_OK;
 }
 
+// Crossing maps along one axis of a resident grid (include/vinterp.h): the slab loop of the peak's two-pass path - the density
+// product of vi_eval_resident_f64 into d_work, as many timesteps as it holds, and k_cross_columns (vi_level.hip) over the slab.
+// An axis of one sample has no pair of neighbours: no product, every column -1.
+extern "C" int vi_eval_resident_cross_f64(vi_model* m, int64_t outer, int64_t L, int64_t inner, int64_t T, const double* d_Y,
+                                          const double* d_C, const double* d_level, int32_t which, int32_t direction,
+                                          int32_t* d_idx, void* d_work, size_t work_bytes)
+{
+    VI_REQUIRE(m && d_Y && d_C && d_level && d_idx, "null argument");
+    VI_REQUIRE(outer >= 0 && L >= 0 && inner >= 0 && T >= 0, "negative size");
+    VI_REQUIRE(which == 0 || which == 1, "which must be 0 (first) or 1 (last)");
+    VI_REQUIRE(direction >= 0 && direction <= 2, "direction must be 0 (any), 1 (up) or 2 (down)");
+    VI_REQUIRE(L <= 0x7fffffffLL, "the axis is longer than a 32-bit index");
+    const int64_t M = outer * inner, Q = M * L;
+    if (Q == 0 || T == 0) return VI_OK;
+    VI_REQUIRE(d_work, "null work space");
+    vi_ctx* c = m->ctx;
+    VI_HIP(hipSetDevice(c->device));
+    EvalTimer timer(c);
+    const int64_t slab = (int64_t)(work_bytes / ((size_t)Q * sizeof(double)));
+    VI_REQUIRE(slab >= 1, "work space smaller than the density map of one timestep");
+    for (int64_t t0 = 0; t0 < T; t0 += slab) {
+        const int64_t tc = (T - t0) < slab ? (T - t0) : slab;
+        int rc = L > 1 ? eval_resident(m, Q, tc, d_Y, d_C + t0 * m->N, (double*)d_work) : (int)VI_OK;
+        if (rc != VI_OK) return rc;
+        rc = vi_cross_columns(c, outer, L, inner, tc, which, direction, (const double*)d_work, d_level + t0 * M, d_idx + t0 * M);
+        if (rc != VI_OK) return rc;
+    }
+    return VI_OK;
+}
+
 // The reduced basis of a resident grid along one axis (include/vinterp.h): k_reduce_basis (vi_eval_resident.hip)
 extern "C" int vi_reduce_basis_f64(vi_model* m, int64_t outer, int64_t L, int64_t inner, const double* d_Y, const double* d_w,
                                    double* d_Yr)

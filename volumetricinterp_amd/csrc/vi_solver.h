@@ -58,6 +58,9 @@ int vi_eval_resident_peak_mfma(vi_ctx* c, int N, int64_t outer, int64_t L, int64
 int vi_peak_columns(vi_ctx* c, int64_t outer, int64_t L, int64_t inner, int64_t T, int kind, const double* d_in, double* d_val,
                     int32_t* d_idx);
 int vi_reduce_basis(vi_ctx* c, int N, int64_t outer, int64_t L, int64_t inner, const double* d_Y, const double* d_w, double* d_Yr);
+// crossing maps of a slab of densities (T, outer, L, inner) (vi_level.hip)
+int vi_cross_columns(vi_ctx* c, int64_t outer, int64_t L, int64_t inner, int64_t T, int which, int direction, const double* d_in,
+                     const double* d_level, int32_t* d_idx);
 
 // ---- what vi_basis.hip and the evaluation units vi_eval.hip (K2), vi_track.hip (K2t, K2tg) and vi_slant.hip (K2l, K1l) share
 //      on the host; internal to the library, not among its dynamic symbols ----

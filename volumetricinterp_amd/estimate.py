@@ -347,6 +347,35 @@ def peak_brackets(alt_axis, index):
     return tuple(np.where(none, np.nan, a) for a in (start, lo, hi))
 
 
+LEVEL_HEIGHT_FIELDS = ('height', 'value', 'slope', 'status', 'iterations')
+LevelHeight = collections.namedtuple('LevelHeight', LEVEL_HEIGHT_FIELDS)
+LevelHeightError = collections.namedtuple('LevelHeightError', LEVEL_HEIGHT_FIELDS + ('height_error',))
+CROSSING_WHICH = {'first': 0, 'last': 1}          # vi_eval_resident_cross_f64's which and direction
+CROSSING_DIRECTIONS = {'any': 0, 'up': 1, 'down': 2}
+
+
+def level_brackets(alt_axis, index):
+    """(lo, hi) for Estimate.level_height from the altitude axis of a grid and the index map of ResidentGrid.crossing: the grid
+    altitudes at `index` and at `index` + 1 - the pair of neighbours that holds the level between them -, the lower of the two
+    as lo, so that lo < hi on a descending axis too; NaN where index is -1 (a column without a crossing; level_height gives
+    such a column status 3).  alt_axis: 1-D, finite, at least one sample; index: integers in [-1, len(alt_axis) - 1) of any
+    shape.  Two float64 arrays of the shape of index.  On the host."""
+    alt = np.asarray(alt_axis, dtype=np.float64)
+    if alt.ndim != 1 or alt.size == 0 or not np.isfinite(alt).all():
+        raise ValueError('alt_axis must be a 1-D array of finite altitudes with at least one sample')
+    index = np.asarray(index)
+    if index.dtype.kind not in 'iu':
+        raise ValueError('index must be an integer array, not %s' % index.dtype)
+    index = index.astype(np.int64)
+    L = alt.size
+    if index.size and (index.min() < -1 or index.max() >= L - 1):
+        raise ValueError('index must lie in [-1, %d)' % (L - 1))
+    none = index < 0
+    i = np.where(none, 0, index)
+    below, above = alt[i], alt[np.minimum(i + 1, L - 1)]
+    return tuple(np.where(none, np.nan, a) for a in (np.minimum(below, above), np.maximum(below, above)))
+
+
 class Estimate(object):
     def __init__(self, coeff_filename, timetol=60., timeinterp=False, ctx=None):
         self.timetol = timetol
@@ -623,6 +652,82 @@ class Estimate(object):
                     herr[t, ok] = np.sqrt(cov[2]) / np.abs(res[3, t][ok])
                 verr[t, ok] = self.error(time, *pts, check_hull)
         return PeakHeightError(*(out + (herr.reshape(shape), verr.reshape(shape))))
+
+    def level_height(self, times, gdlat, gdlon, level, lo, hi, tol=1e-3, max_iter=48, check_hull=True, error=False):
+        """Level crossings: per column (gdlat, gdlon) and time the height in [lo, hi] at which the fitted parameter crosses
+        `level` along the geodetic normal - the reflection height of a sounding frequency (Ne = 1.24e10 f^2 m^-3, f in MHz),
+        the half-peak heights of a layer, an isodensity surface.  A safeguarded Newton search on the analytic model itself, not
+        on grid samples: value and slope df/dh are closed-form and come from one gradient walk of the basis per iteration; a
+        step that leaves the bracket is replaced by a bisection of the bracket, which always holds a change of sign.  All
+        columns and times in ONE library call (vi_eval_level_f64, kernel k_level_sph, include/vinterp.h has the iteration).
+
+        times: one naive-UTC datetime or a sequence of T of them; the coefficients of get_C per time, as peak_height takes
+        them.  gdlat, gdlon: the columns, of one shape S, degrees.  level (the parameter's unit), lo, hi (metres): broadcast to
+        (T,) + S (to S for one time), lo < hi; level_brackets makes lo and hi from the index map of ResidentGrid.crossing.
+        tol: the search stops when a step is at most tol metres.  max_iter: at most 10000.
+
+        Returns the named tuple (height, value, slope, status, iterations), each of shape (T,) + S (S for one time):
+        status 0  a crossing: the value is the level exactly, or the last step was at most tol
+               1  the parameter minus the level has one sign at lo and at hi: no crossing is bracketed
+               2  not converged within max_iter
+               3  nothing to report: lo or hi is outside the hull (check_hull) or NaN - what level_brackets makes of a column
+                  without a grid crossing -, not lo < hi, the level is NaN, or the record or the basis is not finite there
+        height and value are NaN wherever status is not 0; slope is that of the last iterate (NaN with status 1 and 3) and its
+        sign tells a bottomside crossing (> 0) from a topside one; iterations the steps made.  Both ends of every bracket go
+        through the hull test on the device; the heights between them need none - the geodetic normal of a column is a straight
+        line and the hull is convex -, so there is no host pass and no "left the hull" status.
+
+        error=True: the named tuple grows by height_error = error() / |slope| at the crossing, first order - the height moves
+        by -(error of the value) / slope, the level taken as exact -, NaN where status is not 0.  The existing entry called
+        once per time at the crossings, not fused into the search.  Raises ValueError when the Estimate holds no covariance.
+        sphharmlag only, at the orders of gradient."""
+        tol = float(tol)
+        if not (np.isfinite(tol) and tol > 0.):
+            raise ValueError('tol must be finite and positive, not %r' % (tol,))
+        if not isinstance(max_iter, (int, np.integer)) or isinstance(max_iter, bool) or not 0 <= max_iter <= 10000:
+            raise ValueError('max_iter must be an integer in [0, 10000], not %r' % (max_iter,))
+        if error:
+            self._need_covariance()
+        single = isinstance(times, dt.datetime)
+        times = [times] if single else list(times)
+        lat, lon = np.asarray(gdlat, dtype=np.float64), np.asarray(gdlon, dtype=np.float64)
+        if lat.shape != lon.shape:
+            raise ValueError('gdlat and gdlon must have one shape, not %r and %r' % (lat.shape, lon.shape))
+        T, Q, N = len(times), lat.size, self.model.nbasis
+        full = (T,) + lat.shape
+        try:
+            lev, a, b = (np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), full)).reshape(T, Q)
+                         for v in (level, lo, hi))
+        except ValueError:
+            raise ValueError('level, lo and hi must broadcast to the shape %r' % (full,))
+        C = np.empty((T, N))
+        for t, time in enumerate(times):
+            C[t] = self.get_C(time)[0]
+        shape = lat.shape if single else full
+        res, status, iters = np.full((3, T, Q), np.nan), np.full((T, Q), 3, dtype=np.int32), np.zeros((T, Q), dtype=np.int32)
+        if T and Q:
+            # both ends of every bracket in one hull pass: the columns twice, the lower ends, then the upper ends
+            latq, lonq, ends = np.tile(lat.ravel(), 2 * T), np.tile(lon.ravel(), 2 * T), np.stack((a, b))
+            eq, F, htol = self._hull_args(check_hull)
+            with self.model.ctx.scope() as dev:
+                dlat, dlon, dends, dlev, dC_ = (dev.up(v) for v in (latq, lonq, ends, lev, C))
+                dO, dS, dI = dev.empty((3, T, Q)), dev.empty((T, Q), np.int32), dev.empty((T, Q), np.int32)
+                _lib.check(_lib.lib.vi_eval_level_f64(self.model.handle(), T, Q, dlat.ptr, dlon.ptr, dends.ptr, dlev.ptr, dC_.ptr,
+                                                      _ptr(None if eq is None else dev.up(eq)), F, htol, int(max_iter), tol,
+                                                      dO.ptr, dS.ptr, dI.ptr), 'vi_eval_level_f64')
+                res, status, iters = dO.download(), dS.download(), dI.download()
+        res[:2, status != 0] = np.nan
+        out = tuple(r.reshape(shape) for r in res) + (status.reshape(shape), iters.reshape(shape))
+        if not error:
+            return LevelHeight(*out)
+        herr = np.full((T, Q), np.nan)
+        for t, time in enumerate(times):
+            ok = status[t] == 0
+            if ok.any():
+                pts = lat.ravel()[ok], lon.ravel()[ok], res[0, t][ok]
+                with np.errstate(invalid='ignore', divide='ignore'):
+                    herr[t, ok] = self.error(time, *pts, check_hull) / np.abs(res[2, t][ok])
+        return LevelHeightError(*(out + (herr.reshape(shape),)))
 
     def _need_covariance(self):
         if self.Covariance is None:
@@ -1275,6 +1380,53 @@ class ResidentGrid(object):
         val, idx, err = self.evaluate_peak_errors(self._coeffs_at(times), dC, axis=axis, kind=kind)
         return val.reshape(rest), idx.reshape(rest), err.reshape(rest)
 
+    def evaluate_crossings(self, C, level, axis=-1, which='first', direction='any', out=None):
+        """index (T, M) int32, M = Q / L columns as in evaluate_peaks: the position l of the first (which='last': last) pair of
+        neighbours (l, l + 1) along `axis` at which the density of coefficient row C[t] crosses `level` - both samples numbers
+        and direction='up': f[l] <= level <= f[l + 1]; 'down': f[l] >= level >= f[l + 1]; 'any': either -, -1 for a column
+        without such a pair: outside the hull, NaN coefficients, a NaN level, an axis of length 1.  level: a scalar, or
+        anything that broadcasts to (T, M).  Computed on the device from the resident basis, slab by slab
+        (vi_eval_resident_cross_f64); the volume is not copied to the host.  level_brackets turns the map into the brackets
+        of Estimate.level_height.  `out`: a preallocated array."""
+        axis, outer, L, inner = self._columns(axis)
+        if which not in CROSSING_WHICH:
+            raise ValueError("which must be 'first' or 'last', not %r" % (which,))
+        if direction not in CROSSING_DIRECTIONS:
+            raise ValueError("direction must be 'any', 'up' or 'down', not %r" % (direction,))
+        M = outer * inner
+        C = self._coeffs(C)
+        T = C.shape[0]
+        try:
+            level = np.ascontiguousarray(np.broadcast_to(np.asarray(level, dtype=np.float64), (T, M)))
+        except ValueError:
+            raise ValueError('level must be a scalar or broadcast to the shape %r' % ((T, M),))
+        out = _check_out(out, (T, M), np.int32)
+        if T == 0 or self.Q == 0:
+            out.fill(-1)                    # (columns of length zero: no pair of neighbours)
+            return out
+        h, dY = self.est.model.handle(), self._open(self.dY)
+        slab = self._slab(T, self.Q * 8 + M * 12)
+        work = slab * self.Q * 8
+
+        def call(tc, dCo, dI, dW, dL):
+            _lib.check(_lib.lib.vi_eval_resident_cross_f64(h, outer, L, inner, tc, dY.ptr, dCo, dL.ptr, CROSSING_WHICH[which],
+                                                           CROSSING_DIRECTIONS[direction], dI.ptr, dW.ptr, dW.nbytes),
+                       'vi_eval_resident_cross_f64')
+        return self._run(slab, C, (out,), call, work=work, also=(level,))[0]
+
+    def crossing(self, times, level, axis=-1, which='first', direction='any'):
+        """Crossing maps for a list of datetimes (coefficients of Estimate.get_C per time): the index map of
+        evaluate_crossings, (len(times),) + the grid shape without `axis`; level a scalar or anything that broadcasts to that
+        shape.  On a (lat, lon, alt) grid with the default axis and direction='up': the altitude index below the bottomside
+        crossing of the level - est.level_height(times, lat2d, lon2d, level, *level_brackets(alt, index)) refines it."""
+        axis, rest = self._rest(times, axis)
+        try:
+            level = np.broadcast_to(np.asarray(level, dtype=np.float64), rest)
+            level = level.reshape(len(times), int(np.prod(rest[1:], dtype=np.int64)))
+        except ValueError:
+            raise ValueError('level must be a scalar or broadcast to the shape %r' % (rest,))
+        return self.evaluate_crossings(self._coeffs_at(times), level, axis=axis, which=which, direction=direction).reshape(rest)
+
     @staticmethod
     def _weights(L, weights):
         if weights is None:
@@ -1389,7 +1541,8 @@ class ResidentRays(ResidentGrid):
       r(times), evaluate_coeffs(C)    the integrals of slant at one time per image, (T,) + ray shape, as one product (K2r);
       error(times), evaluate_errors   their standard errors sqrt(b^T dC b) (K2e) - the parameter's unit times metres too;
       peak, evaluate_peaks            the largest (smallest) integral along an axis of the ray shape and where it sits;
-      integrate, evaluate_integrals   weighted sums of the integrals along an axis, over the rays that enter the hull.
+      integrate, evaluate_integrals   weighted sums of the integrals along an axis, over the rays that enter the hull;
+      crossing, evaluate_crossings    where the integrals cross a level along an axis of the ray shape.
     NaN for a ray that does not enter the hull or has a non-finite end point, 0 for a segment of length zero inside it.
     peak_error, errors_at and integrate_error give the standard errors of those maxima and weighted sums in the same way.
     It holds no gradient basis: gradient and evaluate_gradients raise."""
