@@ -467,6 +467,47 @@ int  vi_eval_peak_f64(vi_model* model, int64_t T, int64_t Q, const double* d_lat
 int  vi_eval_level_f64(vi_model* model, int64_t T, int64_t Q, const double* d_lat, const double* d_lon, const double* d_ends,
                        const double* d_level, const double* d_C, const double* d_hull_eq, int32_t F, double hull_tol,
                        int32_t max_iter, double tol, double* d_out, int32_t* d_status, int32_t* d_iter);
+/* PEAKS AND LEVEL CROSSINGS ALONG STRAIGHT RAYS (the reference has none): the two searches above along an oblique line instead
+ * of a column's geodetic normal - the profile peak along a radar beam, the point where an oblique sounder's ray meets the plasma
+ * frequency, the place where a line of sight crosses an isodensity surface.  P rays, shared by the T coefficient rows: ray q runs
+ * from a_q to b_q, d_a and d_b (3, P) planar in ECEF metres (vi_eval_slant_f64's layout); with d = b - a,
+ * len = sqrt(dx^2 + dy^2 + dz^2) and u = d / len the point at the distance s metres from a is
+ * (fma(s, ux, ax), fma(s, uy, ay), fma(s, uz, az)), evaluated without a geodetic step.  After the walk of the chains u is turned
+ * as the model turns a position (Rodrigues, +theta0) and met with the unit vectors r', theta', phi' of the rotated spherical
+ * coordinates at the point: w, its components in the orthonormal frame of VI_FRAME_MODEL.  The Hessian of vi_eval_hess_f64 is a
+ * tensor in that frame and the direction of a straight line is constant, so
+ *     d1 = df/ds = w . grad f      d2 = d2f/ds2 = w^T H w      exactly.
+ * Point p = t*P + q (ray q of row t) reads the raw coefficient row d_C + t*N and
+ *   vi_eval_ray_peak_f64   the start d_start[p] and the bracket d_lo[p] <= d_start[p] <= d_hi[p] (metres from a), and runs the
+ *                          iteration of vi_eval_peak_f64 with s in place of h;
+ *                          d_out (4, T*P) planar: s, f, d1, d2.  d_status 0, 1, 2 as there, and
+ *                          3  the four outputs are NaN: an input is not finite, len is not positive and finite, not
+ *                             lo <= start <= hi, an END of the bracket (the points at lo and at hi) is outside the hull, or the
+ *                             coefficient row or the chains gave a non-finite f, d1 or d2
+ *   vi_eval_ray_level_f64  the bracket lo = d_ends[p] < hi = d_ends[T*P + p] and the level d_level[p], and runs the iteration
+ *                          of vi_eval_level_f64 with s in place of h (the walk at lo, the walk at hi, the secant start,
+ *                          safeguarded Newton); d_out (3, T*P) planar: s, f, d1.  d_status 0, 1, 2, 3 as there, 3 also for a
+ *                          ray whose len is not positive and finite.
+ * The hull: each lane tests the two ends of its own bracket against the F half-spaces d_hull_eq (F x 4 doubles, device memory)
+ * with K2l's expression and criterion, fma(nx, X, fma(ny, Y, fma(nz, Z, off))) <= hull_tol; F = 0: no test.  There is no mask
+ * pass, no test of a later iterate and no "left the hull" status in either search: the iterates stay between two points inside
+ * a convex set.
+ * Kernels k_line_peak_sph and k_line_level_sph (csrc/vi_line.hip): a lane per ray, the grid (blocks of 256 rays, rows), the
+ * coefficient reads wave-uniform; a lane that has stopped stores at once and is frozen, a wave leaves when none of its lanes is
+ * searching, a wave without a lane to search leaves before any walk; more than 65 535 rows go in slices.  The bits of a point
+ * depend on its ray, its row, bracket, start or level, kind, max_iter and tol - not on P, T, the other points or its place among
+ * them.  A NaN in a row reaches only that row.
+ * Models and orders as vi_eval_peak_f64, others return VI_ERR_UNSUPPORTED and launch nothing; kind other than +-1, max_iter < 0
+ * or > 10000, tol not finite or <= 0, a null pointer (d_iter excepted), a negative size, P > 2^31 - 1 or F > 0 without facets
+ * return VI_ERR_INVALID.  T = 0 or P = 0 is a no-op.  Asynchronous on the context's stream; timed for vi_eval_kernel_ms like
+ * their siblings (tests/test_gpu_ray.py). */
+int  vi_eval_ray_peak_f64(vi_model* model, int64_t T, int64_t P, const double* d_a, const double* d_b, const double* d_start,
+                          const double* d_lo, const double* d_hi, const double* d_C, const double* d_hull_eq, int32_t F,
+                          double hull_tol, int32_t kind, int32_t max_iter, double tol, double* d_out, int32_t* d_status,
+                          int32_t* d_iter);
+int  vi_eval_ray_level_f64(vi_model* model, int64_t T, int64_t P, const double* d_a, const double* d_b, const double* d_ends,
+                           const double* d_level, const double* d_C, const double* d_hull_eq, int32_t F, double hull_tol,
+                           int32_t max_iter, double tol, double* d_out, int32_t* d_status, int32_t* d_iter);
 /* Column maps of many timesteps on the same resident grid, without the volume.  The grid is seen as (outer, L, inner), point
  * q = (o*L + l)*inner + i, column m = o*inner + i: any axis of a C-ordered grid, the last one with inner = 1.  What a user of
  * Estimate.__call__ (estimate.py:110-123) takes from a (lat, lon, alt) volume per column: the peak of the parameter along
@@ -514,7 +555,7 @@ int    vi_eval_resident_cross_f64(vi_model* model, int64_t outer, int64_t L, int
  * others return VI_ERR_UNSUPPORTED from vi_eval_f64 while the flag is set. */
 int  vi_model_set_eval_precision(vi_model* model, int32_t chain_f32);
 /* device time (ms) of the evaluation kernel launches of the last vi_eval_f64 / vi_eval_track_f64 / vi_eval_track_grad_f64 / vi_eval_slant_f64 / vi_eval_slant_basis_f64 / vi_eval_resident_f64 /
- * vi_eval_resident_err_f64 / vi_eval_resident_err_at_f64 / vi_eval_resident_gradcov_f64 / vi_eval_grad_cov_f64 (its last chunk) / vi_eval_hess_f64 / vi_eval_hess_basis_f64 / vi_eval_peak_f64 / vi_eval_level_f64 / vi_eval_records_gradcov_f64 / vi_eval_track_grad_cov_f64 /vi_eval_resident_peak_f64 / vi_eval_resident_cross_f64 call on this context, from HIP events recorded on the context's stream around them (the preparation kernels are excluded).
+ * vi_eval_resident_err_f64 / vi_eval_resident_err_at_f64 / vi_eval_resident_gradcov_f64 / vi_eval_grad_cov_f64 (its last chunk) / vi_eval_hess_f64 / vi_eval_hess_basis_f64 / vi_eval_peak_f64 / vi_eval_level_f64 / vi_eval_ray_peak_f64 / vi_eval_ray_level_f64 / vi_eval_records_gradcov_f64 / vi_eval_track_grad_cov_f64 /vi_eval_resident_peak_f64 / vi_eval_resident_cross_f64 call on this context, from HIP events recorded on the context's stream around them (the preparation kernels are excluded).
  * The events are recorded only while vi_ctx_set_eval_timing(ctx, 1) is in force (default: off - the pair costs a 0.2 ms call about 7 us);
  * vi_eval_kernel_ms fails with VI_ERR_ARG while it is off or before a call has been timed. */
 int  vi_ctx_set_eval_timing(vi_ctx* ctx, int32_t on);

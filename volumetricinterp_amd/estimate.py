@@ -376,6 +376,114 @@ def level_brackets(alt_axis, index):
     return tuple(np.where(none, np.nan, a) for a in (np.minimum(below, above), np.maximum(below, above)))
 
 
+RAY_PEAK_FIELDS = ('distance', 'value', 'slope', 'curvature', 'status', 'iterations')
+RayPeak = collections.namedtuple('RayPeak', RAY_PEAK_FIELDS)
+RayPeakError = collections.namedtuple('RayPeakError', RAY_PEAK_FIELDS + ('distance_error', 'value_error'))
+RAY_LEVEL_FIELDS = ('distance', 'value', 'slope', 'status', 'iterations')
+RayLevel = collections.namedtuple('RayLevel', RAY_LEVEL_FIELDS)
+RayLevelError = collections.namedtuple('RayLevelError', RAY_LEVEL_FIELDS + ('distance_error',))
+
+
+def _ray_lines(start, end, coords):
+    """(shape, a, b, u, length) of the rays of slant_rays: the ray shape S, the end points (P, 3) in ECEF metres, the unit
+    directions (P, 3) and the lengths (P,) - NaN directions for a ray of length zero."""
+    _, _, shape, a, b = slant_rays(start, end, 1, None, coords)
+    a, b = a.T, b.T
+    d = b - a
+    length = np.sqrt(d[:, 0]**2 + d[:, 1]**2 + d[:, 2]**2)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        u = d / length[:, None]
+    return shape, a, b, u, length
+
+
+def ray_points(start, end, distance, coords='geodetic'):
+    """(gdlat, gdlon, gdalt) of the points at `distance` metres from `start` on the straight rays from `start` to `end`
+    (triples of arrays, as Estimate.slant takes them): the points Estimate.ray_peak and ray_level report, for __call__, error
+    and the other point entries.  distance: the ray shape S with any leading axes - (T,) + S as ray_peak returns it.  Three
+    arrays of the shape of distance, NaN where distance is.  On the host, through geodesy.ecef2geodetic."""
+    shape, a, _, u, _ = _ray_lines(start, end, coords)
+    distance = np.asarray(distance, dtype=np.float64)
+    nd = len(shape)
+    if distance.ndim < nd or distance.shape[distance.ndim - nd:] != shape:
+        raise ValueError('distance must have the ray shape %r as its last axes, not %r' % (shape, distance.shape))
+    s = distance.reshape(-1, a.shape[0])
+    with np.errstate(invalid='ignore'):
+        X = a.T[:, None, :] + s[None] * u.T[:, None, :]                  # (3, lead, P)
+        lat, lon, alt = geodesy.ecef2geodetic(X[0], X[1], X[2])
+    return tuple(np.where(np.isfinite(s), v, np.nan).reshape(distance.shape) for v in (lat, lon, alt))
+
+
+def ray_samples(eq, tol, start, end, n=64, coords='geodetic'):
+    """(dist, gdlat, gdlon, gdalt), each S + (n,), S the ray shape: n equispaced samples on the part of every ray inside the
+    hull (eq, tol) of hull_equations - the chord hull_chords gives -, as distances in metres from `start` and as geodetic points.
+    The two end samples are pulled inside by one part in 10^6 of the chord, so that rounding does not put them outside.  A ray
+    that misses the hull has NaN throughout.  est.resident_grid(gdlat, gdlon, gdalt) on these points gives the coarse stage of
+    ray_peak and ray_level: g.peak(times) and g.crossing(times, level) along the last axis, ray_peak_brackets and
+    ray_level_brackets turn their index maps into brackets.  On the host."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 2:
+        raise ValueError('n must be an integer of at least 2, not %r' % (n,))
+    shape, a, b, u, length = _ray_lines(start, end, coords)
+    s0, s1 = hull_chords(np.zeros((0, 4)) if eq is None else eq, tol, a, b)
+    frac = np.linspace(0., 1., int(n))
+    frac[0], frac[-1] = 1e-6, 1. - 1e-6
+    with np.errstate(invalid='ignore'):
+        dist = length[:, None] * (s0[:, None] + (s1 - s0)[:, None] * frac[None, :])       # (P, n)
+        X = a.T[:, :, None] + dist[None] * u.T[:, :, None]
+        lat, lon, alt = geodesy.ecef2geodetic(X[0], X[1], X[2])
+    ok = np.isfinite(dist)
+    return tuple(np.where(ok, v, np.nan).reshape(shape + (int(n),)) for v in (dist, lat, lon, alt))
+
+
+def _ray_index(dist, index, last):
+    """(dist, index, none) of the two bracket makers below: dist broadcast to index.shape + (n,), the index checked against
+    [-1, last) and with 0 in place of -1, and where it was -1."""
+    dist = np.asarray(dist, dtype=np.float64)
+    if dist.ndim < 1 or dist.shape[-1] < 1:
+        raise ValueError('dist must have the samples of a ray on its last axis')
+    index = np.asarray(index)
+    if index.dtype.kind not in 'iu':
+        raise ValueError('index must be an integer array, not %s' % index.dtype)
+    index = index.astype(np.int64)
+    n = dist.shape[-1]
+    if index.size and (index.min() < -1 or index.max() >= n - last):
+        raise ValueError('index must lie in [-1, %d)' % (n - last))
+    try:
+        dist = np.broadcast_to(dist, index.shape + (n,))
+    except ValueError:
+        raise ValueError('dist %r does not broadcast to the index map %r with the samples on a last axis'
+                         % (dist.shape, index.shape))
+    none = index < 0
+    return dist, np.where(none, 0, index), none
+
+
+def ray_peak_brackets(dist, index):
+    """(s_start, s_lo, s_hi) for Estimate.ray_peak from the sample distances of ray_samples, S + (n,), and the index map
+    (T,) + S (or S) that ResidentGrid.peak gives on those samples along their last axis: the distance of the sample at `index`
+    and those of its two neighbours on the ray - the sample itself where it is the first or the last -, NaN where index is -1 (a
+    ray without a peak; ray_peak gives it status 3) and where the ray has no samples.  Three float64 arrays of the shape of
+    index.  The analogue of peak_brackets.  On the host."""
+    dist, i, none = _ray_index(dist, index, 0)
+    n = dist.shape[-1]
+    pick = lambda j: np.take_along_axis(dist, j[..., None], axis=-1)[..., 0]
+    start, below, above = pick(i), pick(np.maximum(i - 1, 0)), pick(np.minimum(i + 1, n - 1))
+    with np.errstate(invalid='ignore'):
+        lo, hi = np.minimum(np.minimum(below, above), start), np.maximum(np.maximum(below, above), start)
+    return tuple(np.where(none, np.nan, a) for a in (start, lo, hi))
+
+
+def ray_level_brackets(dist, index):
+    """(s_lo, s_hi) for Estimate.ray_level from the sample distances of ray_samples and the index map that ResidentGrid.crossing
+    gives on those samples along their last axis: the distances of the samples at `index` and at `index` + 1, the smaller first;
+    NaN where index is -1 (a ray without a crossing; ray_level gives it status 3).  index: integers in [-1, n - 1).  Two float64
+    arrays of the shape of index.  The analogue of level_brackets.  On the host."""
+    dist, i, none = _ray_index(dist, index, 1)
+    n = dist.shape[-1]
+    pick = lambda j: np.take_along_axis(dist, j[..., None], axis=-1)[..., 0]
+    below, above = pick(i), pick(np.minimum(i + 1, n - 1))
+    with np.errstate(invalid='ignore'):
+        return tuple(np.where(none, np.nan, a) for a in (np.minimum(below, above), np.maximum(below, above)))
+
+
 class Estimate(object):
     def __init__(self, coeff_filename, timetol=60., timeinterp=False, ctx=None):
         self.timetol = timetol
@@ -728,6 +836,161 @@ class Estimate(object):
                 with np.errstate(invalid='ignore', divide='ignore'):
                     herr[t, ok] = self.error(time, *pts, check_hull) / np.abs(res[2, t][ok])
         return LevelHeightError(*(out + (herr.reshape(shape),)))
+
+    def ray_peak(self, times, start, end, s_start, s_lo, s_hi, kind='max', tol=1e-3, max_iter=48, coords='geodetic',
+                 check_hull=True, error=False):
+        """Peaks along straight rays: per ray from `start` to `end` and time the distance from `start`, in [s_lo, s_hi] metres,
+        at which the fitted parameter has its maximum (kind='min': minimum) ALONG THE RAY, and the parameter there - the profile
+        peak along a radar beam, to set beside its range gates.  peak_height's safeguarded Newton search with the distance s
+        along the line in place of the height: value, slope df/ds = w . grad f and curvature d2f/ds2 = w^T H w - w the ray's unit
+        direction in the orthonormal frame of gradient(frame='model') at the point, H the tensor of hessian(frame='model'), so
+        that the curvature is exact on a straight line - come from one walk of the basis per iteration.  All rays and times in
+        ONE library call (vi_eval_ray_peak_f64, kernel k_line_peak_sph, include/vinterp.h has the geometry and the iteration).
+
+        times: one naive-UTC datetime or a sequence of T of them; the coefficients of get_C per time, as peak_height takes
+        them (every ray at every time; rays with a time each: a call per group of rays).  start, end, coords: the rays, as slant
+        takes them, of the broadcast shape S.  s_start, s_lo, s_hi: metres from `start`, broadcast to (T,) + S (to S for one
+        time), s_lo <= s_start <= s_hi; ray_samples, a resident grid on its points and ray_peak_brackets make them.  tol: the
+        search stops when a step is at most tol metres.  max_iter: at most 10000.
+
+        Returns the named tuple (distance, value, slope, curvature, status, iterations), each (T,) + S (S for one time):
+        status 0  an interior peak: converged, the curvature has the sign of the kind, farther than tol from s_lo and s_hi
+               1  converged, but onto an end of the bracket or with a curvature of the wrong sign: no interior peak
+               2  not converged within max_iter; max_iter=0 evaluates the start
+               3  nothing to report: an end of the bracket - the point at s_lo or at s_hi - is outside the hull (check_hull), an
+                  input is NaN (what ray_peak_brackets makes of a ray without a sampled peak), not s_lo <= s_start <= s_hi, the
+                  ray has no length, or the record or the basis is not finite there
+        distance and value are NaN wherever status is not 0; slope and curvature are those of the last iterate (NaN with status
+        3).  Both ends of every bracket are tested against the hull on the device; the iterates between them need no test -
+        the hull is convex -, so there is no host pass and no status 4.  ray_points gives the geodetic points of the distances.
+
+        error=True: the named tuple grows by (distance_error, value_error), first order, NaN where status is not 0:
+        distance_error = sqrt(w^T cov w) / |curvature| with gradient_covariance(frame='model') at the peak, value_error =
+        error() there.  The existing entries called once per time at the found points, not fused into the search.  Raises
+        ValueError when the Estimate holds no covariance.  sphharmlag only, at the orders of gradient."""
+        if kind not in PEAK_HEIGHT_KINDS:
+            raise ValueError("kind must be 'max' or 'min', not %r" % (kind,))
+        q = self._ray_search(times, start, end, coords, (s_start, s_lo, s_hi), 's_start, s_lo and s_hi', tol, max_iter, error)
+        T, P = q['T'], q['P']
+        res, status, iters = np.full((4, T, P), np.nan), np.full((T, P), 3, dtype=np.int32), np.zeros((T, P), dtype=np.int32)
+        if T and P:
+            eq, F, htol = self._hull_args(check_hull)
+            with self.model.ctx.scope() as dev:
+                da, db, d0, dlo, dhi, dC_ = (dev.up(v) for v in (q['a'], q['b']) + q['per'] + (q['C'],))
+                dO, dS, dI = dev.empty((4, T, P)), dev.empty((T, P), np.int32), dev.empty((T, P), np.int32)
+                _lib.check(_lib.lib.vi_eval_ray_peak_f64(self.model.handle(), T, P, da.ptr, db.ptr, d0.ptr, dlo.ptr, dhi.ptr,
+                                                         dC_.ptr, _ptr(None if eq is None else dev.up(eq)), F, htol,
+                                                         PEAK_HEIGHT_KINDS[kind], int(max_iter), q['tol'], dO.ptr, dS.ptr, dI.ptr),
+                           'vi_eval_ray_peak_f64')
+                res, status, iters = dO.download(), dS.download(), dI.download()
+        res[:2, status != 0] = np.nan
+        shape = q['shape']
+        out = tuple(r.reshape(shape) for r in res) + (status.reshape(shape), iters.reshape(shape))
+        if not error:
+            return RayPeak(*out)
+        derr, verr = np.full((T, P), np.nan), np.full((T, P), np.nan)
+        for t, time in enumerate(q['times']):
+            ok = status[t] == 0
+            if ok.any():
+                pts, w = self._ray_frame(q, ok, res[0, t][ok])
+                cov = gradcov_matrix(self._gradient_covariance(time, *pts, check_hull, 'model'))
+                with np.errstate(invalid='ignore', divide='ignore'):
+                    derr[t, ok] = np.sqrt(np.einsum('pi,pij,pj->p', w, cov, w)) / np.abs(res[3, t][ok])
+                verr[t, ok] = self.error(time, *pts, check_hull)
+        return RayPeakError(*(out + (derr.reshape(shape), verr.reshape(shape))))
+
+    def ray_level(self, times, start, end, level, s_lo, s_hi, tol=1e-3, max_iter=48, coords='geodetic', check_hull=True,
+                  error=False):
+        """Level crossings along straight rays: per ray from `start` to `end` and time the distance from `start`, in
+        [s_lo, s_hi] metres, at which the fitted parameter crosses `level` ALONG THE RAY - the point where an oblique sounder's
+        ray meets the plasma frequency, the place where a line of sight enters a patch (crosses an isodensity surface).
+        level_height's safeguarded Newton search with the distance s along the line in place of the height: value and slope
+        df/ds = w . grad f, w the ray's unit direction in the frame of gradient(frame='model') at the point, from one gradient
+        walk of the basis per iteration.  All rays and times in ONE library call (vi_eval_ray_level_f64, kernel
+        k_line_level_sph).
+
+        times, start, end, coords: as ray_peak.  level (the parameter's unit), s_lo, s_hi (metres from `start`): broadcast to
+        (T,) + S (to S for one time), s_lo < s_hi; ray_samples, a resident grid on its points (ResidentGrid.crossing) and
+        ray_level_brackets make the bracket.  tol, max_iter: as ray_peak.
+
+        Returns the named tuple (distance, value, slope, status, iterations), each (T,) + S (S for one time):
+        status 0  a crossing: the value is the level exactly, or the last step was at most tol
+               1  the parameter minus the level has one sign at s_lo and at s_hi: no crossing is bracketed
+               2  not converged within max_iter
+               3  nothing to report: an end of the bracket is outside the hull (check_hull), an input is NaN, not s_lo < s_hi,
+                  the ray has no length, or the record or the basis is not finite there
+        distance and value are NaN wherever status is not 0; slope is that of the last iterate (NaN with status 1 and 3), its
+        sign tells entering (> 0) from leaving.  The hull as in ray_peak.
+
+        error=True: the named tuple grows by distance_error = error() / |slope| at the crossing, first order, NaN where status
+        is not 0; the existing entry called once per time, not fused.  sphharmlag only, at the orders of gradient."""
+        q = self._ray_search(times, start, end, coords, (level, s_lo, s_hi), 'level, s_lo and s_hi', tol, max_iter, error)
+        T, P = q['T'], q['P']
+        res, status, iters = np.full((3, T, P), np.nan), np.full((T, P), 3, dtype=np.int32), np.zeros((T, P), dtype=np.int32)
+        if T and P:
+            lev, lo, hi = q['per']
+            eq, F, htol = self._hull_args(check_hull)
+            with self.model.ctx.scope() as dev:
+                da, db, dends, dlev, dC_ = (dev.up(v) for v in (q['a'], q['b'], np.stack((lo, hi)), lev, q['C']))
+                dO, dS, dI = dev.empty((3, T, P)), dev.empty((T, P), np.int32), dev.empty((T, P), np.int32)
+                _lib.check(_lib.lib.vi_eval_ray_level_f64(self.model.handle(), T, P, da.ptr, db.ptr, dends.ptr, dlev.ptr, dC_.ptr,
+                                                          _ptr(None if eq is None else dev.up(eq)), F, htol, int(max_iter),
+                                                          q['tol'], dO.ptr, dS.ptr, dI.ptr), 'vi_eval_ray_level_f64')
+                res, status, iters = dO.download(), dS.download(), dI.download()
+        res[:2, status != 0] = np.nan
+        shape = q['shape']
+        out = tuple(r.reshape(shape) for r in res) + (status.reshape(shape), iters.reshape(shape))
+        if not error:
+            return RayLevel(*out)
+        derr = np.full((T, P), np.nan)
+        for t, time in enumerate(q['times']):
+            ok = status[t] == 0
+            if ok.any():
+                pts, _ = self._ray_frame(q, ok, res[0, t][ok])
+                with np.errstate(invalid='ignore', divide='ignore'):
+                    derr[t, ok] = self.error(time, *pts, check_hull) / np.abs(res[2, t][ok])
+        return RayLevelError(*(out + (derr.reshape(shape),)))
+
+    def _ray_search(self, times, start, end, coords, per, names, tol, max_iter, error):
+        """What ray_peak and ray_level share ahead of their library call: the arguments checked, the rays as (3, P) planar end
+        points, the three per-(time, ray) arrays `per` broadcast to (T, P) and the coefficient rows of the times."""
+        tol = float(tol)
+        if not (np.isfinite(tol) and tol > 0.):
+            raise ValueError('tol must be finite and positive, not %r' % (tol,))
+        if not isinstance(max_iter, (int, np.integer)) or isinstance(max_iter, bool) or not 0 <= max_iter <= 10000:
+            raise ValueError('max_iter must be an integer in [0, 10000], not %r' % (max_iter,))
+        if error:
+            self._need_covariance()
+        single = isinstance(times, dt.datetime)
+        times = [times] if single else list(times)
+        _, _, S, a, b = slant_rays(start, end, 1, None, coords)
+        T, P, N = len(times), a.shape[1], self.model.nbasis
+        full = (T,) + S
+        try:
+            per = tuple(np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), full)).reshape(T, P) for v in per)
+        except ValueError:
+            raise ValueError('%s must broadcast to the shape %r' % (names, full))
+        C = np.empty((T, N))
+        for t, time in enumerate(times):
+            C[t] = self.get_C(time)[0]
+        return dict(times=times, T=T, P=P, a=np.ascontiguousarray(a), b=np.ascontiguousarray(b), per=per, C=C, tol=tol,
+                    shape=S if single else full)
+
+    def _ray_frame(self, q, ok, distance):
+        """((gdlat, gdlon, gdalt), w) at `distance` on the rays `ok` (a mask over the P rays) of _ray_search's `q`: the geodetic
+        points, and the rays' unit directions in the model's orthonormal frame there - u turned into east, north, up at the
+        point and then through Model.gradient_frame (orthogonal: w = F^T u_enu)."""
+        a, b = q['a'][:, ok].T, q['b'][:, ok].T
+        d = b - a
+        u = d / np.sqrt(d[:, 0]**2 + d[:, 1]**2 + d[:, 2]**2)[:, None]
+        X = a + distance[:, None] * u
+        lat, lon, alt = geodesy.ecef2geodetic(X[:, 0], X[:, 1], X[:, 2])
+        sl, cl, so, co = (f(np.radians(v)) for v in (lat, lon) for f in (np.sin, np.cos))
+        enu = np.stack([-so * u[:, 0] + co * u[:, 1],
+                        -sl * co * u[:, 0] - sl * so * u[:, 1] + cl * u[:, 2],
+                        cl * co * u[:, 0] + cl * so * u[:, 1] + sl * u[:, 2]], axis=1)
+        w = np.einsum('pic,pi->pc', self.model.gradient_frame(lat, lon, alt), enu)
+        return (lat, lon, alt), w
 
     def _need_covariance(self):
         if self.Covariance is None:
