@@ -508,6 +508,64 @@ int  vi_eval_ray_peak_f64(vi_model* model, int64_t T, int64_t P, const double* d
 int  vi_eval_ray_level_f64(vi_model* model, int64_t T, int64_t P, const double* d_a, const double* d_b, const double* d_ends,
                            const double* d_level, const double* d_C, const double* d_hull_eq, int32_t F, double hull_tol,
                            int32_t max_iter, double tol, double* d_out, int32_t* d_status, int32_t* d_iter);
+/* MAXIMA AND MINIMA IN THREE DIMENSIONS (the reference has none): the searches above follow a direction the caller chooses - a
+ * column's normal, a line of sight - and give the extremum along it.  This one gives the point itself: for T coefficient rows and
+ * P searches per row the point x inside the ball |x - x0| <= radius and inside the hull at which the fitted parameter has its
+ * maximum (kind +1) or minimum (-1) - the centre of a polar-cap patch or of a depletion -, its value, gradient and Hessian there
+ * (the principal curvatures are the size of the patch).  Search p = t*P + q reads the start d_x0[p], d_x0[T*P + p],
+ * d_x0[2*T*P + p] (ECEF metres), d_radius[p] (metres) and the raw coefficient row d_C + t*N.  One walk of the chains from the
+ * ECEF point (no geodetic step) gives f, the gradient and the Hessian tensor in the orthonormal frame (r', theta', phi') of
+ * VI_FRAME_MODEL; with E the three unit vectors of that frame at the point written in ECEF,
+ *     g = E^T g_model      H = E^T H_model E
+ * are the plain Cartesian gradient and matrix of second derivatives - the Hessian is a tensor, there are no connection terms -,
+ * and Newton's iteration runs in R^3.  With sg = kind, |.| the Euclidean norm and ms = max_step, or radius / 8 where max_step
+ * is 0:
+ *     x0 or radius not finite, or not radius > 0: status 3, stop
+ *     x = x0; have = done = full = false; it = 0; D = ms
+ *     loop:  f, g, H at x                                                        (one walk)
+ *            ins = x inside every facet (K2l's expression and tolerance, as the rays' ends) and |x - x0| <= radius
+ *            f, g or H not finite, or (not have and not ins): status 3, stop
+ *            done or it == max_iter: report x, f, g, H;
+ *                  status = 2 if not done, else 0 if full and ins and all three pivots of -sg H > 0, else 1;  stop
+ *            it += 1;  gn = |g|
+ *            have and (not ins or not (sg f >= sg fb or (full and gn < gb))):     reject - backtrack along the same step
+ *                  full = false;  |d| <= tol: x = xb, done = true;  else: d = d / 4, D = |d|, x = xb + d;  next pass
+ *            have: D = min(2 D, ms)
+ *            xb = x; fb = f; gb = gn; have = true
+ *            gn == 0: d = 0, n = 0, full = true  (a zero gradient is a step of zero length; nothing is divided by it)
+ *            else: solve (-sg H) d = sg g by LDL^T in the fixed order 1, 2, 3 - p1 = a11, l21 = a21/p1, l31 = a31/p1,
+ *                  p2 = a22 - l21 a21, t = a32 - l31 a21, l32 = t/p2, p3 = a33 - l31 a31 - l32 t -, every pivot that is not
+ *                  > mu = gn / D replaced by mu;  full = no pivot was replaced;  n = |d|;
+ *                  n > D: d = d (D / n), n = D, full = false
+ *            done = n <= tol;  x = x + d
+ * The floored pivots make every step an ascent direction of sg f and bound its length by about D where the curvature has the
+ * wrong sign.  A step is accepted by the value, or - a full Newton step - by the gradient norm: close to the extremum the gain
+ * 1/2 |H| d^2 falls below the rounding of f and the value alone cannot decide.  A rejected iterate, or one outside the hull or
+ * the ball, backtracks towards the best point - a quarter of the step at a time, until a step of at most tol is rejected too -, so
+ * that the result lies in the region (a last Newton step of at most tol is not tested) and a search that ends on the boundary
+ * ends within tol of a point outside.  Every pass stops the search or adds one to `it`, which max_iter bounds; a converged search makes it + 1 walks.
+ *   d_out     (13, T*P) planar: x, y, z, f, g (3), H (6: xx yy zz xy xz yz, the order of vi_eval_hess_f64), all in ECEF; NaN
+ *             with status 3, the last iterate's with 1 and 2 (max_iter = 0: the start and its values)
+ *   d_status  0  an interior extremum: the last step was an unmodified, unclipped Newton step of at most tol, the result is
+ *                inside the region and H there is definite with the sign of the kind
+ *             1  converged without one: onto the boundary of the hull or of the ball, or at a point of the wrong curvature
+ *             2  not done within max_iter
+ *             3  the outputs are NaN: the start is outside the hull or not finite, radius is not finite and positive, or the
+ *                coefficient row or the chains gave a non-finite f, g or H
+ *   d_iter    the passes that did not stop the search, or NULL
+ * Kernel k_extremum_sph (csrc/vi_extremum.hip): a lane per search, the grid (blocks of 256 searches, rows), the coefficient and
+ * facet reads wave-uniform; a lane that has stopped stores at once and is frozen, a wave leaves when none of its lanes is
+ * searching, a wave without a lane to search leaves before any walk; more than 65 535 rows go in slices.  The hull test of
+ * every iterate is in the kernel (F = 0: no test); there is no host pass.  The bits of a search depend on its start, radius,
+ * row, kind, max_step, max_iter, tol and the facet list - not on P, T, the other searches or its place among them.  A NaN in a
+ * row reaches only that row.
+ * Models and orders as vi_eval_peak_f64, others return VI_ERR_UNSUPPORTED and launch nothing; kind other than +-1, max_iter < 0
+ * or > 10000, tol not finite or <= 0, max_step not finite or < 0, a null pointer (d_iter excepted), a negative size,
+ * P > 2^31 - 1 or F > 0 without facets return VI_ERR_INVALID.  T = 0 or P = 0 is a no-op.  Asynchronous on the context's
+ * stream; timed for vi_eval_kernel_ms like its siblings (tests/test_gpu_extremum.py). */
+int  vi_eval_extremum_f64(vi_model* model, int64_t T, int64_t P, const double* d_x0, const double* d_radius, const double* d_C,
+                          const double* d_hull_eq, int32_t F, double hull_tol, int32_t kind, double max_step, int32_t max_iter,
+                          double tol, double* d_out, int32_t* d_status, int32_t* d_iter);
 /* Column maps of many timesteps on the same resident grid, without the volume.  The grid is seen as (outer, L, inner), point
  * q = (o*L + l)*inner + i, column m = o*inner + i: any axis of a C-ordered grid, the last one with inner = 1.  What a user of
  * Estimate.__call__ (estimate.py:110-123) takes from a (lat, lon, alt) volume per column: the peak of the parameter along
@@ -555,7 +613,7 @@ int    vi_eval_resident_cross_f64(vi_model* model, int64_t outer, int64_t L, int
  * others return VI_ERR_UNSUPPORTED from vi_eval_f64 while the flag is set. */
 int  vi_model_set_eval_precision(vi_model* model, int32_t chain_f32);
 /* device time (ms) of the evaluation kernel launches of the last vi_eval_f64 / vi_eval_track_f64 / vi_eval_track_grad_f64 / vi_eval_slant_f64 / vi_eval_slant_basis_f64 / vi_eval_resident_f64 /
- * vi_eval_resident_err_f64 / vi_eval_resident_err_at_f64 / vi_eval_resident_gradcov_f64 / vi_eval_grad_cov_f64 (its last chunk) / vi_eval_hess_f64 / vi_eval_hess_basis_f64 / vi_eval_peak_f64 / vi_eval_level_f64 / vi_eval_ray_peak_f64 / vi_eval_ray_level_f64 / vi_eval_records_gradcov_f64 / vi_eval_track_grad_cov_f64 /vi_eval_resident_peak_f64 / vi_eval_resident_cross_f64 call on this context, from HIP events recorded on the context's stream around them (the preparation kernels are excluded).
+ * vi_eval_resident_err_f64 / vi_eval_resident_err_at_f64 / vi_eval_resident_gradcov_f64 / vi_eval_grad_cov_f64 (its last chunk) / vi_eval_hess_f64 / vi_eval_hess_basis_f64 / vi_eval_peak_f64 / vi_eval_level_f64 / vi_eval_ray_peak_f64 / vi_eval_ray_level_f64 / vi_eval_extremum_f64 / vi_eval_records_gradcov_f64 / vi_eval_track_grad_cov_f64 /vi_eval_resident_peak_f64 / vi_eval_resident_cross_f64 call on this context, from HIP events recorded on the context's stream around them (the preparation kernels are excluded).
  * The events are recorded only while vi_ctx_set_eval_timing(ctx, 1) is in force (default: off - the pair costs a 0.2 ms call about 7 us);
  * vi_eval_kernel_ms fails with VI_ERR_ARG while it is off or before a call has been timed. */
 int  vi_ctx_set_eval_timing(vi_ctx* ctx, int32_t on);

@@ -124,6 +124,8 @@ _sig('vi_eval_ray_peak_f64', C.c_int, VOIDP, I64, I64, VOIDP, VOIDP, VOIDP, VOID
      C.c_int32, C.c_double, VOIDP, VOIDP, VOIDP)
 _sig('vi_eval_ray_level_f64', C.c_int, VOIDP, I64, I64, VOIDP, VOIDP, VOIDP, VOIDP, VOIDP, VOIDP, C.c_int32, C.c_double, C.c_int32,
      C.c_double, VOIDP, VOIDP, VOIDP)
+_sig('vi_eval_extremum_f64', C.c_int, VOIDP, I64, I64, VOIDP, VOIDP, VOIDP, VOIDP, C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_int32,
+     C.c_double, VOIDP, VOIDP, VOIDP)
 _sig('vi_eval_resident_cross_f64', C.c_int, VOIDP, I64, I64, I64, I64, VOIDP, VOIDP, VOIDP, C.c_int32, C.c_int32, VOIDP, VOIDP,
      C.c_size_t)
 _sig('vi_eval_records_gradcov_f64', C.c_int, VOIDP, I64, VOIDP, VOIDP, VOIDP, I64, VOIDP, VOIDP)
@@ -148,7 +150,7 @@ _sig('vi_rccl_init', C.c_int, VOIDP, C.c_int, C.c_int, C.c_char_p)
 _sig('vi_rccl_bcast_f64', C.c_int, VOIDP, VOIDP, I64, C.c_int)
 _sig('vi_rccl_destroy', C.c_int, VOIDP)
 
-EXPORTS = ['vi_eval_ray_peak_f64', 'vi_eval_ray_level_f64', 'vi_eval_level_f64', 'vi_eval_resident_cross_f64', 'vi_eval_peak_f64', 'vi_eval_hess_f64', 'vi_eval_hess_basis_f64', 'vi_eval_resident_err_at_f64', 'vi_eval_records_gradcov_f64', 'vi_eval_track_grad_cov_f64', 'vi_eval_records_err_f64', 'vi_eval_track_err_f64', 'vi_eval_slant_err_f64', 'vi_eval_track_grad_f64', 'vi_eval_track_f64', 'vi_eval_slant_f64', 'vi_eval_slant_basis_f64', 'vi_eval_resident_peak_f64', 'vi_eval_resident_peak_work_bytes', 'vi_reduce_basis_f64', 'vi_eval_basis_f64', 'vi_eval_grad_basis_f64', 'vi_eval_resident_f64', 'vi_eval_resident_err_f64', 'vi_eval_resident_gradcov_f64', 'vi_eval_grad_cov_f64', 'vi_host_alloc', 'vi_host_free', 'vi_model_set_eval_precision', 'vi_solve_rounds', 'vi_grad_basis_f64', 'vi_eval_grad_f64', 'vi_eval_err_f64', 'vi_eval_kernel_ms', 'vi_ctx_set_eval_timing', 'vi_solve_timing', 'vi_rccl_unique_id', 'vi_rccl_init', 'vi_rccl_bcast_f64', 'vi_rccl_destroy', 'vi_abi_version', 'vi_device_count', 'vi_ctx_create', 'vi_ctx_destroy', 'vi_ctx_sync', 'vi_last_error',
+EXPORTS = ['vi_eval_extremum_f64', 'vi_eval_ray_peak_f64', 'vi_eval_ray_level_f64', 'vi_eval_level_f64', 'vi_eval_resident_cross_f64', 'vi_eval_peak_f64', 'vi_eval_hess_f64', 'vi_eval_hess_basis_f64', 'vi_eval_resident_err_at_f64', 'vi_eval_records_gradcov_f64', 'vi_eval_track_grad_cov_f64', 'vi_eval_records_err_f64', 'vi_eval_track_err_f64', 'vi_eval_slant_err_f64', 'vi_eval_track_grad_f64', 'vi_eval_track_f64', 'vi_eval_slant_f64', 'vi_eval_slant_basis_f64', 'vi_eval_resident_peak_f64', 'vi_eval_resident_peak_work_bytes', 'vi_reduce_basis_f64', 'vi_eval_basis_f64', 'vi_eval_grad_basis_f64', 'vi_eval_resident_f64', 'vi_eval_resident_err_f64', 'vi_eval_resident_gradcov_f64', 'vi_eval_grad_cov_f64', 'vi_host_alloc', 'vi_host_free', 'vi_model_set_eval_precision', 'vi_solve_rounds', 'vi_grad_basis_f64', 'vi_eval_grad_f64', 'vi_eval_err_f64', 'vi_eval_kernel_ms', 'vi_ctx_set_eval_timing', 'vi_solve_timing', 'vi_rccl_unique_id', 'vi_rccl_init', 'vi_rccl_bcast_f64', 'vi_rccl_destroy', 'vi_abi_version', 'vi_device_count', 'vi_ctx_create', 'vi_ctx_destroy', 'vi_ctx_sync', 'vi_last_error',
            'vi_dmalloc', 'vi_dfree', 'vi_h2d', 'vi_d2h', 'vi_d2h_side_mark', 'vi_d2h_side', 'vi_dmemset', 'vi_mem_info', 'vi_timer_start', 'vi_timer_stop_ms',
            'vi_model_create', 'vi_model_destroy', 'vi_basis_f64', 'vi_transform_f64', 'vi_eval_f64',
            'vi_eval_f64_host']

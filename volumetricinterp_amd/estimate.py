@@ -484,6 +484,47 @@ def ray_level_brackets(dist, index):
         return tuple(np.where(none, np.nan, a) for a in (np.minimum(below, above), np.maximum(below, above)))
 
 
+EXTREMUM_FIELDS = ('gdlat', 'gdlon', 'gdalt', 'value', 'gradient', 'hessian', 'status', 'iterations')
+Extremum = collections.namedtuple('Extremum', EXTREMUM_FIELDS)
+ExtremumError = collections.namedtuple('ExtremumError', EXTREMUM_FIELDS + ('position_covariance', 'value_error'))
+
+
+def local_maxima(value, index, alt_axis, kind='max'):
+    """The starts of Estimate.extremum from the column maps of ResidentGrid.peak on a (lat, lon, alt) grid: value and index
+    (T, nlat, nlon) - the peak of every column along altitude and its position on alt_axis, as g.peak(times, kind=kind) gives
+    them -, alt_axis the grid's altitudes.  Returns (t, i, j, alt): the positions, in C order, whose column peak is a number
+    (index >= 0) and strictly above (kind='min': below) those of its eight horizontal neighbours that are numbers - a tie with
+    a neighbour is no maximum, a NaN neighbour or the edge of the map does not count against one -, and the grid altitude
+    alt_axis[index] of that peak.  The coarse stage of a search in three dimensions: a maximum over altitude of every
+    column that is also a maximum among the columns around it.  On the host."""
+    if kind not in PEAK_HEIGHT_KINDS:
+        raise ValueError("kind must be 'max' or 'min', not %r" % (kind,))
+    alt = np.asarray(alt_axis, dtype=np.float64)
+    if alt.ndim != 1 or alt.size == 0:
+        raise ValueError('alt_axis must be a 1-D array with at least one sample')
+    value, index = np.asarray(value, dtype=np.float64), np.asarray(index)
+    if index.dtype.kind not in 'iu':
+        raise ValueError('index must be an integer array, not %s' % index.dtype)
+    if value.ndim != 3 or index.shape != value.shape:
+        raise ValueError('value and index must have one shape (T, nlat, nlon), not %r and %r' % (value.shape, index.shape))
+    index = index.astype(np.int64)
+    if index.size and (index.min() < -1 or index.max() >= alt.size):
+        raise ValueError('index must lie in [-1, %d)' % alt.size)
+    T, n, m = value.shape
+    v = PEAK_HEIGHT_KINDS[kind] * np.where(index >= 0, value, np.nan)
+    pad = np.full((T, n + 2, m + 2), np.nan)
+    pad[:, 1:-1, 1:-1] = v
+    top = ~np.isnan(v)
+    with np.errstate(invalid='ignore'):
+        for di in (0, 1, 2):
+            for dj in (0, 1, 2):
+                if (di, dj) != (1, 1):
+                    w = pad[:, di:di + n, dj:dj + m]
+                    top &= (v > w) | np.isnan(w)
+    t, i, j = np.nonzero(top)
+    return t, i, j, alt[index[t, i, j]]
+
+
 class Estimate(object):
     def __init__(self, coeff_filename, timetol=60., timeinterp=False, ctx=None):
         self.timetol = timetol
@@ -950,6 +991,114 @@ class Estimate(object):
                 with np.errstate(invalid='ignore', divide='ignore'):
                     derr[t, ok] = self.error(time, *pts, check_hull) / np.abs(res[2, t][ok])
         return RayLevelError(*(out + (derr.reshape(shape),)))
+
+    def extremum(self, times, gdlat, gdlon, gdalt, radius, kind='max', max_step=None, tol=1e-3, max_iter=48, check_hull=True,
+                 error=False):
+        """Maxima and minima in three dimensions: per start (gdlat, gdlon, gdalt) and time the point within `radius` metres of
+        the start, and inside the hull, at which the fitted parameter has its maximum (kind='min': minimum) - the centre of a
+        polar-cap patch or of a depletion -, the parameter there and its Hessian, whose principal curvatures are the size of the
+        patch.  peak_height, level_height and ray_peak search along a direction the caller chooses and give the extremum along
+        it; this one has no direction.  A safeguarded Newton iteration in ECEF on the analytic model itself: value, gradient and
+        Hessian are closed-form and come from one walk of the basis per iteration, the Hessian - a tensor - turned into the plain
+        Cartesian matrix of second derivatives, so that the iteration is exact; steps are limited to a trust length (max_step at
+        most), curvature of the wrong sign is floored, a step that lowers the value or leaves the region is taken back in part.
+        All starts and times in ONE library call (vi_eval_extremum_f64, kernel k_extremum_sph, include/vinterp.h has the
+        iteration); the hull test of every iterate is in the kernel, there is no host pass.
+
+        times: one naive-UTC datetime or a sequence of T of them; the coefficients of get_C per time, as peak_height takes
+        them.  gdlat, gdlon (degrees): the starts' columns, broadcast to one shape S.  gdalt, radius (metres): broadcast to
+        (T,) + S, as peak_height takes its start; with one time all four broadcast to S.  local_maxima makes the starts from
+        the maps of ResidentGrid.peak.  max_step: metres, one number, the longest step;
+        None: an eighth of each search's radius.  tol: the search stops when a step is at most tol metres.  max_iter: at most
+        10000.
+
+        Returns the named tuple (gdlat, gdlon, gdalt, value, gradient, hessian, status, iterations): gradient (T,) + S + (3,)
+        and hessian (T,) + S + (3, 3) along local east, north, up at the RETURNED point, the others (T,) + S (S for one time):
+        status 0  an interior extremum: the last step was an unmodified Newton step of at most tol, and the Hessian at the
+                  result is definite with the sign of the kind
+               1  converged without one: onto the boundary of the hull or of the ball, or at a point of the wrong curvature
+               2  not converged within max_iter; max_iter=0 evaluates the start
+               3  nothing to report: the start is outside the hull (check_hull) or NaN, radius is not finite and positive, or
+                  the record or the basis is not finite there
+        Position and value are NaN wherever status is not 0; gradient and hessian are those of the last iterate (NaN with
+        status 3).  gdlon comes from geodesy.ecef2geodetic, in (-180, 180].
+
+        error=True: the named tuple grows by (position_covariance, value_error), first order, NaN where status is not 0:
+        position_covariance (..., 3, 3) = H^-1 S H^-1 in east, north, up with S = gradient_covariance(frame='enu') at the point
+        and H the returned Hessian - the extremum is where the gradient is zero, so it moves by -H^-1 (error of the gradient),
+        the three-dimensional form of peak_height's sqrt(cov) / |curvature| - and value_error = error() there.  The existing
+        entries called once per time at the found points, not fused into the search.  Raises ValueError when the Estimate
+        holds no covariance.  sphharmlag only, at the orders of gradient."""
+        if kind not in PEAK_HEIGHT_KINDS:
+            raise ValueError("kind must be 'max' or 'min', not %r" % (kind,))
+        tol = float(tol)
+        if not (np.isfinite(tol) and tol > 0.):
+            raise ValueError('tol must be finite and positive, not %r' % (tol,))
+        if not isinstance(max_iter, (int, np.integer)) or isinstance(max_iter, bool) or not 0 <= max_iter <= 10000:
+            raise ValueError('max_iter must be an integer in [0, 10000], not %r' % (max_iter,))
+        if max_step is not None:
+            max_step = float(max_step)
+            if not (np.isfinite(max_step) and max_step > 0.):
+                raise ValueError('max_step must be finite and positive, not %r' % (max_step,))
+        if error:
+            self._need_covariance()
+        single = isinstance(times, dt.datetime)
+        times = [times] if single else list(times)
+        T, N = len(times), self.model.nbasis
+        args = tuple(np.asarray(v, dtype=np.float64) for v in (gdlat, gdlon, gdalt, radius))
+        try:
+            S = np.broadcast(*args).shape if single else np.broadcast(args[0], args[1]).shape
+        except ValueError:
+            raise ValueError('gdlat, gdlon, gdalt and radius do not broadcast to one shape')
+        full, P = (T,) + S, int(np.prod(S, dtype=np.int64))
+        try:
+            lat, lon, alt, rad = (np.ascontiguousarray(np.broadcast_to(v, full)).reshape(T, P) for v in args)
+        except ValueError:
+            raise ValueError('gdlat, gdlon, gdalt and radius must broadcast to the shape %r' % (full,))
+        C = np.empty((T, N))
+        for t, time in enumerate(times):
+            C[t] = self.get_C(time)[0]
+        shape = S if single else full
+        res, status, iters = np.full((13, T, P), np.nan), np.full((T, P), 3, dtype=np.int32), np.zeros((T, P), dtype=np.int32)
+        if T and P:
+            with np.errstate(invalid='ignore'):
+                x0 = np.ascontiguousarray(np.stack(geodesy.geodetic2ecef(lat, lon, alt)))
+            eq, F, htol = self._hull_args(check_hull)
+            with self.model.ctx.scope() as dev:
+                dx, dr, dC_ = dev.up(x0), dev.up(rad), dev.up(C)
+                dO, dS, dI = dev.empty((13, T, P)), dev.empty((T, P), np.int32), dev.empty((T, P), np.int32)
+                _lib.check(_lib.lib.vi_eval_extremum_f64(self.model.handle(), T, P, dx.ptr, dr.ptr, dC_.ptr,
+                                                         _ptr(None if eq is None else dev.up(eq)), F, htol,
+                                                         PEAK_HEIGHT_KINDS[kind], 0. if max_step is None else max_step,
+                                                         int(max_iter), tol, dO.ptr, dS.ptr, dI.ptr), 'vi_eval_extremum_f64')
+                res, status, iters = dO.download(), dS.download(), dI.download()
+        # geodetic points, and gradient and Hessian along east, north, up there: A g and A H A^T with the geodetic axes A
+        with np.errstate(invalid='ignore'):
+            plat, plon, palt = geodesy.ecef2geodetic(res[0], res[1], res[2])
+            sl, cl, so, co = (f(np.radians(v)) for v in (plat, plon) for f in (np.sin, np.cos))
+            zero = np.zeros_like(sl)
+            A = np.stack([np.stack([-so, co, zero], axis=-1), np.stack([-sl * co, -sl * so, cl], axis=-1),
+                          np.stack([cl * co, cl * so, sl], axis=-1)], axis=-2)                    # (T, P, 3, 3): rows e, n, u
+            grad = np.einsum('tpic,ctp->tpi', A, res[4:7])
+            hess = np.einsum('tpic,tpcd,tpjd->tpij', A, gradcov_matrix(res[7:13].reshape(6, T * P)).reshape(T, P, 3, 3), A)
+        value = res[3].copy()
+        for v in (plat, plon, palt, value):
+            v[status != 0] = np.nan
+        out = tuple(v.reshape(shape) for v in (plat, plon, palt, value)) + (grad.reshape(shape + (3,)),
+                                                                            hess.reshape(shape + (3, 3)),
+                                                                            status.reshape(shape), iters.reshape(shape))
+        if not error:
+            return Extremum(*out)
+        pcov, verr = np.full((T, P, 3, 3), np.nan), np.full((T, P), np.nan)
+        for t, time in enumerate(times):
+            ok = status[t] == 0
+            if ok.any():
+                pts = plat[t][ok], plon[t][ok], palt[t][ok]
+                cov = gradcov_matrix(self._gradient_covariance(time, *pts, check_hull, 'enu'))
+                Hi = np.linalg.inv(hess[t][ok])
+                pcov[t, ok] = np.einsum('pij,pjk,plk->pil', Hi, cov, Hi)
+                verr[t, ok] = self.error(time, *pts, check_hull)
+        return ExtremumError(*(out + (pcov.reshape(shape + (3, 3)), verr.reshape(shape))))
 
     def _ray_search(self, times, start, end, coords, per, names, tol, max_iter, error):
         """What ray_peak and ray_level share ahead of their library call: the arguments checked, the rays as (3, P) planar end

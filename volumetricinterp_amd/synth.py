@@ -61,6 +61,19 @@ def chapman_record(alt, nmax=3e11, hm=300e3, scale=50e3):
     return value, 0.05 * value + 1e10
 
 
+def patch_record(lat, lon, alt, lat0=78.5, lon0=263.0, sigma=120e3, amp=1.0, **chapman):
+    """One noise-free record of chapman_record's layer with a horizontal enhancement - a polar-cap patch, an object with a
+    centre in three dimensions (Estimate.extremum): the layer at `alt` times 1 + amp exp(-d^2 / 2 sigma^2), d the ECEF distance
+    (m) between the point (lat, lon) and the centre (lat0, lon0), both taken at 300 km of altitude.  amp=0 is chapman_record
+    itself; amp < 0 a depletion.  **chapman: nmax, hm, scale of chapman_record.  Returns value, error (5 % + 1e10 of the
+    value, as chapman_record forms them)."""
+    from .geodesy import geodetic2ecef
+    layer = chapman_record(alt, **chapman)[0]
+    d2 = sum((p - c)**2 for p, c in zip(geodetic2ecef(lat, lon, 300e3), geodetic2ecef(lat0, lon0, 300e3)))
+    value = layer * (1. + amp * np.exp(-d2 / (2. * sigma**2)))
+    return value, 0.05 * value + 1e10
+
+
 def unix_times(T, t0=1480286700.0, dt=60.0):
     """(T,2) start/end Unix times, 2016-11-27T22:45:00Z onwards, 1-minute records."""
     s = t0 + dt * np.arange(T)
