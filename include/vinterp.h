@@ -803,6 +803,17 @@ int  vi_eigvals_f64(vi_ctx* ctx, int64_t B, int32_t N, double* d_X, double* d_la
 int  vi_qr_similarity_f64(vi_ctx* ctx, int64_t B, int32_t N, const double* d_X, const double* d_y, double* d_X1,
                           double* d_y1, double* d_Q);
 
+/* Stage-test entry of the three kernels of that pre-conditioner, called as the solves call them.  vi_qr_hh_doubles(N) is
+ * the packed size of one system's reflector set in doubles (v_0 .. v_{N-1} in the layout of csrc/vi_qr.hip, then the N
+ * taus), 0 where the pre-conditioner does not serve N.  vi_qr_stage_f64 factors B systems: d_y is read at row d_rec[i]
+ * (row i with d_rec NULL); d_X1 (may be d_X) and d_y1 receive Q^T X Q and Q^T y; d_hh receives the reflector sets
+ * hh_stride doubles apart (0: packed; the gaps of a larger stride are not written); d_RPt (B x N x N) receives the rows of
+ * R P^T.  Then d_C (B x N, or NULL) becomes Q c by the vector back-transformation and d_V (B x N x N, vector j contiguous,
+ * or NULL) becomes Q V by the matrix one.  N outside the served range: VI_ERR_UNSUPPORTED, nothing written. */
+int64_t vi_qr_hh_doubles(int32_t N);
+int  vi_qr_stage_f64(vi_ctx* ctx, int64_t B, int32_t N, const double* d_X, const double* d_y, const int32_t* d_rec,
+                     double* d_X1, double* d_y1, double* d_hh, int64_t hh_stride, double* d_RPt, double* d_C, double* d_V);
+
 /* Stage-test entry of the forming step of vi_basis_solve_f64 (csrc/vi_walk.hip, or the library chain with
  * VINTERP_WALK_FORM=blas; the routine vi_basis_solve_f64 itself calls before its eigen-solve).  For B (record, basis,
  * alpha) triples, with A = AWA[rec[i]], V = V[basis[i]] stored "row k = basis vector k" and D2 = D2[basis[i]]:

@@ -252,7 +252,10 @@ __global__ __launch_bounds__(RT <= 8 ? 320 : 640) void k_qr_sim(
                 pmax = take ? ov : pmax;
                 p = take ? oi : p;
             }
-            if (!(pmax > 0.0)) return true;          // what is left is exactly zero: the remaining reflectors are identities
+            // what is left is exactly zero: the remaining reflectors are identities.  A squared norm below the normal range
+            // (columns of 1e-162 .. 1e-154 beside a matrix maximum of 1) ends the phase the same way: tau ~ 1 / pmax would
+            // overflow to inf and spread NaN, and what is left stays in the rows of R P^T as it is.
+            if (!(pmax >= 2.2250738585072014e-308)) return true;
             double* vb = vcur + (k & 1) * NR + l;
             if ((p >> 1) == (tid >> 3)) {
                 const bool second = p & 1;
@@ -581,4 +584,33 @@ extern "C" int vi_qr_similarity_f64(vi_ctx* c, int64_t B, int32_t N, const doubl
         VI_HIP(hipMemcpyAsync(d_Q + b * (int64_t)N * N, eye.data(), eye.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     VI_HIP(hipStreamSynchronize(c->stream));
     return vi_qr_back_mat(c, B, N, hhp, d_Q, 0);
+}
+
+// Stage-test entry (tests/test_gpu_qr_geometry.py): what the three kernels themselves produce, called the way the engine
+// calls them.  vi_qr_precond with the caller's d_RPt as its scratch (it is left holding the rows of R P^T), d_rec and
+// hh_stride passed through, d_X1 allowed to be d_X; then vi_qr_back_vec on d_C and vi_qr_back_mat on d_V (either may be
+// NULL) with the same reflectors.
+extern "C" int64_t vi_qr_hh_doubles(int32_t N)
+{
+    return vi_qr_supported(N) ? (int64_t)(vi_qr_hh_bytes(N) / sizeof(double)) : 0;
+}
+
+extern "C" int vi_qr_stage_f64(vi_ctx* c, int64_t B, int32_t N, const double* d_X, const double* d_y, const int32_t* d_rec,
+                               double* d_X1, double* d_y1, double* d_hh, int64_t hh_stride, double* d_RPt, double* d_C,
+                               double* d_V)
+{
+    VI_REQUIRE(c && d_X && d_y && d_X1 && d_y1 && d_hh && d_RPt, "null argument");
+    VI_REQUIRE(B >= 0 && N > 0, "bad size");
+    if (B == 0) return VI_OK;
+    if (!vi_qr_supported(N)) {
+        vi_set_error("vi_qr_stage_f64: N=%d outside the range of the register-resident QR", N);
+        return VI_ERR_UNSUPPORTED;
+    }
+    VI_REQUIRE(hh_stride == 0 || hh_stride >= vi_qr_hh_doubles(N), "hh_stride smaller than a reflector set");
+    VI_HIP(hipSetDevice(c->device));
+    int rc;
+    if ((rc = vi_qr_precond(c, B, N, d_X, d_y, d_rec, d_X1, d_y1, d_hh, d_RPt, hh_stride)) != VI_OK) return rc;
+    if (d_C && (rc = vi_qr_back_vec(c, B, N, d_hh, d_C, hh_stride)) != VI_OK) return rc;
+    if (d_V && (rc = vi_qr_back_mat(c, B, N, d_hh, d_V, hh_stride)) != VI_OK) return rc;
+    return VI_OK;
 }

@@ -73,11 +73,13 @@ _lib._sig('vi_gcv_terms_f64', C.c_int, _lib.VOIDP, C.c_int64, C.c_int64, C.c_int
 _lib._sig('vi_eigvals_f64', C.c_int, _lib.VOIDP, C.c_int64, C.c_int32, _lib.VOIDP, _lib.VOIDP, _lib.VOIDP)
 _lib._sig('vi_qr_similarity_f64', C.c_int, _lib.VOIDP, C.c_int64, C.c_int32, _lib.VOIDP, _lib.VOIDP, _lib.VOIDP, _lib.VOIDP,
           _lib.VOIDP)
+_lib._sig('vi_qr_hh_doubles', C.c_int64, C.c_int32)
+_lib._sig('vi_qr_stage_f64', C.c_int, _lib.VOIDP, C.c_int64, C.c_int32, *([_lib.VOIDP] * 6), C.c_int64, *([_lib.VOIDP] * 3))
 _lib._sig('vi_walk_form_f64', C.c_int, _lib.VOIDP, C.c_int64, C.c_int32, *([_lib.VOIDP] * 10))
 _lib._sig('vi_brent_host_one_f64', C.c_int, _lib.VOIDP, C.c_int32, C.c_int64, *([_lib.VOIDP] * 11), C.c_int32, C.c_int32,
           C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _lib.VOIDP, _lib.VOIDP)
 _lib._sig('vi_brent_warm_supported', C.c_int, C.c_int32, C.c_int64)
-_lib.EXPORTS += ['vi_brent_warm_supported', 'vi_brent_host_one_f64', 'vi_brent_warm_f64', 'vi_exp10_f64', 'vi_max_sweeps', 'vi_cold_max_sweeps', 'vi_qr_similarity_f64', 'vi_walk_form_f64', 'vi_rotation_log_bytes', 'vi_decompose_f64', 'vi_warm_finish_f64', 'vi_warm_rebase_f64', 'vi_reg_floor_f64', 'vi_basis_solve_f64', 'vi_warm_chi2_one_f64', 'vi_gcv_terms_f64', 'vi_warm_prepare_f64', 'vi_warm_solve_f64', 'vi_eigvals_f64', 'vi_normal_eq_f64', 'vi_form_system_f64', 'vi_solve_trunc_f64', 'vi_chi2_f64', 'vi_cov_f64']
+_lib.EXPORTS += ['vi_brent_warm_supported', 'vi_brent_host_one_f64', 'vi_brent_warm_f64', 'vi_exp10_f64', 'vi_max_sweeps', 'vi_cold_max_sweeps', 'vi_qr_similarity_f64', 'vi_qr_hh_doubles', 'vi_qr_stage_f64', 'vi_walk_form_f64', 'vi_rotation_log_bytes', 'vi_decompose_f64', 'vi_warm_finish_f64', 'vi_warm_rebase_f64', 'vi_reg_floor_f64', 'vi_basis_solve_f64', 'vi_warm_chi2_one_f64', 'vi_gcv_terms_f64', 'vi_warm_prepare_f64', 'vi_warm_solve_f64', 'vi_eigvals_f64', 'vi_normal_eq_f64', 'vi_form_system_f64', 'vi_solve_trunc_f64', 'vi_chi2_f64', 'vi_cov_f64']
 
 
 
